@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Benchmark of the per-image inference hot path on MI355X (contract: see the round prompt / DESIGN.md).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,11 @@ A step = one pass of the hot path over one batch of synthetic proxy representati
 ResNet-18 encoder -> distribution head -> matrix-Fisher sampling (num_samples=100) -> SMPL forward over
 B*(N+2) meshes -> per-vertex uncertainty (BASELINE.json configs[1]: batch 64, 256x256, num_samples 100).
 Inputs are resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds every leg after the timed region (the CPU
+baseline, secondary.{mesh_bf16x3, lbs_unfused, latency_b1, from_rgb, stress_n1000} and the live rocprofv3 traffic passes); an
+explicit value of a leg's own option (--cpu-images, --split-steps, ...) is honoured with or without --full.
+--dump-outputs DIR writes the result arrays of the last timed step as DIR/<name>.npy (float32).
 """
 import argparse
 import json
@@ -33,6 +38,30 @@ ENCODER_GFLOP_PER_IMAGE = 6.279      # 3.139 GMAC per
 MFMA_FP32_PEAK_TF = 157.3            # MI355X_MICROARCH.md: dense fp32 matrix peak
 INPUT_SETS = 2                       # different input batches rotated through the timed loop
 SET_STRIDE = 1 << 16                 # global image index distance between the input sets (> any global batch)
+# the legs after the timed region: their option's value under --full when the option is not given; without --full they are off
+FULL_LEG_DEFAULTS = {"split_steps": 16, "cpu_images": 64, "from_rgb_steps": 16, "latency_reps": 40, "stress_steps": 8,
+                     "live_traffic": "auto", "lbs_unfused_reps": 12}
+DUMP_BYTES = 60 * 10 ** 6            # --dump-outputs: array data written per rank, at most
+
+
+def dump_outputs(res, out_dir, suffix=""):
+    """The tensors of one step's result dict as <out_dir>/<name><suffix>.npy in float32, DUMP_BYTES in all.  Arrays are taken
+    smallest first, each whole when it fits its even share of what is left of the budget, else as a fixed, seeded sample of its
+    rows (the last axis kept whole: e.g. xyz triples of verts_samples), in row order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(((k, v) for k, v in res.items() if torch.is_tensor(v)), key=lambda kv: kv[1].numel())
+    budget = DUMP_BYTES // 4
+    for i, (name, t) in enumerate(items):
+        share = budget // (len(items) - i)
+        t = t.detach().float()
+        if t.numel() > share:
+            rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1, 1)
+            k = max(1, share // rows.shape[1])
+            idx = torch.randint(rows.shape[0], (k,), generator=torch.Generator().manual_seed(0)).unique()    # sorted
+            t = rows[idx.to(rows.device)]
+        budget -= t.numel()
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), t.cpu().numpy())
 
 
 def synthetic_inputs(lo, hi):
@@ -238,11 +267,12 @@ def main():
                     help="arithmetic of the shared-shape mesh kernel's pose blend GEMM in the HEADLINE run: f32 = v_mfma_f32_32x32x2_f32 (default, the "
                          "reference's arithmetic type in every instruction); bf16x3 = fp32 operands as three bf16 pieces, six exact piece products on the "
                          "bf16 matrix pipe, fp32 accumulation (fp32 accuracy, other bits; SMPL.mesh_arith)")
-    ap.add_argument("--split-steps", type=int, default=16,
-                    help="after the timed region: pipelined steps with SMPL.mesh_arith = 'bf16x3' for secondary.mesh_bf16x3 (0 = skip)")
+    ap.add_argument("--split-steps", type=int, default=None,
+                    help="after the timed region: pipelined steps with SMPL.mesh_arith = 'bf16x3' for secondary.mesh_bf16x3 (0 = skip; default: 16 with --full, else 0)")
     ap.add_argument("--unfused-mesh", action="store_true", help="blend GEMM + LBS as two kernels (the unfused definition) instead of the fused mesh kernel")
     ap.add_argument("--trace-steps", action="store_true", help="print host-side per-step times to stderr (debugging)")
-    ap.add_argument("--cpu-images", type=int, default=64, help="images in the CPU-baseline sample (0 = skip); 64 = one full batch, SURVEY 8(d)")
+    ap.add_argument("--cpu-images", type=int, default=None,
+                    help="images in the CPU-baseline sample (0 = skip); 64 = one full batch, SURVEY 8(d) (default: 64 with --full, else 0)")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
                     help="process-group backend when launched by torch.distributed.run: nccl (= RCCL over xGMI, the product "
                          "setting) or gloo (functional runs with more ranks than GPUs: ranks share devices, collectives are "
@@ -250,22 +280,34 @@ def main():
     ap.add_argument("--as-rank", type=int, nargs=2, metavar=("R", "W"), default=None,
                     help="single process, no process group: do exactly the work rank R of a W-rank job would do (its image "
                          "shard, its Philox offsets) -- what the multi-rank tests compare the per-rank checksums against")
-    ap.add_argument("--from-rgb-steps", type=int, default=16,
-                    help="after the timed region: steps of the PCIe-inclusive path from host RGB crops + keypoints for secondary.from_rgb (0 = skip)")
+    ap.add_argument("--from-rgb-steps", type=int, default=None,
+                    help="after the timed region: steps of the PCIe-inclusive path from host RGB crops + keypoints for secondary.from_rgb (0 = skip; "
+                         "default: 16 with --full, else 0)")
     ap.add_argument("--from-rgb-variant", choices=("default", "no-copy", "nchw"), default="default",
                     help="diagnostic: 'no-copy' runs the from-RGB loop on device-resident crops (isolates the cost of the H2D copies); "
                          "'nchw' builds the (B,18,D,D) tensor and lets the encoder split it into phase frames (the round-4 route)")
-    ap.add_argument("--latency-reps", type=int, default=40,
-                    help="after the timed region: batch-1, num_samples=50 calls timed one by one for secondary.latency_b1 (0 = skip)")
-    ap.add_argument("--stress-steps", type=int, default=8,
+    ap.add_argument("--latency-reps", type=int, default=None,
+                    help="after the timed region: batch-1, num_samples=50 calls timed one by one for secondary.latency_b1 (0 = skip; default: 40 with "
+                         "--full, else 0)")
+    ap.add_argument("--stress-steps", type=int, default=None,
                     help="after the timed region (one GPU only): pipelined steps of BASELINE configs[4] (batch 16, num_samples 1000) "
-                         "for secondary.stress_n1000 (0 = skip)")
-    ap.add_argument("--live-traffic", choices=("auto", "off"), default="auto",
+                         "for secondary.stress_n1000 (0 = skip; default: 8 with --full, else 0)")
+    ap.add_argument("--live-traffic", choices=("auto", "off"), default=None,
                     help="auto (one GPU only): measure roofline.traffic in this run with two rocprofv3 --pmc passes over a three-step sub-run "
-                         "(~15 s); off / unavailable: read it from the committed PMC summary under profiles/ and flag it traffic_imported")
-    ap.add_argument("--lbs-unfused-reps", type=int, default=12,
-                    help="after the timed region: launches of the unfused blend + LBS pair timed for secondary.lbs_unfused (0 = skip)")
+                         "(~15 s); off / unavailable: read it from the committed PMC summary under profiles/ and flag it traffic_imported "
+                         "(default: auto with --full, else off)")
+    ap.add_argument("--lbs-unfused-reps", type=int, default=None,
+                    help="after the timed region: launches of the unfused blend + LBS pair timed for secondary.lbs_unfused (0 = skip; default: 12 "
+                         "with --full, else 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg after the timed region with its default (see FULL_LEG_DEFAULTS); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result arrays of the last timed step as DIR/<name>.npy (float32; at most 60 MB, larger arrays as a fixed, "
+                         "seeded sample of their rows; with several ranks: DIR/<name>_rank<r>.npy)")
     args = ap.parse_args()
+    for k, v in FULL_LEG_DEFAULTS.items():
+        if getattr(args, k) is None:
+            setattr(args, k, v if args.full else ("off" if k == "live_traffic" else 0))
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X (HIP) device; there is no CPU fallback for the product path")
@@ -335,6 +377,8 @@ def main():
         return on
 
     def run_steps(first, count, on_result=None):
+        if count <= 0:
+            return None
         # input_ready=False: the inputs are resident and complete before the loop starts (nothing produces them on a stream)
         pipe.enc_events = ev_lists["enc"] if sample_events(first) else None
         ticket = pipe.submit(xs[first % INPUT_SETS], input_ready=False)
@@ -382,15 +426,23 @@ def main():
         sharding.batch_metric_sums(res, accumulate=sums)      # the running total is formed by the checksum's own second launch
 
     if not args.no_pipeline:
-        run_steps(args.warmup, args.steps, accumulate)
+        last = run_steps(args.warmup, args.steps, accumulate)
     else:
+        last = None
         for i in range(args.steps):
-            accumulate(infer(net, smpl, xs[(args.warmup + i) % INPUT_SETS], num_samples=N, use_mean_shape=True,
-                             seed=1234 + args.warmup + i, image_offset=offset_of(args.warmup + i)))
+            res = infer(net, smpl, xs[(args.warmup + i) % INPUT_SETS], num_samples=N, use_mean_shape=True,
+                        seed=1234 + args.warmup + i, image_offset=offset_of(args.warmup + i))
+            accumulate(res)
+            last = res if i + 1 == args.steps else None      # no step's outputs outlive it but the last one's
+            del res
     per_rank, total = sharding.gather_metric_sums(sums)                 # the one collective of the run
     torch.cuda.synchronize()
     barrier()
     dt = sharding.all_reduce_max(time.perf_counter() - t0)               # the slowest rank's time
+    if args.dump_outputs and last is not None:
+        # before any leg below runs another step on the pipeline's buffers
+        dump_outputs(last, args.dump_outputs, "_rank%d" % rank if world > 1 else "")
+    del last
 
     # LBS kernel time from HIP events recorded around each launch on the launch stream
     M = B * (N + 2)

@@ -468,7 +468,7 @@ def test_bench_line_has_every_leg(dev):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--cpu-images", "1", "--lbs-unfused-reps", "2",
-           "--latency-reps", "3", "--from-rgb-steps", "8", "--stress-steps", "3"]
+           "--latency-reps", "3", "--from-rgb-steps", "8", "--stress-steps", "3", "--full"]
     p = subprocess.run(cmd, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert p.returncode == 0, p.stderr.decode(errors="replace")[-3000:]
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
