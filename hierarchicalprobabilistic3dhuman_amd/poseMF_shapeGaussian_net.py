@@ -29,6 +29,7 @@ from torch import nn
 from torch.distributions import Normal
 
 from . import _capi
+from .device_state import DeviceStateModule
 from .resnet import resnet18
 from .rigid_transform_utils import rotmat_to_rot6d
 from .sharding import effective_cpus
@@ -58,12 +59,9 @@ def immediate_parents_to_all_parents(immediate_parents):
     return all_parents
 
 
-def _invalidate_after_load(module, incompatible_keys):
-    """load_state_dict post hook (fires for sub-modules too); module level so that the module stays picklable."""
-    module.invalidate()
+class PoseMFShapeGaussianNet(DeviceStateModule):
+    SWITCHES = ("latency_mode", "svd_mode", "svd_flavor", "composite_head")
 
-
-class PoseMFShapeGaussianNet(nn.Module):
     def __init__(self, smpl_parents, config):
         super().__init__()
         self.config = config
@@ -97,9 +95,7 @@ class PoseMFShapeGaussianNet(nn.Module):
         # kinematic depth levels: joints whose ancestors are all in earlier levels
         depth = [len(self.parents_dict[j]) for j in range(self.num_joints)]
         self.levels = [[j for j in range(self.num_joints) if depth[j] == d] for d in range(max(depth) + 1)]
-        self._prepared = None
         self._pinned_bufs = {}
-        self.register_load_state_dict_post_hook(_invalidate_after_load)
         self.composite_head = True     # joint loop through hps_head_pose_levels (one call) instead of per-level Python
         self.svd_mode = "device"       # "device": in-kernel gesdd-faithful SVD; "host": MKL sgesdd round trip (the routine itself)
         self.svd_flavor = None         # None: the rounding flavour of this host's MKL (calibrated); 0 / 1 force one
@@ -118,22 +114,9 @@ class PoseMFShapeGaussianNet(nn.Module):
         reproduces this host's LAPACK bit for bit (_capi.svd_flavor)."""
         return _capi.svd_flavor() if self.svd_flavor is None else int(self.svd_flavor)
 
-    # ---- kernel-side weights; rebuilt after .to() / load_state_dict ----
-    def _apply(self, fn, *args, **kwargs):
-        self._prepared = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def invalidate(self):
-        """Drop the kernel-side weight copies / pointer tables (rebuilt by the next forward).  Automatic after .to() and after
-        any load_state_dict that reaches this module, directly or through a parent (post hook); call it by hand after
-        editing parameters in place."""
-        self._prepared = None
-
     def __getstate__(self):
-        # copy.deepcopy / pickle: the pointer tables hold raw device addresses of THIS module's tensors and the staging
-        # buffers are page-locked host memory -- a copy must rebuild its own
-        state = self.__dict__.copy()
-        state["_prepared"] = None
+        # copy.deepcopy / pickle: the staging buffers are page-locked host memory -- a copy makes its own
+        state = super().__getstate__()
         state["_pinned_bufs"] = {}
         return state
 
@@ -151,6 +134,7 @@ class PoseMFShapeGaussianNet(nn.Module):
             self._pinned_bufs[key] = buf
         return buf[:numel]
 
+    # ---- kernel-side weights; rebuilt after .to() / load_state_dict / a switch ----
     def prepare(self):
         dev = self.fc1.weight.device
         t = lambda w: w.detach().float().t().contiguous()

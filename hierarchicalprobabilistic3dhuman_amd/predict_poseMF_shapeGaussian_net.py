@@ -21,7 +21,6 @@ from .resnet import FilledStemFrames
 
 
 FUSE_JOINTS_AND_UNCERTAINTY = True     # False: hps_smpl_joints and hps_vertex_uncertainty as two launches (the cross-check of the tests; same bits)
-_SHARED_SHAPE_TABLES = weakref.WeakKeyDictionary()      # smpl model -> ((B, N, device), mesh_row, group_rows) of the last infer() layout
 
 
 @torch.no_grad()
@@ -77,15 +76,10 @@ def infer(pose_shape_model, smpl_model, proxy_rep_input, num_samples=50, use_mea
     # _after_unc to another stream, and every result must come from the caller's pool -- see SMPL.forward, "ordered")
     unc = torch.empty(B, smpl_model.num_verts, **f32)
     shared = None
-    if use_mean_shape and hasattr(smpl_model, "shared_shape_tables"):
+    if use_mean_shape and hasattr(smpl_model, "layout_tables"):
         # every mesh of image b has the betas loc[b]: the shape blend is formed once per image (hps_smpl_mesh_fused_shared_shape)
-        key = (B, N, dev)
-        tables = _SHARED_SHAPE_TABLES.get(smpl_model)
-        if tables is None or tables[0] != key:
-            rows = list(range(B)) + list(range(B)) + [b for b in range(B) for _ in range(N)]          # [mode | T-pose | samples]
-            tables = (key,) + smpl_model.shared_shape_tables(rows)
-            _SHARED_SHAPE_TABLES[smpl_model] = tables
-        shared = (loc, tables[1], tables[2])
+        rows = lambda: list(range(B)) + list(range(B)) + [b for b in range(B) for _ in range(N)]          # [mode | T-pose | samples]
+        shared = (loc,) + smpl_model.layout_tables((B, N), rows)
     # the joint regression of the call's meshes and the uncertainty pass read what the mesh kernel has just written and do not depend
     # on each other: one launch (hps_joints_and_uncertainty) when the sample count takes the register-resident pass
     deferred = {}
@@ -180,6 +174,7 @@ class InferencePipeline:
         # wait that polls beside a chain of small kernels doubled that chain's time, tests/dev/graph_time.py.  Normal priority.)
         self.head_stream = torch.cuda.Stream()
         self.enc_stream = None        # created by the first submit (its kind depends on the batch size)
+        self._seen = (None, None)     # the encoder's and the head's device states at the last submit
         self.mesh_stream = None
         self._smpl_done = None
         self._enc_tail = None         # the event recorded last on the encoder's stream, while nothing has been queued behind it
@@ -280,7 +275,6 @@ class InferencePipeline:
                 self.mesh_stream = None
         if self.enc_stream is None:
             self.enc_stream = torch.cuda.Stream()
-        self._fresh_streams = True
 
     @torch.no_grad()
     def submit(self, proxy_rep_input=None, input_ready=None, make_input=None):
@@ -307,21 +301,17 @@ class InferencePipeline:
             if proxy_rep_input is None:
                 raise _capi.HpsError("InferencePipeline: call caller_stream(batch) before the first submit(make_input=...)")
             self._setup_streams(proxy_rep_input.shape[0])
-        # (re-armed whenever the encoder's prepared weights are gone -- load_state_dict / invalidate() / .to(): the next forward runs the
-        # lazy prepare() on the ENCODER's stream and must not read parameters a device-to-device copy is still writing on the caller's;
-        # the head's weights are re-prepared on its stream the same way: ADVICE r5)
-        if getattr(self.net.image_encoder, "_prepared", True) is None or getattr(self.net, "_prepared", True) is None:
-            self._fresh_streams = True
-        if getattr(self, "_fresh_streams", False):
-            # ONE-TIME ordering of the side streams behind whatever the caller has queued so far: parameters still
-            # being written by a device-to-device load_state_dict, BN folding of a preceding warm-up infer(), ... -- whatever
-            # `input_ready` says about the INPUT, the encoder's lazy prepare() and first convolutions (and the head) must not
-            # read weights that are still in flight.  Costs nothing in steady state.
+        # ONE-TIME ordering of the side streams behind whatever the caller has queued so far: parameters still being
+        # written by a device-to-device load_state_dict, BN folding of a preceding warm-up infer(), ... -- whatever `input_ready` says
+        # about the INPUT, the encoder's lazy prepare() and first convolutions (and the head) must not read weights that are still in
+        # flight.  Again whenever the encoder's or the head's device state has been replaced (load_state_dict / invalidate() / .to() /
+        # a switch): the next forward re-prepares on the side streams.  Costs nothing in steady state.
+        seen, self._seen = self._seen, (self.net.image_encoder.device_state(), self.net.device_state())
+        if seen[0] is not self._seen[0] or seen[1] is not self._seen[1]:
             self.enc_stream.wait_stream(main)
             self.head_stream.wait_stream(main)
             if self.mesh_stream is not None and self.mesh_stream != main:
                 self.mesh_stream.wait_stream(main)
-            self._fresh_streams = False
         if input_ready is None:
             ready = torch.cuda.Event()
             ready.record(main)
@@ -500,7 +490,10 @@ class GraphedInfer:
         self.input_shape = tuple(input_shape)
         self._slots = [None] * max(1, int(slots))
         self._k = 0
-        self._net_key = None
+
+    def _state(self):
+        """What a captured launch sequence depends on beyond its own buffers; held by the slot, it keeps that memory alive."""
+        return (self.net.image_encoder.device_state(), self.net.device_state(), self.smpl.device_state(), FUSE_JOINTS_AND_UNCERTAINTY)
 
     def _capture(self, dev):
         stream = torch.cuda.Stream()
@@ -519,7 +512,7 @@ class GraphedInfer:
         from . import sampling_utils
         accepted = sampling_utils.last_accepted[0]
         return dict(stream=stream, x=x, key_dev=key_dev, key_host=key_host, graph=graph, out=out, accepted=accepted,
-                    copied=None, done=None)
+                    copied=None, done=None, state=self._state())
 
     @torch.no_grad()
     def __call__(self, proxy_rep_input, seed=None, image_offset=0, wait=True):
@@ -527,36 +520,32 @@ class GraphedInfer:
         row by row into the slot's static input: no concatenation).  ``wait=False``: the caller's stream is NOT made to wait for the
         replay -- returns (out, done_event) and the caller waits for the event before it reads ``out`` (the predict loop issues call
         k + 1 first, so that two replays overlap)."""
-        from .sampling_utils import _philox_seed
+        from .sampling_utils import _philox_seed, philox_key
         items = proxy_rep_input if isinstance(proxy_rep_input, (list, tuple)) else None
         shape = ((len(items),) + tuple(items[0].shape[1:])) if items is not None else tuple(proxy_rep_input.shape)
         if shape != (self.batch,) + self.input_shape:
             raise _capi.HpsError("GraphedInfer was captured for inputs of shape %s, got %s" % ((self.batch,) + self.input_shape, shape))
-        dev = torch.device("cuda", torch.cuda.current_device())
-        net_key = (id(getattr(self.net.image_encoder, "_prepared", None)), id(getattr(self.net, "_prepared", None)),
-                   bool(getattr(self.net, "latency_mode", False)))
-        if self._net_key != net_key and any(s is not None for s in self._slots):
-            self._slots = [None] * len(self._slots)            # weights re-prepared / mode switched: the graphs hold the old pointers
         i = self._k % len(self._slots)
         self._k += 1
-        if self._slots[i] is None:
-            self._slots[i] = self._capture(dev)
-            self._net_key = (id(getattr(self.net.image_encoder, "_prepared", None)), id(getattr(self.net, "_prepared", None)),
-                             bool(getattr(self.net, "latency_mode", False)))
         s = self._slots[i]
+        if s is not None and any(a is not b for a, b in zip(s["state"], self._state())):
+            torch.cuda.synchronize()             # every graph is stale: none may still run when its memory goes back to the allocator
+            self._slots = [None] * len(self._slots)
+            s = None
+        if s is None:
+            s = self._slots[i] = self._capture(torch.device("cuda", torch.cuda.current_device()))
         if s["copied"] is not None:
             s["copied"].synchronize()            # the key copy that last used the page-locked pair (``slots`` calls ago) has run
-        s["key_host"][0] = _philox_seed(seed) & 0x7FFFFFFFFFFFFFFF
+        s["key_host"][0] = philox_key(_philox_seed(seed), signed=True)
         s["key_host"][1] = int(image_offset) * self.net.num_joints
         caller = torch.cuda.current_stream()
         st = s["stream"]
         st.wait_stream(caller)                   # the input's producer (and whoever still reads the slot's previous outputs)
         with torch.cuda.stream(st):
-            if items is not None:
-                for r, it in enumerate(items):
-                    s["x"][r:r + 1].copy_(it, non_blocking=True)
-            else:
-                s["x"].copy_(proxy_rep_input, non_blocking=True)
+            for dst, src in (zip(s["x"].split(1), items) if items is not None else [(s["x"], proxy_rep_input)]):
+                dst.copy_(src, non_blocking=True)
+                if src.is_cuda:
+                    src.record_stream(st)        # the caller may drop its input before the copy has run
             s["key_dev"].copy_(s["key_host"], non_blocking=True)
             s["copied"] = torch.cuda.Event()
             s["copied"].record(st)
@@ -697,9 +686,9 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         # each, and the host needs longer to issue them than the device to run them.  Each (batch, num_samples) is captured ONCE in
         # hipGraphs (GraphedInfer, two slots on two streams); the loop issues image k + 1 before it waits for image k, so two replays
         # overlap on the mostly idle chip.  Same kernels, same order, same bits as infer().
-        key = ("graph", id(smpl_model), num_samples, batch_size, torch.cuda.current_device())
+        key = ("graph", num_samples, batch_size, torch.cuda.current_device())
         cached = _PREDICT_PIPELINES.get(pose_shape_model)
-        if cached is None or cached[0] != key:
+        if cached is None or cached[0] != key or cached[1].smpl is not smpl_model:
             cached = (key, GraphedInfer(weakref.proxy(pose_shape_model), smpl_model, batch_size, num_samples, use_mean_shape=True, slots=2), None)
             _PREDICT_PIPELINES[pose_shape_model] = cached
         graphed = cached[1]
@@ -731,9 +720,9 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         return
     # the pipeline (its streams, the encoder's frame buffers bound to them, the upload slots) is kept between calls, per model (weakly
     # referenced side table: nothing is attached to the module, so copies / pickles of it are unaffected)
-    key = (id(smpl_model), num_samples, batch_size, torch.cuda.current_device())
+    key = (num_samples, batch_size, torch.cuda.current_device())
     cached = _PREDICT_PIPELINES.get(pose_shape_model)
-    if cached is None or cached[0] != key:
+    if cached is None or cached[0] != key or cached[1].smpl is not smpl_model:
         # the cached pipeline refers to the model through a weak proxy: a strong reference from the table's value to its key would
         # keep the model (and the encoder's frame buffers) alive for ever
         cached = (key, InferencePipeline(weakref.proxy(pose_shape_model), smpl_model, num_samples=num_samples, use_mean_shape=True),

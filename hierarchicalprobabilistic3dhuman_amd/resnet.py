@@ -11,6 +11,7 @@ import torch
 from torch import nn
 
 from . import _capi
+from .device_state import DeviceStateModule
 
 
 class _ConvBN:
@@ -274,16 +275,6 @@ class FilledStemFrames:
         pass
 
 
-class _FrameCache(dict):
-    """Per-(batch shape, stream) activation frames and launch lists; device-bound scratch, never copied or pickled."""
-
-    def __deepcopy__(self, memo):
-        return _FrameCache()
-
-    def __reduce__(self):
-        return (_FrameCache, ())
-
-
 class BasicBlock(nn.Module):
     """models/resnet.py:40-78 (parameter container; executed by ResNet._run_block)."""
     expansion = 1
@@ -299,13 +290,10 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
 
-def _invalidate_after_load(module, incompatible_keys):
-    """load_state_dict post hook (fires for sub-modules too); module level so that the module stays picklable."""
-    module.invalidate()
-
-
-class ResNet(nn.Module):
+class ResNet(DeviceStateModule):
     """models/resnet.py:125-217 for BasicBlock stacks."""
+
+    SWITCHES = ("_winograd", "_latency", "composite", "fused_pool", "fold_downsample", "stem_reads_nchw")
 
     def __init__(self, layers, in_channels):
         super().__init__()
@@ -326,7 +314,6 @@ class ResNet(nn.Module):
             elif isinstance(m, nn.BatchNorm2d):
                 nn.init.constant_(m.weight, 1)
                 nn.init.constant_(m.bias, 0)
-        self._prepared = None
         # kernel-selection modes are properties of the MODEL (set_winograd / set_latency_mode) and survive .to() / load_state_dict:
         # prepare() re-applies them to the rebuilt _ConvBN objects
         self._winograd = True
@@ -346,8 +333,6 @@ class ResNet(nn.Module):
         # profiles/r06_ab.txt).  False = phase split + frame-fed kernel (the cross-check of the tests; callers that fill the frames
         # themselves -- stem_frames -- use the frame-fed kernel either way).
         self.stem_reads_nchw = True
-        self._frames = _FrameCache()
-        self.register_load_state_dict_post_hook(_invalidate_after_load)
 
     def _make_layer(self, planes, blocks, stride=1):
         downsample = None
@@ -360,23 +345,12 @@ class ResNet(nn.Module):
             blks.append(BasicBlock(planes, planes))
         return nn.Sequential(*blks)
 
-    # ---- weight preparation (BN folding, k-major filters); redone after .to() / load_state_dict ----
-    def _apply(self, fn, *args, **kwargs):
-        self._prepared = None
-        self._frames = _FrameCache()
-        return super()._apply(fn, *args, **kwargs)
-
+    # ---- weight preparation (BN folding, k-major filters); redone after .to() / load_state_dict / a switch ----
     def set_winograd(self, on):
         """Product default True: the stride-1 3x3 layers of layer1-3 run as Winograd F(2x2, 3x3) (csrc/conv_wino.hip); False runs
         every layer on the direct implicit-GEMM kernel (csrc/conv_pad.hip) -- the cross-check of the tests."""
         self._winograd = bool(on)
-        self._apply_modes(self._prepared or self.prepare())
-
-    def _apply_modes(self, prep):
-        for c in [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]:
-            c.latency = self._latency
-            c.use_winograd = self._winograd and not self._latency      # latency mode runs every layer on the direct kernel
-        self._frames = _FrameCache()          # cached launch lists belong to the previous selection
+        self._prepared or self.prepare()
 
     def set_latency_mode(self, on=True):
         """Per-model switch for latency-bound deployments (the reference's own operating point is ONE image per call,
@@ -388,22 +362,7 @@ class ResNet(nn.Module):
         depend on the batch size within a mode; between the modes they differ in the last bits (another summation order, same
         1e-4 feature tolerance against the reference -- tests/test_gpu_net.py)."""
         self._latency = bool(on)              # switching it off restores whatever set_winograd selected before
-        self._apply_modes(self._prepared or self.prepare())
-
-    def invalidate(self):
-        """Drop the folded BatchNorm / filter copies and the cached launch lists; the next forward rebuilds them from the
-        current parameters.  Called automatically by .to() and by any load_state_dict that reaches this module (also through
-        a parent: nn.Module.load_state_dict recurses with _load_from_state_dict and never calls a child's load_state_dict
-        override, so the reset hangs on a post hook).  Call it by hand after editing parameters in place."""
-        self._prepared = None
-        self._frames = _FrameCache()
-
-    def __getstate__(self):
-        # copies / pickles never carry device-bound caches (raw pointers into the original's tensors)
-        state = self.__dict__.copy()
-        state["_prepared"] = None
-        state["_frames"] = _FrameCache()
-        return state
+        self._prepared or self.prepare()
 
     def prepare(self):
         cin = self.conv1.in_channels
@@ -413,9 +372,16 @@ class ResNet(nn.Module):
             for blk in layer:
                 down = _ConvBN(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None
                 prep["blocks"].append((_ConvBN(blk.conv1, blk.bn1), _ConvBN(blk.conv2, blk.bn2), down))
+        for c in [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]:
+            c.latency = self._latency
+            c.use_winograd = self._winograd and not self._latency      # latency mode runs every layer on the direct kernel
         self._prepared = prep
-        self._apply_modes(prep)               # (also drops the launch lists: they hold pointers to the previous filters)
         return prep
+
+    @property
+    def _frames(self):
+        """The activation frame sets of the current device state, by (batch shape, stream) key."""
+        return {key: entry[0] for key, entry in self.device_state().get("frames", {}).items()}
 
     # ---- halo-padded activation frames: owned by the module, zeroed once, only interiors are ever written ----
     def _frame_set(self, prep, B, C, H, W, device, frames=False):
@@ -424,12 +390,12 @@ class ResNet(nn.Module):
         stem_wino = stem.stem_winograd_ok(C, H, W)
         fused_pool = bool(stem_wino and self.fused_pool)
         from_nchw = bool(fused_pool and self.stem_reads_nchw and not frames)
-        key = (B, C, H, W, str(device), _capi.stream().value, stem_wino, fused_pool, from_nchw, bool(self.fold_downsample))
-        fs = self._frames.get(key)
-        if fs is not None:
-            return fs
-        if len(self._frames) >= 6:                       # a handful of batch shapes / streams at most
-            self._frames.pop(next(iter(self._frames)))
+        key = (B, C, H, W, _capi.stream().value, from_nchw)          # (switches and layer modes: one device state each)
+        return self._derived("frames", key, lambda: self._new_frame_set(prep, B, C, H, W, device, stem_wino, fused_pool, from_nchw),
+                             limit=6)                # a handful of batch shapes / streams at most
+
+    def _new_frame_set(self, prep, B, C, H, W, device, stem_wino, fused_pool, from_nchw):
+        stem = prep["stem"]
         z = lambda *shape: torch.zeros(*shape, device=device, dtype=torch.float32)
         # input frame of the direct stem: channels as the stem's filters expect them (row mode: row_c; Cin % 32 == 0: cin_p), an even
         # number of columns; zero channels / a zero column are part of the convolution's zero padding
@@ -503,7 +469,6 @@ class ResNet(nn.Module):
         ops.append(_capi.EncOp(kind=_capi.ENC_AVGPOOL, x=y.data_ptr(), y=None, B=B, H=h, W=w, Cin=y.shape[3], ipad=1))
         fs["ops"] = (_capi.EncOp * len(ops))(*ops)
         fs["variants"] = self._variant_state(prep)
-        self._frames[key] = fs
         return fs
 
     @staticmethod

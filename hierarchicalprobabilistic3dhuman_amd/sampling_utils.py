@@ -52,7 +52,7 @@ def _launch(pose_U, pose_S, pose_V, num_samples, n_prop, b, eps=None, w=None, dr
                C, nj, num_samples, n_prop, float(b), _m_star(b) if m_star is None else float(m_star),
                P(eps) if eps is not None else None, P(w) if w is not None else None,
                _capi.iptr(draw_idx) if draw_idx is not None else None,
-               int(seed) & 0xFFFFFFFFFFFFFFFF, int(call_offset),
+               philox_key(seed), int(call_offset),
                _capi.ptr(seed_dev, torch.int64) if seed_dev is not None else None, _MAX_ROUNDS,
                P(R), P(quat) if quat is not None else None, _capi.iptr(accepted), _capi.stream())
     if ev is not None:
@@ -89,6 +89,13 @@ def _host_stream_sampling(pose_U, pose_S, pose_V, num_samples, n_prop, b, bingha
         first = int(fails[0])
         assign[first:] += 1          # call `first` retries with the next pair; later calls shift along
         draw(1)
+
+
+def philox_key(seed, signed=False):
+    """The 64 key bits hps_mf_sample takes for an integer ``seed`` (modulo 2^64): unsigned, or ``signed`` as the two's complement
+    int64 that holds the same bits in a seed_dev tensor."""
+    key = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return key - (1 << 64) if signed and key >> 63 else key
 
 
 def _philox_seed(seed):

@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 from . import _capi
+from .device_state import DeviceStateModule
 from .configs import SMPLX_EXTRA_VERTEX_IDS
 from .smpl_data import resolve_smpl_model, load_extra_joint_regressors, parents_from_kintree
 
@@ -32,11 +33,12 @@ def _round_up(x, m):
     return (x + m - 1) // m * m
 
 
-class SMPL(nn.Module):
+class SMPL(DeviceStateModule):
     """models/smpl_official.py:12-41.  ``model_path``: directory holding SMPL_<GENDER>.pkl, a pkl path,
     or a dict of arrays (e.g. ``smpl_data.synthetic_smpl_model()``).  ``model_files_dir`` may point at the
     reference's model_files/ (extra joint regressors); the packaged copies are used otherwise."""
 
+    SWITCHES = ("fused_mesh", "picked_joints", "shared_shape", "mesh_arith", "pad_v_posed")
     NUM_JOINTS = 24
     NUM_BODY_JOINTS = 23
 
@@ -63,7 +65,6 @@ class SMPL(nn.Module):
         # pipe, fp32 accumulation -- fp32 accuracy (as close to the float64 twin as "f32"), not the same bits (include/hps.h:
         # hps_smpl_mesh_fused_shared_shape_bf16x3).  Applies where the shared-shape form applies; every other call is "f32".
         self.mesh_arith = "f32"
-        self._bsplit = None
 
         f32 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float32)
         v_template = np.asarray(model["v_template"], np.float64)
@@ -179,30 +180,27 @@ class SMPL(nn.Module):
         dev = self.v_template.device
         return torch.from_numpy(full).to(dev), torch.from_numpy(groups.reshape(-1)).to(dev)
 
+    def layout_tables(self, layout, mesh_rows):
+        """shared_shape_tables(mesh_rows()) kept in the device state for a few ``layout`` keys (infer(): (B, N))."""
+        return self._derived("layouts", layout, lambda: self.shared_shape_tables(mesh_rows()))
+
     def _blend_matrix_split(self, with_shape_rows=False):
-        """The panel-permuted blend matrix as bf16 piece planes in MFMA fragment order (once per model and device): the 207 pose rows
+        """The panel-permuted blend matrix as bf16 piece planes in MFMA fragment order (once per device state): the 207 pose rows
         (shared shapes) or, ``with_shape_rows``, all num_betas + 207 rows (the shape blend inside the GEMM)."""
-        dev = self._bmat_p.device
-        if self._bsplit is None or self._bsplit[0] != dev:
-            self._bsplit = (dev, {})
-        cache = self._bsplit[1]
-        if with_shape_rows not in cache:
+        def build():
             first, rows = (0, self.num_betas + self._n_pose) if with_shape_rows else (self.num_betas, self._n_pose)
             n = _capi.load(dev=_capi._use_dev).hps_smpl_split_bf16x3_bytes(rows, self._np_fused)
-            buf = torch.empty(n, dtype=torch.uint8, device=dev)
+            buf = torch.empty(n, dtype=torch.uint8, device=self._bmat_p.device)
             _capi.call("hps_smpl_split_bf16x3", _capi._P(self._bmat_p.data_ptr() + 4 * first * self._np_fused), rows, self._np_fused,
                        self._np_fused, 192, _capi._P(buf.data_ptr()), _capi.stream())
-            cache[with_shape_rows] = buf
-        return cache[with_shape_rows]
+            return buf
+        return self._derived("bsplit", with_shape_rows, build)
 
     def _one_shape_tables(self, mp):
         """(mesh_row, group_rows) of the bf16x3 kernel for a call whose meshes do NOT share shapes: one template row (v_template) for all."""
         dev = self.v_template.device
-        key = (dev, mp)
-        if getattr(self, "_one_shape", (None,))[0] != key:
-            groups = torch.tensor([0, 0, 32], dtype=torch.int32).repeat(mp // 32)
-            self._one_shape = (key, torch.zeros(mp, dtype=torch.int32, device=dev), groups.to(dev))
-        return self._one_shape[1], self._one_shape[2]
+        return self._derived("one_shape", mp, lambda: (torch.zeros(mp, dtype=torch.int32, device=dev),
+                                                        torch.tensor([0, 0, 32], dtype=torch.int32).repeat(mp // 32).to(dev)))
 
     # ------------------------------------------------------------------------------------------
     def forward(self, betas=None, body_pose=None, global_orient=None, transl=None, pose2rot=True,

@@ -459,6 +459,49 @@ def test_graphed_infer_equals_infer_and_draws_new_samples_on_every_replay(dev, n
     assert torch.equal(o1["verts_samples"], w1["verts_samples"]) and torch.equal(o2["verts_samples"], w2["verts_samples"])
 
 
+def test_graphs_follow_every_change_of_the_device_state(dev, net_gpu, smpl_gpu, golden_input):
+    """a GraphedInfer replay after each change its launches depend on -- the Winograd switch, latency mode on
+    and off, eager calls at other shapes on more stream / shape keys than the encoder's frames and SMPL's layout tables keep, the mesh
+    arithmetic -- equals a fresh eager infer() with the current settings, bit for bit; so does a seed at or above 2^63."""
+    from hierarchicalprobabilistic3dhuman_amd.predict_poseMF_shapeGaussian_net import GraphedInfer
+    x = golden_input.to(dev)
+    enc = net_gpu.image_encoder
+    keys = ("pose_F", "R_samples", "verts_mode", "verts_tpose", "verts_samples", "joints_samples", "unc", "cam")
+    g = GraphedInfer(net_gpu, smpl_gpu, batch=2, num_samples=7, slots=2)
+
+    def check(case, seed=5):
+        want = infer(net_gpu, smpl_gpu, x, num_samples=7, seed=seed)
+        for _ in range(2):                       # both slots
+            got = g(x, seed=seed)
+            for k in keys:
+                assert torch.equal(got[k], want[k]), (case, k)
+
+    try:
+        check("capture")
+        enc.set_winograd(False)
+        check("winograd off")
+        enc.set_winograd(True)
+        net_gpu.set_latency_mode(True)
+        check("latency on")
+        net_gpu.set_latency_mode(False)
+        check("latency off")
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        for i, (B, N) in enumerate(((1, 3), (3, 5), (4, 2), (5, 9), (6, 4), (7, 3), (3, 6))):
+            with torch.cuda.stream(side if i % 2 else torch.cuda.current_stream()):
+                infer(net_gpu, smpl_gpu, torch.rand(B, 18, 256, 256, device=dev), num_samples=N, seed=1)
+        torch.cuda.current_stream().wait_stream(side)
+        check("other shapes and streams")
+        smpl_gpu.mesh_arith = "bf16x3"
+        check("bf16x3")
+        check("seed 2^63 + 5", seed=2 ** 63 + 5)
+    finally:
+        enc.set_winograd(True)
+        net_gpu.set_latency_mode(False)
+        smpl_gpu.mesh_arith = "f32"
+    torch.cuda.synchronize()
+
+
 def test_bench_line_has_every_leg(dev):
     """The line the driver records: one short run of bench.py with all of its legs on (headline, lbs_unfused, latency_b1,
     from_rgb), every field the contract names present and consistent."""

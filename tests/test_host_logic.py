@@ -282,6 +282,72 @@ def test_kernel_selection_modes_survive_invalidation():
     assert all(not c.use_winograd and not c.latency for c in convs()), "set_latency_mode(False) must not force Winograd back on"
 
 
+def test_device_state_is_replaced_by_every_reset_and_by_nothing_else(net_cpu):
+    """the encoder, the head and SMPL each keep their derived device data in one dict, device_state() -- the token a
+    captured launch sequence is checked against.  invalidate(), load_state_dict, .to() and a new value of any kernel switch replace it;
+    repeated calls and a switch assigned its current value (bench.py assigns them unconditionally) do not; a held state keeps its
+    tensors alive."""
+    import copy
+    import gc
+    import weakref
+    net = copy.deepcopy(net_cpu[0])
+    enc = net.image_encoder
+    smpl = SMPL(smpl_data.synthetic_smpl_model(0))
+
+    def replaced(action, *models):
+        before = [m.device_state() for m in models]
+        assert all(m.device_state() is b for m, b in zip(models, before))
+        action()
+        return all(m.device_state() is not b for m, b in zip(models, before))
+
+    for m in (enc, net, smpl):
+        assert replaced(m.invalidate, m)
+        assert replaced(lambda: m.load_state_dict(m.state_dict()), m)
+        assert replaced(lambda: m.to("cpu"), m)
+    assert replaced(lambda: net.load_state_dict(net.state_dict()), net, enc)          # through the parent
+    assert replaced(lambda: net.to("cpu"), net, enc)
+    switches = {enc: ("composite", "fused_pool", "fold_downsample", "stem_reads_nchw"),
+                net: ("latency_mode", "svd_mode", "svd_flavor", "composite_head"),
+                smpl: ("fused_mesh", "picked_joints", "shared_shape", "mesh_arith", "pad_v_posed")}
+    other = {"svd_mode": "host", "svd_flavor": 0, "mesh_arith": "bf16x3"}
+    for m, names in switches.items():
+        for name in names:
+            v = getattr(m, name)
+            assert not replaced(lambda: setattr(m, name, v), m), name
+            assert replaced(lambda: setattr(m, name, other.get(name, not v)), m), name
+            assert replaced(lambda: setattr(m, name, v), m), name
+    for on in (False, True):
+        assert replaced(lambda: enc.set_winograd(on), enc)
+        assert not replaced(lambda: enc.set_winograd(on), enc)
+    for on in (True, False):
+        assert replaced(lambda: net.set_latency_mode(on), net, enc)
+        assert not replaced(lambda: net.set_latency_mode(on), net) and not replaced(lambda: net.set_latency_mode(on), enc)
+    net.invalidate()
+    enc.invalidate()
+    held = (enc.device_state(), net.device_state())
+    alive = [weakref.ref(enc.prepare()["stem"].wk), weakref.ref(net.prepare()["fc1_wt"])]
+    assert enc.device_state() is held[0] and net.device_state() is held[1]          # the first prepare fills an empty state
+    assert replaced(net.prepare, net) and replaced(enc.prepare, enc)                 # a later one replaces it
+    net.invalidate()
+    enc.invalidate()
+    gc.collect()
+    assert all(r() is not None for r in alive)
+    del held
+    gc.collect()
+    assert all(r() is None for r in alive)
+
+
+def test_philox_key_keeps_the_seeds_bits():
+    """GraphedInfer stores the Philox key in an int64 tensor: the two's complement of the 64 bits eager infer() passes by value."""
+    from hierarchicalprobabilistic3dhuman_amd.sampling_utils import philox_key
+    for seed in (0, 5, 2 ** 62, 2 ** 63 - 1, 2 ** 63, 2 ** 63 + 5, 2 ** 64 - 1, 2 ** 64 + 3, -1, -2 ** 63):
+        u, s = philox_key(seed), philox_key(seed, signed=True)
+        assert 0 <= u < 2 ** 64 and -2 ** 63 <= s < 2 ** 63 and u == seed % 2 ** 64
+        assert int(np.array([s], np.int64).view(np.uint64)[0]) == u
+        if 0 <= seed < 2 ** 63:
+            assert s == u == seed
+
+
 def test_bf16x3_split_is_exact_and_the_dropped_products_are_below_one_fp32_rounding():
     """The arithmetic behind SMPL.mesh_arith = "bf16x3" (csrc/mesh_split.hip), stated on the host with torch's own conversions: an fp32
     number is EXACTLY the sum of three round-to-nearest bf16 pieces; the six piece products the kernel issues reproduce the fp32 product to
