@@ -16,10 +16,8 @@
 // (column = lane & 31) and 16 meshes (rows (r & 3) + 8 (r >> 2) + 4 (lane >> 5)) -- x, y, z in registers, no transpose.
 // K loop: 16-row chunks of both operands (k-major, exactly as they lie in HBM) land in LDS by LDS-DMA, one chunk ahead;
 // fragments are conflict-free 32-lane row reads.  MFMA k order = blend_gemm_kernel's (pairs (2i, 2i+1), ascending):
-// identical bits.  Epilogue: the skinning transforms A of the tile's meshes are DMA'd into the LDS that held the operand
-// chunks, in two passes of 32 meshes (36 KiB for SMPL: the first / second half of each wave's 32 meshes), and every lane
-// skins its vertex for its 16 meshes with skin_vertex<K> (the function lbs_kernel uses) and stores 12-byte records:
-// 384 contiguous bytes per mesh per wave instruction.
+// identical bits.  Epilogue: csrc/mesh_epilogue.h (shared with mesh_split_kernel), the tile skinned in two passes of 32 meshes with the
+// transforms A DMA'd into the LDS that held the operand chunks (36 KiB for SMPL).
 //
 // Why small workgroups: tools/mfma_valu_overlap.hip shows that on gfx950 fp32 VALU work does NOT overlap with
 // v_mfma_f32_32x32x2_f32, neither in one wave nor across the waves of a SIMD (times add) -- so the epilogue's VALU
@@ -27,20 +25,13 @@
 // <= 128 registers put four independent workgroups on a CU (one wave of each per SIMD), each in its own phase.  The first
 // version (512 threads, 64 meshes x 128 vertices, all 72 KiB of A at once: two workgroups per CU) ran 0.60 ms at 6 528
 // meshes against 0.46 ms for its K loop alone.
-// Block -> (mesh tile, panel): block ids congruent mod 8 (one XCD) own the same mesh tiles, and every XCD walks the
-// panels in order, so an XCD's L2 holds its own xt / A slices plus the few panels in flight; bmat_p streams from the
-// memory-side cache once per XCD.
 
-#include <type_traits>
-
-#include "hps_common.h"
+#include "mesh_epilogue.h"
 
 namespace hps {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int FM = 64;            // meshes per workgroup tile
-constexpr int FV = 64;            // vertices per panel
+constexpr int FV = MESH_PANEL;    // vertices per panel
 constexpr int FN = 3 * FV;        // blend-matrix columns per panel
 constexpr int FBK = 16;           // K rows per chunk
 constexpr int FT = 256;           // threads per workgroup
@@ -51,8 +42,8 @@ constexpr int F_BP = FBK * FN / 256;                     // ... of the blend mat
 static_assert(F_XP == FW && F_BP % FW == 0, "DMA pieces must divide evenly over the waves");
 
 // ABL: profiling ablations, dev library only (hps_dev_mesh_fused); the product instantiates ABL = 0.
-// JC: joints per mesh as a compile-time constant (24 = SMPL: every LDS offset of the epilogue folds into an immediate), 0 = runtime J;
-// HAS_T: a per-mesh translation is added (smplx SMPL.forward step (7)).
+// JC: joints per mesh as a compile-time constant (24 = SMPL: every LDS offset of the epilogue folds into an immediate), 0 = runtime J.
+// HAS_T, PICK, VS: see mesh_epilogue.h.
 // TAIL: k-pairs of the LAST chunk that carry data (compile-time: a run-time bound inside the unrolled MFMA run cost 30 % -- the
 // branch per k-step broke the pinned schedule and put an accumulator into scratch); 8 = the whole chunk.
 // ST: operand chunks resident in LDS (K-loop stages).  2 = the throughput form (four workgroups per CU cover each other's fetch
@@ -66,10 +57,7 @@ static_assert(F_XP == FW && F_BP % FW == 0, "DMA pieces must divide evenly over 
 // default: utils/sampling_utils.py:178-179) -- so the shape blend is not part of the GEMM at all: ``v_template`` is then the (R, V, 3) array
 // of the R distinct shaped templates v_template + S beta_r (hps_smpl_v_shaped: smplx lbs step (1), once per image), ``xt`` / ``bmat_p`` hold
 // the 207 pose rows only (K = 207 -> kp = 208 = thirteen whole chunks: 312 MFMAs per wave instead of 327) and the lane adds its mesh's
-// shaped template where the plain form adds v_template: v_posed = v_shaped + P pf, in smplx's own order of the two additions.  A lane's 16
-// meshes lie in ONE group of 32 consecutive meshes; ``group_rows`` describes the group as (row A, row B, split): local mesh < split has
-// template row A, the others row B (a tile of sample meshes spans at most two images) -- both rows are fetched before the K loop;
-// split < 0 marks a group whose rows change more than once (the mode / T-pose meshes: one image each): its lanes fetch per mesh by ``mesh_row``.
+// shaped template where the plain form adds v_template: v_posed = v_shaped + P pf, in smplx's own order of the two additions.
 template <int K, int ABL, int JC, bool HAS_T, int TAIL = FBK / 2, int ST = 2, bool PICK = false, bool VS = false>
 __global__ __launch_bounds__(FT, 4) void mesh_fused_kernel(
     const float* __restrict__ xt, const float* __restrict__ bmat_p, const float* __restrict__ v_template,
@@ -80,44 +68,11 @@ __global__ __launch_bounds__(FT, 4) void mesh_fused_kernel(
     typedef __attribute__((address_space(3))) void* lptr_t;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // union: ST operand chunks | A of 32 of the tile's meshes
 
-    // tiles_m_per_xcd == 0: fewer than eight mesh tiles -- plain mapping (block = panel * tiles_m + tile), consecutive panels on
-    // consecutive XCDs.  (With the XCD-aware mapping below a call of ONE mesh tile -- one image at a time, 52 meshes -- had all of
-    // its 108 working blocks at ids = 0 mod 8: on ONE XCD's 32 CUs, the other seven idle: 55-58 us per call.)
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int tile_m = tiles_m_per_xcd ? (local % tiles_m_per_xcd) * 8 + xcd : (int)blockIdx.x % tiles_m;
-    const int panel = tiles_m_per_xcd ? local / tiles_m_per_xcd : (int)blockIdx.x / tiles_m;
-    if (tile_m >= tiles_m) return;
+    int tile_m, panel;
+    if (!mesh_block(tiles_m, tiles_m_per_xcd, tile_m, panel)) return;
     const int m0 = tile_m * FM;
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kl = lane >> 5, il = lane & 31;
-    const int wm = wave >> 1, wn = wave & 1;
-
-    // this lane's vertex and its skinning weights (kept in registers through the K loop)
-    const int v = panel * FV + wn * 32 + il;
-    const bool live_v = v < V;
-    const int vc = live_v ? v : V - 1;
-    int idx[K];
-    float w[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        idx[k] = w_idx[(size_t)vc * K + k] * 12;
-        w[k] = w_val[(size_t)vc * K + k];
-    }
-    f3 vt, vtb;
-    int split = 32;
-    if (VS) {
-        const int32_t* gr = group_rows + 3 * __builtin_amdgcn_readfirstlane((m0 + wm * 32) >> 5);      // wave-uniform: scalar loads
-        const int row_a = gr[0], row_b = gr[1];
-        split = gr[2];
-        vt = reinterpret_cast<const f3*>(v_template)[(size_t)row_a * V + vc];
-        vtb = reinterpret_cast<const f3*>(v_template)[(size_t)row_b * V + vc];
-    } else {
-        vt = reinterpret_cast<const f3*>(v_template)[vc];
-        vtb = vt;
-    }
-    const int split_lane = split - 4 * kl;                    // local mesh 4 kl + dr < split  <=>  dr < split_lane
-    const int pick = PICK && live_v ? pick_slot[vc] : -1;     // this lane's slot in the compact array of regressor vertices, or -1
+    const MeshLane<K> L = mesh_lane<K, FM / 32, VS, PICK>(panel, m0, V, w_idx, w_val, v_template, group_rows, pick_slot);
+    const int lane = L.lane, wave = L.wave, kl = L.kl, il = L.il, wm = L.wm, wn = L.wn;
 
     // LDS-DMA pieces (1 KiB each): a chunk is F_XP pieces of xt rows ([FBK][FM]) and F_BP of bmat_p rows ([FBK][FN]);
     // wave w moves mesh-operand piece w and blend-matrix pieces w, w + 4, w + 8.
@@ -217,90 +172,12 @@ __global__ __launch_bounds__(FT, 4) void mesh_fused_kernel(
     for (int c = 0; c + 1 < nchunks; ++c) do_chunk(std::integral_constant<int, FBK / 2>(), c, ABL != 4);
     do_chunk(std::integral_constant<int, TAIL>(), nchunks - 1, false);
 
-    if (ABL == 3) {                                        // K loop only: one never-taken store keeps the accumulators alive
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += acc[0][r] + acc[1][r] + acc[2][r];
-        if (t == 12345.678f) verts[0].x = t;
+    if (ABL == 3) {                                        // K loop only
+        mesh_keep_acc(acc, verts);
         return;
     }
-
-    // Skinning, two passes of 32 meshes: pass p stages A of meshes [16 p, 16 p + 16) and [32 + 16 p, 32 + 16 p + 16) of the
-    // tile -- the meshes of accumulator registers r = 8 p .. 8 p + 7 of both mesh groups -- as LDS slots 0..15 and 16..31.
-    const int a_stride = JC ? JC * 12 : J * 12;
-    const int half_bytes = 16 * a_stride * 4;              // one contiguous source range of J * 768 bytes (whole 1 KiB pieces iff J % 4 == 0;
-                                                           // the last piece is cut by the off < valid mask otherwise: tested with J = 22)
-    const int slot0 = wm * 16 + 4 * kl;                    // the lane's first slot
-    int aoff[K];                                           // float offset of A[slot0][joint_k] in LDS
-#pragma unroll
-    for (int k = 0; k < K; ++k) aoff[k] = slot0 * a_stride + idx[k];
-    char* const vbase = reinterpret_cast<char*>(verts) + (size_t)(m0 + wm * 32) * V * 12;      // wave-uniform
-    const unsigned voff = ((unsigned)(4 * kl) * (unsigned)V + (unsigned)v) * 12u;              // per lane
-    char* const pbase = PICK ? reinterpret_cast<char*>(picked) + (size_t)(m0 + wm * 32) * n_picked * 12 : nullptr;
-    const unsigned poff = PICK ? ((unsigned)(4 * kl) * (unsigned)n_picked + (unsigned)max(pick, 0)) * 12u : 0u;
-    // MANY (VS only): the wave's group of 32 meshes has more than two templates (split < 0: the mode / T-pose meshes, one image each --
-    // 4 of 204 groups at B = 64, N = 100) and every mesh fetches its own inside the loop.  That form is a COPY of the epilogue, chosen by one
-    // wave-uniform branch in front of it: a load -- or a branch around one -- inside the loop of the common form puts a vmcnt(0) there,
-    // which on gfx950 also waits for the previous mesh's store, and splits the loop body into blocks hipcc does not schedule across
-    // (measured: +7 us on the whole launch, more than the fifteen MFMAs per wave the K = 207 form saves).  Both copies pass the same
-    // barriers, so the waves of a workgroup may take different ones.
-    auto epilogue = [&](auto many_c) __attribute__((always_inline)) {
-    constexpr bool MANY = decltype(many_c)::value;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        __syncthreads();                                   // operand chunks / the previous pass's transforms are dead
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const int mh = m0 + 32 * h + 16 * pass;                                              // first mesh of this range
-            const int valid = max(0, min(16, M - mh)) * a_stride * 4;                          // bytes that exist in `a`
-            const float* a_src = a + (size_t)mh * a_stride;
-            for (int piece = wave; piece * 1024 < half_bytes; piece += FW) {
-                const int off = piece * 1024 + lane * 16;
-                if (off < valid) lds_dma16((unsigned)off, a_src, lds0 + (unsigned)(h * half_bytes + piece * 1024));
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // branch-free: the per-lane parts of every address were formed once, the per-r parts are compile-time / wave-uniform
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const int r = 8 * pass + q;
-            const int dr = (r & 3) + 8 * (r >> 2);         // mesh row step of accumulator register r (within the wave's 32)
-            const int ds = (q & 3) + 8 * (q >> 2);         // ... within the pass's 16 slots of this mesh group
-            const int m = m0 + wm * 32 + 4 * kl + dr;
-            float tx = 0.f, ty = 0.f, tz = 0.f;
-            if (HAS_T) {
-                const float* t = transl + (size_t)min(m, M - 1) * 3;
-                tx = t[0]; ty = t[1]; tz = t[2];
-            }
-            f3 base = vt;
-            if (VS && !MANY) {                             // template A / B of the group by the split: three selects, no load
-                const bool first = dr < split_lane;
-                base.x = first ? vt.x : vtb.x; base.y = first ? vt.y : vtb.y; base.z = first ? vt.z : vtb.z;
-            }
-            if (VS && MANY) base = reinterpret_cast<const f3*>(v_template)[(size_t)mesh_row[min(m, M - 1)] * V + vc];
-            f3 pv;
-            pv.x = base.x + acc[0][r]; pv.y = base.y + acc[1][r]; pv.z = base.z + acc[2][r];
-            f3 o;
-            if (ABL == 1) {
-                o = pv;
-            } else {
-                int ao[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) ao[k] = aoff[k] + ds * a_stride;
-                o = skin_vertex<K>(smem, ao, w, pv, tx, ty, tz);
-            }
-            // Pin the result in front of the guard: hipcc otherwise sinks the whole skinning of a mesh (12 LDS reads, the FMAs)
-            // into the guarded store's block, where the reads cannot be issued under the previous mesh's arithmetic and the
-            // block's entry waits vmcnt(0) -- i.e. for the previous mesh's store -- on account of the v_template load.
-            asm volatile("" :: "v"(o.x), "v"(o.y), "v"(o.z));
-            if (live_v && m < M) *reinterpret_cast<f3*>(vbase + (size_t)dr * V * 12 + voff) = o;
-            if (PICK && pick >= 0 && m < M) *reinterpret_cast<f3*>(pbase + (size_t)dr * n_picked * 12 + poff) = o;
-        }
-    }
-    };
-    if (VS && split < 0) epilogue(std::true_type());
-    else epilogue(std::false_type());
+    mesh_epilogue<K, JC, FM / 32, HAS_T, PICK, VS, ABL == 1 ? EPI_NO_SKIN : EPI_ALL>(smem, L, acc, m0, M, V, J, a, transl, v_template,
+                                                                                       mesh_row, verts, picked, n_picked);
 }
 
 #ifdef HPS_DEV_BUILD
@@ -324,8 +201,7 @@ static int launch_fused_cfg(const float* xt, const float* bmat_p, const float* v
                      && g_mesh_stages != 2
 #endif
         ;
-    const int tiles_m_per_xcd = tiles_m >= 8 ? ceil_div(tiles_m, 8) : 0;          // 0: plain block mapping (see the kernel)
-    const dim3 grid(tiles_m_per_xcd ? tiles_m_per_xcd * 8 * n_panels : tiles_m * n_panels);
+    const MeshGrid g = mesh_grid(tiles_m, n_panels);
     // the last chunk's data-carrying k-pairs: SMPL (K = 10 + 207 -> kp = 218) has 5 of 8; that case is instantiated for the product
     // configuration, every other tail runs the whole (zero-padded) chunk
     const int tail = (kp - FBK * ((kp + FBK - 1) / FBK - 1)) / 2;
@@ -333,9 +209,9 @@ static int launch_fused_cfg(const float* xt, const float* bmat_p, const float* v
 #define HPS_MESH_LAUNCH(...)                                                                                                       \
     do {                                                                                                                           \
         if (int rc = grant_lds<&mesh_fused_kernel<__VA_ARGS__>>(160 * 1024, "hps_smpl_mesh_fused")) return rc;                    \
-        hipLaunchKernelGGL((mesh_fused_kernel<__VA_ARGS__>), grid, dim3(FT), lds, s, xt, bmat_p, v_template, a, w_idx, w_val, J,   \
-                           transl, reinterpret_cast<f3*>(verts), M, V, kp, mp, np, tiles_m, tiles_m_per_xcd, pick_slot, pk, n_picked, \
-                           mesh_row, group_rows);                                                                                 \
+        hipLaunchKernelGGL((mesh_fused_kernel<__VA_ARGS__>), dim3(g.blocks), dim3(FT), lds, s, xt, bmat_p, v_template, a, w_idx,   \
+                           w_val, J, transl, reinterpret_cast<f3*>(verts), M, V, kp, mp, np, tiles_m, g.tiles_m_per_xcd,           \
+                           pick_slot, pk, n_picked, mesh_row, group_rows);                                                         \
     } while (0)
     if constexpr (K == 4 && JC == 24 && ABL == 0 && !HAS_T) {     // shared shapes (VS): SMPL's 207 pose rows, thirteen whole chunks
         if (group_rows) {

@@ -17,20 +17,17 @@
 // features once per call: 5 MB):  dst[col tile][16-row chunk][piece s][k half kl][column w][8 bf16]  -- a (tile, chunk) block is one
 // contiguous run (6 KiB per 64 meshes, 18 KiB per 192-column panel), so a K-loop stage is 24 linear 1 KiB LDS-DMA pieces, and a
 // fragment is one conflict-free ds_read_b128 per lane (32 consecutive lanes read 512 consecutive bytes).
-// Tile, block mapping and the skinning epilogue are mesh_fused_kernel's (csrc/mesh_fused.hip), the VS / PICK form.
+// Tile, block mapping and the skinning epilogue (VS, PICK, no translation) are csrc/mesh_epilogue.h's, shared with mesh_fused_kernel.
 //
 // Replaces smplx 0.1.26 lbs steps pose_feature @ posedirs, W @ A and T @ v_posed (reached from models/smpl_official.py:29).
 
-#include <type_traits>
-
-#include "hps_common.h"
+#include "mesh_epilogue.h"
 
 namespace hps {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
-constexpr int SV = 64;                         // vertices per panel
+constexpr int SV = MESH_PANEL;                 // vertices per panel
 constexpr int SN = 3 * SV;                     // blend-matrix columns per panel
 constexpr int SBK = 16;                        // K rows per chunk = one bf16 MFMA
 constexpr int S_BB = 3 * 2 * SN * 16;          // bytes of a chunk's blend-matrix panel: [3 pieces][2 k halves][192 columns][8 bf16] = 18 432
@@ -100,11 +97,8 @@ __global__ __launch_bounds__(SplitCfg<MG>::THREADS, SplitCfg<MG>::WAVES_PER_SIMD
     typedef __attribute__((address_space(3))) void* lptr_t;
     extern __shared__ __attribute__((aligned(16))) float smem[];   // union: two operand stages | A of 16 MG of the tile's meshes
 
-    // block -> (mesh tile, panel): mesh_fused_kernel's mapping (blocks of one XCD own the same mesh tiles and walk the panels in order)
-    const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-    const int tile_m = tiles_m_per_xcd ? (local % tiles_m_per_xcd) * 8 + xcd : (int)blockIdx.x % tiles_m;
-    const int panel = tiles_m_per_xcd ? local / tiles_m_per_xcd : (int)blockIdx.x / tiles_m;
-    if (tile_m >= tiles_m) return;
+    int tile_m, panel;
+    if (!mesh_block(tiles_m, tiles_m_per_xcd, tile_m, panel)) return;
     const int m0 = tile_m * SM;
     // De-phasing: the workgroups that share a CU start together and, all tiles costing the same, stay in step -- K loops (matrix pipe, L2
     // stream) together, then epilogues (VALU, LDS, stores) together.  The second resident workgroup of every CU (blocks 256 .. 511 of
@@ -112,26 +106,8 @@ __global__ __launch_bounds__(SplitCfg<MG>::THREADS, SplitCfg<MG>::WAVES_PER_SIMD
     if (stagger > 0 && blockIdx.x >= 256 && blockIdx.x < 512)
         for (int i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(56);
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kl = lane >> 5, il = lane & 31;
-    const int wm = wave >> 1, wn = wave & 1;
-
-    const int v = panel * SV + wn * 32 + il;
-    const bool live_v = v < V;
-    const int vc = live_v ? v : V - 1;
-    int idx[K];
-    float w[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        idx[k] = w_idx[(size_t)vc * K + k] * 12;
-        w[k] = w_val[(size_t)vc * K + k];
-    }
-    const int32_t* gr = group_rows + 3 * __builtin_amdgcn_readfirstlane((m0 + wm * 32) >> 5);      // wave-uniform: scalar loads
-    const int split = gr[2];
-    const f3 vt = reinterpret_cast<const f3*>(v_shaped)[(size_t)gr[0] * V + vc];
-    const f3 vtb = reinterpret_cast<const f3*>(v_shaped)[(size_t)gr[1] * V + vc];
-    const int split_lane = split - 4 * kl;                    // local mesh 4 kl + dr < split  <=>  dr < split_lane
-    const int pick = live_v ? pick_slot[vc] : -1;
+    const MeshLane<K> L = mesh_lane<K, MG, true, true>(panel, m0, V, w_idx, w_val, v_shaped, group_rows, pick_slot);
+    const int lane = L.lane, wave = L.wave, kl = L.kl, il = L.il, wm = L.wm, wn = L.wn;
 
     const unsigned lds0 = (unsigned)(size_t)(lptr_t)(smem);
     const unsigned lane16 = (unsigned)lane * 16u;
@@ -237,74 +213,12 @@ __global__ __launch_bounds__(SplitCfg<MG>::THREADS, SplitCfg<MG>::WAVES_PER_SIMD
         for (int c = 0; c + 1 < nchunks; ++c) do_chunk(std::false_type(), std::true_type(), c);
         do_chunk(std::false_type(), std::false_type(), nchunks - 1);
     }
-    if (ABL == 1 || ABL == 3 || (ABL >= 6 && ABL <= 9)) {                            // K loop only: one never-taken store keeps the accumulators alive
-        float t = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) t += acc[0][r] + acc[1][r] + acc[2][r];
-        if (t == 12345.678f) verts[0].x = t;
+    if (ABL == 1 || ABL == 3 || (ABL >= 6 && ABL <= 9)) {                            // K loop only
+        mesh_keep_acc(acc, verts);
         return;
     }
-
-    // Skinning: mesh_fused_kernel's epilogue (VS, PICK, no translation), two passes: pass p stages A of meshes [32 h + 16 p, + 16) of the
-    // tile for every mesh group h -- the meshes of accumulator registers r = 8 p .. 8 p + 7 -- as LDS slots 16 h .. 16 h + 15.
-    const int a_stride = JC * 12;
-    const int half_bytes = 16 * a_stride * 4;
-    const int slot0 = wm * 16 + 4 * kl;
-    int aoff[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) aoff[k] = slot0 * a_stride + idx[k];
-    char* const vbase = reinterpret_cast<char*>(verts) + (size_t)(m0 + wm * 32) * V * 12;      // wave-uniform
-    const unsigned voff = ((unsigned)(4 * kl) * (unsigned)V + (unsigned)v) * 12u;              // per lane
-    char* const pbase = reinterpret_cast<char*>(picked) + (size_t)(m0 + wm * 32) * n_picked * 12;
-    const unsigned poff = ((unsigned)(4 * kl) * (unsigned)n_picked + (unsigned)max(pick, 0)) * 12u;
-    auto epilogue = [&](auto many_c) __attribute__((always_inline)) {
-        constexpr bool MANY = decltype(many_c)::value;
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            __syncthreads();                               // operand stages / the previous pass's transforms are dead
-#pragma unroll
-            for (int h = 0; h < MG; ++h) {
-                const int mh = m0 + 32 * h + 16 * pass;
-                const int valid = max(0, min(16, M - mh)) * a_stride * 4;
-                const float* a_src = a + (size_t)mh * a_stride;
-                for (int piece = wave; piece * 1024 < half_bytes; piece += SW) {
-                    const int off = piece * 1024 + lane * 16;
-                    if (off < valid && ABL != 10) lds_dma16((unsigned)off, a_src, lds0 + (unsigned)(h * half_bytes + piece * 1024));
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                const int r = 8 * pass + q;
-                const int dr = (r & 3) + 8 * (r >> 2);
-                const int ds = (q & 3) + 8 * (q >> 2);
-                const int m = m0 + wm * 32 + 4 * kl + dr;
-                f3 base;
-                if (!MANY) {
-                    const bool first = dr < split_lane;
-                    base.x = first ? vt.x : vtb.x; base.y = first ? vt.y : vtb.y; base.z = first ? vt.z : vtb.z;
-                } else {
-                    base = reinterpret_cast<const f3*>(v_shaped)[(size_t)mesh_row[min(m, M - 1)] * V + vc];
-                }
-                f3 pv;
-                pv.x = base.x + acc[0][r]; pv.y = base.y + acc[1][r]; pv.z = base.z + acc[2][r];
-                int ao[K];
-#pragma unroll
-                for (int k = 0; k < K; ++k) ao[k] = aoff[k] + ds * a_stride;
-                const f3 o = ABL == 12 ? pv : skin_vertex<K>(smem, ao, w, pv, 0.f, 0.f, 0.f);
-                asm volatile("" :: "v"(o.x), "v"(o.y), "v"(o.z));      // (see mesh_fused_kernel: keeps the skinning out of the guarded block)
-                if (ABL == 11) {                           // dev: no stores (a never-true guard keeps the skinning alive)
-                    if (o.x == 12345.678f) *reinterpret_cast<f3*>(vbase + (size_t)dr * V * 12 + voff) = o;
-                    continue;
-                }
-                if (live_v && m < M) *reinterpret_cast<f3*>(vbase + (size_t)dr * V * 12 + voff) = o;
-                if (pick >= 0 && m < M) *reinterpret_cast<f3*>(pbase + (size_t)dr * n_picked * 12 + poff) = o;
-            }
-        }
-    };
-    if (split < 0) epilogue(std::true_type());
-    else epilogue(std::false_type());
+    constexpr int EPI = ABL == 10 ? EPI_NO_A_DMA : ABL == 11 ? EPI_NO_STORES : ABL == 12 ? EPI_NO_SKIN : EPI_ALL;
+    mesh_epilogue<K, JC, MG, false, true, true, EPI>(smem, L, acc, m0, M, V, JC, a, nullptr, v_shaped, mesh_row, verts, picked, n_picked);
 }
 
 #ifdef HPS_DEV_BUILD
@@ -320,17 +234,16 @@ static int launch_split(const void* xsplit, const void* bsplit, const float* v_s
                         const int32_t* pick_slot, float* picked, int n_picked, hipStream_t s) {
     typedef SplitCfg<MG> C;
     const int tiles_m = ceil_div(M, C::SM), n_panels = ceil_div(V, SV);
-    const int tiles_m_per_xcd = tiles_m >= 8 ? ceil_div(tiles_m, 8) : 0;
-    const dim3 grid(tiles_m_per_xcd ? tiles_m_per_xcd * 8 * n_panels : tiles_m * n_panels);
+    const MeshGrid g = mesh_grid(tiles_m, n_panels);
     // (only launches of several resident rounds: a few hundred workgroups have no second round to keep apart, and the delay would be latency)
-    int stagger = grid.x >= 2048 ? SPLIT_STAGGER : 0;
+    int stagger = g.blocks >= 2048 ? SPLIT_STAGGER : 0;
 #ifdef HPS_DEV_BUILD
     if (g_split_stagger >= 0) stagger = g_split_stagger;
 #endif
     if (int rc = grant_lds<&mesh_split_kernel<4, 24, MG, ABL>>(160 * 1024, "hps_smpl_mesh_fused_shared_shape_bf16x3")) return rc;
-    hipLaunchKernelGGL((mesh_split_kernel<4, 24, MG, ABL>), grid, dim3(C::THREADS), (size_t)C::LDS, s, reinterpret_cast<const char*>(xsplit),
+    hipLaunchKernelGGL((mesh_split_kernel<4, 24, MG, ABL>), dim3(g.blocks), dim3(C::THREADS), (size_t)C::LDS, s, reinterpret_cast<const char*>(xsplit),
                        reinterpret_cast<const char*>(bsplit), v_shaped, a, w_idx, w_val, reinterpret_cast<f3*>(verts), M, V,
-                       ceil_div(rows, SBK), tiles_m, tiles_m_per_xcd, pick_slot, reinterpret_cast<f3*>(picked), n_picked, mesh_row, group_rows, stagger);
+                       ceil_div(rows, SBK), tiles_m, g.tiles_m_per_xcd, pick_slot, reinterpret_cast<f3*>(picked), n_picked, mesh_row, group_rows, stagger);
     return check_launch("hps_smpl_mesh_fused_shared_shape_bf16x3");
 }
 

@@ -472,6 +472,21 @@ def test_hip_smpl_matches_the_reference_class_on_smplx(dev, smplx_golden):
             assert maxerr(o.joints, t(name + "_joints")) <= TOL, (key, name)
 
 
+def _same_bits_for_any_split(smpl_gpu, loc, mesh_row, group_rows, args):
+    """The shared-shape mesh kernel with group_rows as built, with split = -1 in every group, and with split = -1 in every other group
+    (hps.h: mesh_row is authoritative, so any group may say -1; the last mixes both kinds of group in one workgroup): the per-mesh
+    template fetch and the two-row select give the same bits.  Returns the first output."""
+    forced = []
+    for step in (1, 2):
+        gr = group_rows.view(-1, 3).clone()
+        gr[::step, 2] = -1
+        forced.append(gr.view(-1))
+    outs = [smpl_gpu(_shared_shapes=(loc, mesh_row, g), **args) for g in [group_rows] + forced]
+    for o in outs[1:]:
+        assert torch.equal(o.vertices, outs[0].vertices) and torch.equal(o.joints, outs[0].joints)
+    return outs[0]
+
+
 @pytest.mark.parametrize("B,N", [(1, 1), (1, 50), (3, 7), (2, 100), (17, 33), (64, 100)])
 def test_shared_shape_form_of_the_mesh_kernel(B, N, dev, smpl_gpu, smpl_assets):
     """hps_smpl_mesh_fused_shared_shape (K = 207: the shape blend once per image, smplx's v_posed = v_shaped + pose_offsets) on infer()'s
@@ -497,7 +512,7 @@ def test_shared_shape_form_of_the_mesh_kernel(B, N, dev, smpl_gpu, smpl_assets):
         else:
             assert int((r[1:] != r[:-1]).sum()) > 1                 # more than one change of row inside the group
     args = dict(betas=betas.to(dev), body_pose=R[:, 1:].to(dev), global_orient=R[:, :1].to(dev), pose2rot=False)
-    shared = smpl_gpu(_shared_shapes=(loc.to(dev), mesh_row, group_rows), **args)
+    shared = _same_bits_for_any_split(smpl_gpu, loc.to(dev), mesh_row, group_rows, args)
     plain = smpl_gpu(**args)                                     # K = 217: template + shape + pose in one chain
     assert maxerr(shared.vertices, plain.vertices) <= 4e-6 and maxerr(shared.joints, plain.joints) <= 4e-6
     if M <= 700:
@@ -575,7 +590,7 @@ def test_split_bf16_form_of_the_mesh_kernel(B, N, dev, smpl_gpu, smpl_assets):
     moved32 = smpl_gpu(transl=tr, **args)
     smpl_gpu.mesh_arith = "bf16x3"
     try:
-        sp = smpl_gpu(_shared_shapes=(loc.to(dev), mesh_row, group_rows), **args)
+        sp = _same_bits_for_any_split(smpl_gpu, loc.to(dev), mesh_row, group_rows, args)
         sp2 = smpl_gpu(_shared_shapes=(loc.to(dev), mesh_row, group_rows), **args)
         plain = smpl_gpu(**args)                                  # no shared shapes: the same kernel over all 217 rows
         moved = smpl_gpu(transl=tr, **args)                       # a translation: the fp32 kernel
