@@ -12,6 +12,7 @@ behaviour) over libhps.so, a C-ABI library of hand-written gfx950 HIP kernels (i
     predict/predict_poseMF_shapeGaussian_net ->   predict_poseMF_shapeGaussian_net.*
     models/canny_edge_detector.py            ->   canny_edge_detector.CannyEdgeDetector
     utils/label_conversions.py (heat-maps)   ->   label_conversions.*
+    losses/matrix_fisher_loss.py             ->   matrix_fisher_loss.{LogMFNormConstant, matrix_fisher_nll, PoseMFShapeGaussianLoss}
 """
 from .configs import get_cfg_defaults, SMPL_PARENTS  # noqa: F401
 

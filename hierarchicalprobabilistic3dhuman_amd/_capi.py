@@ -85,6 +85,10 @@ _PROTOTYPES = {
     "hps_nchw_to_padded_nhwc_generic": [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "hps_maxpool3x3s2_pad": [_P, _P, _I, _I, _I, _I, _I, _P],
     "hps_global_avgpool_pad": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "hps_mf_log_norm_const": [_P, _I, _P, _P, _P, _P],
+    "hps_mf_nll": [_P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _P, _P],
+    "hps_mf_loss_forward": [_P, _P, _P, _P],
+    "hps_mf_loss_backward": [_P, _P, _P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t}
@@ -104,6 +108,18 @@ class EncOp(_c.Structure):
                     ("w_down", _P), ("scale_down", _P), ("shift_down", _P), ("y_down", _P)]
 
 
+class MfLossArgs(_c.Structure):
+    """include/hps.h: hps_mf_loss_args (struct_bytes = ctypes.sizeof(MfLossArgs); the library rejects any other value)."""
+    _fields_ = [("struct_bytes", _I), ("reduction", _I)] + [
+        (n, _c.c_int64) for n in ("n_pose", "shape_B", "n_shape", "j2d_B", "Ns", "K", "n_glob", "n_verts", "n_joints3d")] + [
+        ("img_wh", _c.c_double), ("overreg", _c.c_double), ("weights", _c.c_double * 6)] + [
+        (n, _P) for n in ("pose_F", "pose_U", "pose_S", "pose_V", "shape_loc", "shape_scale", "joints2d", "glob_rotmats", "verts",
+                          "joints3d", "t_pose_rotmats", "t_shape", "t_joints2d", "t_joints2d_vis", "t_glob_rotmats", "t_verts",
+                          "t_joints3d", "g_pose_F", "g_pose_S", "g_shape_loc", "g_shape_scale", "g_joints2d", "g_glob_rotmats",
+                          "g_verts", "g_joints3d")]
+
+
+MF_REDUCTION_MEAN, MF_REDUCTION_SUM = 0, 1
 ENC_RELAYOUT, ENC_CONV, ENC_MAXPOOL, ENC_AVGPOOL, ENC_CONV_WINOGRAD, ENC_STEM_SPLIT, ENC_STEM_WINOGRAD, ENC_RELAYOUT_GENERIC = 0, 1, 2, 3, 4, 5, 6, 7
 ENC_STEM_WINOGRAD_POOLED, ENC_STEM_WINOGRAD_POOLED_NCHW, ENC_CONV_DOWN = 8, 9, 10
 SVD_HOST, SVD_DEVICE, SVD_DEVICE_FMA = 0, 1, 2
@@ -267,6 +283,7 @@ def call(name, *args):
 
 
 WS_CONV_SPLITK, WS_SMPL_MP, WS_SMPL_XT, WS_SMPL_A, WS_SMPL_VPOSED, WS_HEAD_F, WS_HEAD_USV = range(7)
+WS_MF_LOSS = 8
 
 
 def query_workspace(what, d0=0, d1=0, d2=0):

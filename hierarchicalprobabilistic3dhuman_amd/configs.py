@@ -20,12 +20,21 @@ SMPLX_EXTRA_VERTEX_IDS = [332, 6260, 2800, 4071, 583,
                           6191, 5782, 5905, 6016, 6133]
 
 
+def _loss_stage(overreg, pose, shape, joints2d, glob_rotmats, verts3d, joints3d):
+    return SimpleNamespace(REDUCTION="mean", MF_OVERREG=overreg,
+                           WEIGHTS=SimpleNamespace(POSE=pose, SHAPE=shape, JOINTS2D=joints2d, GLOB_ROTMATS=glob_rotmats,
+                                                   VERTS3D=verts3d, JOINTS3D=joints3d))
+
+
 def get_cfg_defaults():
-    """Values of configs/poseMF_shapeGaussian_net_config.py:8-24 that the inference path reads."""
+    """Values of configs/poseMF_shapeGaussian_net_config.py:8-24 that the inference path reads, and of :83-110 that
+    matrix_fisher_loss.PoseMFShapeGaussianLoss reads (LOSS.STAGE1 / STAGE2: REDUCTION, MF_OVERREG, WEIGHTS)."""
     return SimpleNamespace(
         MODEL=SimpleNamespace(NUM_IN_CHANNELS=18, NUM_RESNET_LAYERS=18, EMBED_DIM=256,
                               DELTA_I=True, DELTA_I_WEIGHT=1.0, NUM_SMPL_BETAS=10),
         DATA=SimpleNamespace(PROXY_REP_SIZE=256, HEATMAP_GAUSSIAN_STD=4.0, EDGE_NMS=True,
                              EDGE_THRESHOLD=0.0, EDGE_GAUSSIAN_STD=1.0, EDGE_GAUSSIAN_SIZE=5,
                              BBOX_THRESHOLD=0.95, BBOX_SCALE_FACTOR=1.2),
+        LOSS=SimpleNamespace(STAGE1=_loss_stage(1.005, 80.0, 50.0, 5000.0, 5000.0, 0.0, 0.0),
+                             STAGE2=_loss_stage(1.005, 10.0, 80.0, 30000.0, 5000.0, 5000.0, 5000.0)),
     )

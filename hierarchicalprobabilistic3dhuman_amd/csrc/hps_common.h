@@ -16,6 +16,9 @@ namespace hps {
 // thread-local last-error text returned by hps_last_error()
 void set_error(const char* fmt, ...);
 
+// bytes of the hps_mf_loss_forward / _backward workspace for n_pose matrix-Fisher rows (csrc/mf_loss.hip; HPS_WS_MF_LOSS)
+int64_t mf_loss_ws_bytes(int64_t rows);
+
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {

@@ -96,9 +96,10 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_SMPL_VPOSED (d0 = M, d1 = V)                         v_posed of the unfused hps_smpl_blend with 128-byte aligned rows
  *   HPS_WS_HEAD_F      (d0 = B, d1 = largest level size)        f_level_dev / f_host_pinned of hps_head_pose_levels
  *   HPS_WS_HEAD_USV    (d0 = B, d1 = largest level size)        usv_level_dev / usv_host_pinned of hps_head_pose_levels
+ *   HPS_WS_MF_LOSS     (d0 = n_pose)                            workspace of hps_mf_loss_forward / hps_mf_loss_backward
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
-       HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6 };
+       HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -600,6 +601,67 @@ int hps_pointset_errors(const float* pred, const float* target, int S, int group
  * accumulator without a launch of its own). */
 int hps_sums_f64(const float* const* xs, const int64_t* ns, const int32_t* take_abs, int count, double first,
                  double* partial_ws, double* out, double* accumulate, hps_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Matrix-Fisher likelihood and the pose / shape loss  (losses/matrix_fisher_loss.py)
+ * ---------------------------------------------------------------------------------------- */
+
+/* log c(S) of the matrix-Fisher distribution, LogMFNormConstant (:134-192).  S (n,3): proper singular values.
+ *   log_c (n,) = log c_bar(S) + s0 + s1 + s2 with c_bar by the reference's own rule (:48-96, :157-170): 512 trapezoid nodes on [-1, 1]
+ *   (end weights 1/2) over the integrand I0bar((s1 - s2)(1 - u)/2) I0bar((s1 + s2)(1 + u)/2) exp((s2 + s0)(u - 1)), I0bar the
+ *   exp-scaled Numerical Recipes polynomials of :9-11, :30-45 -- not a better quadrature, which would differ from it by up to units
+ *   in log c at concentrations of 10^4.
+ *   grad_log_c / grad_S, both or neither: grad_S (n,3) = d log c / dS * grad_log_c, from the three cyclic-shift integrals of :99-131,
+ *   :173-192, evaluated in the same pass over the nodes.  log_c may be NULL when only the gradient is wanted.
+ * One wave64 per row, fp64 arithmetic inside, every output rounded once. */
+int hps_mf_log_norm_const(const float* S, int n, float* log_c, const float* grad_log_c, float* grad_S, hps_stream_t stream);
+
+/* matrix_fisher_nll (:195-228) over n rows: nll (n,) = -<F, R> + overreg * log c(s0, s1, s2 * det(U V^T)) -- the determinant's VALUE
+ * multiplies s2, as at :222-224 (whose torch.det(...).cpu() is a host round trip; here it is formed in the kernel).  F, U, V, R (n,3,3),
+ * S (n,3).  Backward (grad_nll (n,) not NULL): grad_F = -R * grad_nll and grad_S = overreg * grad_nll * d log c / d s_proper with the
+ * s2 entry times det (either may be NULL, and nll too); U and V get no gradient (the reference uses them under no_grad). */
+int hps_mf_nll(const float* F, const float* U, const float* S, const float* V, const float* R, int n, double overreg, float* nll,
+               const float* grad_nll, float* grad_F, float* grad_S, hps_stream_t stream);
+
+/* PoseMFShapeGaussianLoss (:231-301), all six terms from one argument block:
+ *   pose NLL       matrix_fisher_nll over n_pose rows (:254-259)
+ *   shape NLL      -sum over betas of Normal(loc, scale).log_prob(target), (shape_B, n_shape / shape_B) (:266)
+ *   joints2D MSE   the entries of VISIBLE joints only: predictions (j2d_B, Ns, K, 2) against targets (j2d_B, K, 2) normalised by
+ *                  2 t / img_wh - 1 and broadcast over the Ns samples; visibility (j2d_B, K) bytes 0 / 1 -- what :273-283 selects with
+ *                  boolean masks (a host round trip each on a GPU), counted on the device here
+ *   glob-rotmat, vertex and joints3D MSE over n_glob / n_verts / n_joints3d elements (:286-292)
+ * each reduced by `reduction` -- under HPS_MF_REDUCTION_MEAN a mean over no element (no visible joint) is NaN, and so is the total
+ * then, whatever the term's weight, as in the reference -- then weighted and added in the reference's order (:294-299).  All
+ * arrays contiguous fp32 (the visibility bytes excepted); g_* are the backward's outputs, shaped like their predictions, NULL = not
+ * wanted (the forward ignores them).  struct_bytes = sizeof(hps_mf_loss_args) as the caller compiled it: a mirror that drifts is
+ * rejected instead of read. */
+#define HPS_MF_REDUCTION_MEAN 0
+#define HPS_MF_REDUCTION_SUM 1
+typedef struct hps_mf_loss_args {
+    int struct_bytes;
+    int reduction;                                             /* HPS_MF_REDUCTION_* (loss_config.REDUCTION) */
+    int64_t n_pose;                                            /* matrix-Fisher rows (B * 23) */
+    int64_t shape_B, n_shape;                                  /* rows and elements of the shape distribution */
+    int64_t j2d_B, Ns, K;                                      /* joints2D geometry */
+    int64_t n_glob, n_verts, n_joints3d;                       /* elements of the three plain MSE terms */
+    double img_wh, overreg;                                    /* img_wh, loss_config.MF_OVERREG */
+    double weights[6];                                         /* WEIGHTS.POSE, SHAPE, JOINTS2D, GLOB_ROTMATS, VERTS3D, JOINTS3D */
+    const float *pose_F, *pose_U, *pose_S, *pose_V;            /* predictions */
+    const float *shape_loc, *shape_scale, *joints2d, *glob_rotmats, *verts, *joints3d;
+    const float *t_pose_rotmats, *t_shape, *t_joints2d;        /* targets */
+    const uint8_t* t_joints2d_vis;
+    const float *t_glob_rotmats, *t_verts, *t_joints3d;
+    float *g_pose_F, *g_pose_S, *g_shape_loc, *g_shape_scale;  /* gradients of the predictions (U and V get none) */
+    float *g_joints2d, *g_glob_rotmats, *g_verts, *g_joints3d;
+} hps_mf_loss_args;
+
+/* Forward, 2 launches: per-workgroup fp64 partial sums -- one wave per pose row, whose d log c / ds and det go to the workspace --
+ * then one workgroup that adds them in a fixed order (bitwise reproducible) and writes *total (one float, device).  workspace:
+ * hps_query_workspace(HPS_WS_MF_LOSS, n_pose) bytes, 8-byte aligned, kept unchanged until the backward call.
+ * Backward, 1 launch: every g_* that is not NULL = d total / d prediction * grad_total[0] (a device scalar: no host round trip).
+ * Replaces :254-301 with the autograd graph behind it (118 + 347 aten operators per normaliser on (rows x 512) temporaries). */
+int hps_mf_loss_forward(const hps_mf_loss_args* args, void* workspace, float* total, hps_stream_t stream);
+int hps_mf_loss_backward(const hps_mf_loss_args* args, const void* workspace, const float* grad_total, hps_stream_t stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
