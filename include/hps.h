@@ -267,7 +267,17 @@ int hps_vertex_uncertainty(const float* verts, float* unc, int B, int N, int V, 
  *                   reports accepted[c] < N and its outputs are to be discarded (the caller retries with
  *                   the next draw, as the reference does at :68-69).
  *   eps == NULL   : counter-based Philox4x32-10 in the kernel, keyed by (seed, call_offset + c,
- *                   round, proposal) so results do not depend on how images are sharded over GPUs;
+ *                   round, proposal) so results do not depend on how images are sharded over GPUs.
+ *                   Seeded results are part of the contract; the layout, with g = call_offset + c:
+ *                     key     = (seed bits 0..31, seed bits 32..63)
+ *                     counter = (proposal, round, g bits 0..31, g bits 32..62 | block << 31)
+ *                     block 0 : words (x, y) -> the normals (e0, e1), words (z, w) -> (e2, e3) by Box-Muller,
+ *                               radius sqrt(-2 ln u), u = ((a >> 8) + 1) / 2^24 in (0, 1] from the pair's first word a,
+ *                               angle 2 pi v, v = (b >> 8) / 2^24 in [0, 1) from its second word b, (cos, sin)
+ *                     block 1 : word x -> the acceptance uniform (x >> 8) / 2^24 in [0, 1); words y, z, w unused
+ *                   (bit 63 of g does not reach the counter).  Pinned word for word by tests/test_gpu_philox.py against the
+ *                   host replica tests/philox_replica.py; a change of this layout changes every user's seeded samples and
+ *                   is an ABI change.
  *                   rounds are redrawn in-kernel until N proposals are accepted; a call that exhausts
  *                   max_rounds (non-finite concentrations) gets NaN outputs and accepted[c] < N.
  *                   seed_dev (optional, device, two uint64: seed, call_offset) overrides the by-value pair: a launch captured in

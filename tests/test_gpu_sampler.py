@@ -1,6 +1,7 @@
 """GPU parity: matrix-Fisher sampling kernel against the golden vectors the imported reference produced
 (same torch seed, sample_on_cpu route), against the oracle with forced discarded rounds, and the Philox
-route through seed-independent properties (first moment, orthonormality, sharding invariance).
+route through seed-independent properties (first moment, orthonormality, sharding invariance).  The Philox route is pinned
+sample by sample in tests/test_gpu_philox.py, against the host replica of the kernel's noise (tests/philox_replica.py).
 
 Stated tolerance: rotation matrices <= 1e-5 given identical (U,S,V, eps, w); an accept decision may flip only
 on an fp32 rounding tie (<= 1e-6 of proposals) -- a flip would change every later sample of that call."""
@@ -11,6 +12,7 @@ from oracle import ref_cpu as O
 from hierarchicalprobabilistic3dhuman_amd import sampling_utils as su
 from hierarchicalprobabilistic3dhuman_amd import rigid_transform_utils as rtu
 from conftest import maxerr
+import sampler_stats
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -107,6 +109,12 @@ def test_philox_route_properties(dev, golden):
     D = torch.matmul(U[0].transpose(-1, -2), torch.matmul(R[0].mean(0), V[0])).cpu()
     rows = [0, 1, 2, 3, 4, 6]
     assert maxerr(D[rows], torch.diag_embed(golden["sweep_dlogc_dS"])[rows]) <= 0.025
+    # ... and every row, row 5 included, against the float64 first moment (tests/sampler_stats.py: Gauss-Legendre on the
+    # one-dimensional form of c(S), not the reference's trapezoid rule) at the normal-tail bound z(alpha/2) std / sqrt(N)
+    for row in range(7):
+        stats = sampler_stats.moment_statistics(R[0, :, row].cpu().numpy(), U[0, row].cpu().numpy(), S[0, row].cpu().numpy(),
+                                                V[0, row].cpu().numpy())
+        assert not sampler_stats.failures(stats), (row, stats)
     # same seed -> same samples; different seed -> different samples
     assert torch.equal(R, su.pose_matrix_fisher_sampling_torch(U, S, V, N, seed=2024))
     assert not torch.equal(R, su.pose_matrix_fisher_sampling_torch(U, S, V, N, seed=2025))

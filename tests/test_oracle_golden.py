@@ -6,6 +6,7 @@ import torch
 from oracle import ref_cpu as O
 from hierarchicalprobabilistic3dhuman_amd import configs
 from conftest import maxerr
+import sampler_stats
 
 
 def test_encoder_matches_reference(golden, net_cpu, golden_input):
@@ -86,6 +87,10 @@ def test_sampler_first_moment_matches_normalising_constant_gradient(golden):
     # (0.95/0.91 where the true value is ~0.999), so it is excluded; Monte-Carlo sigma of the mean <= 0.004
     rows = [0, 1, 2, 3, 4, 6]
     assert maxerr(D[rows], want[rows]) <= 0.025
+    # every row, row 5 included, against the float64 first moment (tests/sampler_stats.py) at z(alpha/2) std / sqrt(N)
+    for row in range(7):
+        stats = sampler_stats.moment_statistics(R[:, row].numpy(), U[0, row].numpy(), S[0, row].numpy(), V[0, row].numpy())
+        assert not sampler_stats.failures(stats), (row, stats)
 
 
 def test_vertex_uncertainty_sampling_matches_reference(golden, smpl_assets):
