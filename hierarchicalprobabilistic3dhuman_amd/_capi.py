@@ -39,6 +39,9 @@ _PROTOTYPES = {
     "hps_smpl_mesh_fused_shared_shape_bf16x3": [_P] * 8 + [_I, _I, _P] + [_I] * 4 + [_P, _P, _I, _P],
     "hps_smpl_v_shaped": [_P, _I, _P, _I, _P, _P, _I, _I, _P],
     "hps_smpl_mesh_fused_np": [_I],
+    "hps_smpl_lbs_backward": [_P, _I, _P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    "hps_smpl_blend_backward": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
+    "hps_smpl_pose_prep_backward": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _I, _P],
     "hps_smpl_joints": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P],
     "hps_vertex_uncertainty": [_P, _P, _I, _I, _I, _P],
     "hps_joints_and_uncertainty": [_P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P],
@@ -284,6 +287,7 @@ def call(name, *args):
 
 WS_CONV_SPLITK, WS_SMPL_MP, WS_SMPL_XT, WS_SMPL_A, WS_SMPL_VPOSED, WS_HEAD_F, WS_HEAD_USV = range(7)
 WS_MF_LOSS = 8
+WS_SMPL_LBS_BWD, WS_SMPL_BLEND_BWD = 9, 10
 
 
 def query_workspace(what, d0=0, d1=0, d2=0):

@@ -18,6 +18,9 @@ void set_error(const char* fmt, ...);
 
 // bytes of the hps_mf_loss_forward / _backward workspace for n_pose matrix-Fisher rows (csrc/mf_loss.hip; HPS_WS_MF_LOSS)
 int64_t mf_loss_ws_bytes(int64_t rows);
+// bytes of the hps_smpl_lbs_backward / hps_smpl_blend_backward workspaces (csrc/smpl_backward.hip; HPS_WS_SMPL_LBS_BWD / _BLEND_BWD)
+int64_t lbs_backward_ws_bytes(int64_t M, int64_t V, int64_t J);
+int64_t blend_backward_ws_bytes(int64_t M, int64_t kp, int64_t np);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -11,6 +11,10 @@ Kernel sequence per call (all on the current HIP stream, no host synchronisation
                       epilogue: v_posed never exists in HBM.  ``fused_mesh = False`` selects the unfused pair
                       hps_smpl_blend + hps_smpl_lbs (bit-identical vertices; the definition SURVEY 8(d)'s LBS bytes use)
   hps_smpl_joints     24 kinematic joints + 21 vertex picks + 45 regressed joints
+
+Under autograd (grad mode on and betas / body_pose / global_orient / transl requiring grad) the same kernels run inside a
+torch.autograd.Function whose backward is three more (hps_smpl_lbs_backward, hps_smpl_blend_backward,
+hps_smpl_pose_prep_backward): see ``SMPL.forward``.
 """
 from collections import namedtuple
 
@@ -31,6 +35,26 @@ _LBS_K_CHOICES = (4, 8, 12, 24)
 
 def _round_up(x, m):
     return (x + m - 1) // m * m
+
+
+class _SMPLFunction(torch.autograd.Function):
+    """SMPL.forward for autograd: forward = the module's own kernel sequence (K = 217 forms), backward = the three device backward
+    stages on what hps_smpl_pose_prep + hps_smpl_blend recompute from the saved INPUTS (nothing else is kept: 83 KB of transient
+    v_posed per mesh in the backward instead of 83 KB per mesh held from forward to backward)."""
+
+    @staticmethod
+    def forward(ctx, smpl, pose2rot, g, b, be, tr):
+        out = smpl.forward(betas=be, body_pose=b, global_orient=g, transl=tr, pose2rot=pose2rot, _k217=True)
+        ctx.smpl, ctx.pose2rot = smpl, pose2rot
+        ctx.save_for_backward(g, b, be)
+        ctx.set_materialize_grads(False)
+        return out.vertices, out.joints
+
+    @staticmethod
+    def backward(ctx, g_verts, g_joints):
+        g, b, be = ctx.saved_tensors
+        grads = ctx.smpl._backward(g, b, be, ctx.pose2rot, g_verts, g_joints, ctx.needs_input_grad[2:6])
+        return (None, None) + grads
 
 
 class SMPL(DeviceStateModule):
@@ -159,6 +183,21 @@ class SMPL(DeviceStateModule):
         self.register_buffer("_csr_ptr", torch.tensor(ptr_, dtype=torch.int32), persistent=False)
         self.register_buffer("_csr_col", torch.tensor(col_, dtype=torch.int32), persistent=False)
         self.register_buffer("_csr_val", torch.tensor(val_, dtype=torch.float32), persistent=False)
+        # backward: the same matrix transposed (CSR over the vertices, a vertex's entries in row order) -- over all vertices for the
+        # dense route, over the picked vertices' slots for the joints-only route, which runs the backward kernels on the picked
+        # vertices alone (their columns of the blend matrix, their skinning weights: _picked_tables)
+        row_of = np.repeat(np.arange(dense.shape[0]), np.diff(ptr_))
+        def transposed(cols, n):
+            order = np.argsort(np.asarray(cols, np.int64), kind="stable")
+            tptr = np.concatenate([[0], np.cumsum(np.bincount(np.asarray(cols, np.int64), minlength=n))])
+            return (torch.tensor(tptr, dtype=torch.int32), torch.tensor(row_of[order], dtype=torch.int32),
+                    torch.tensor(np.asarray(val_, np.float64)[order], dtype=torch.float32))
+        for name, t in zip(("_csrt_ptr", "_csrt_row", "_csrt_val"), transposed(col_, V)):
+            self.register_buffer(name, t, persistent=False)
+        for name, t in zip(("_pk_csrt_ptr", "_pk_csrt_row", "_pk_csrt_val"), transposed([slot_of[v] for v in col_], len(uniq))):
+            self.register_buffer(name, t, persistent=False)
+        self.register_buffer("_pk_verts", torch.tensor(uniq, dtype=torch.long), persistent=False)
+        self._last_backward = None
 
     def shared_shape_tables(self, mesh_rows):
         """The (mesh_row, group_rows) tables of hps_smpl_mesh_fused_shared_shape for meshes whose shapes are rows of a small table:
@@ -202,12 +241,84 @@ class SMPL(DeviceStateModule):
         return self._derived("one_shape", mp, lambda: (torch.zeros(mp, dtype=torch.int32, device=dev),
                                                         torch.tensor([0, 0, 32], dtype=torch.int32).repeat(mp // 32).to(dev)))
 
+    def _picked_tables(self):
+        """Constants of the joints-only backward (once per device state): the picked vertices' columns of the blend matrix padded to
+        the kernels' multiple, their template entries and skinning weights."""
+        def build():
+            n = self._n_picked
+            cols = (3 * self._pk_verts.unsqueeze(1) + torch.arange(3, device=self._pk_verts.device)).reshape(-1)
+            np_ = _round_up(3 * n, 128)
+            bmat = torch.zeros(self._kp, np_, dtype=torch.float32, device=cols.device)
+            bmat[:, :3 * n] = self._bmat.index_select(1, cols)
+            return dict(V=n, N=3 * n, np=np_, bmat=bmat, v_template=self._v_template_flat.index_select(0, cols).contiguous(),
+                        w_idx=self._w_idx.index_select(0, self._pk_verts).contiguous(),
+                        w_val=self._w_val.index_select(0, self._pk_verts).contiguous(),
+                        csrt=(self._pk_csrt_ptr, self._pk_csrt_row, self._pk_csrt_val))
+        return self._derived("picked_bwd", 0, build)
+
+    def _backward(self, g, b, be, pose2rot, g_verts, g_joints, needs):
+        """Gradients of (global_orient, body_pose, betas, transl), fp32 (M, -1) like the Function's inputs; ``needs``: which of
+        them are wanted.  g_verts / g_joints: cotangents of vertices / joints or None."""
+        if (g_verts is None and g_joints is None) or not any(needs):
+            return (None, None, None, None)
+        dev, J, M = g.device, self.NUM_JOINTS, g.shape[0]
+        f32 = dict(device=dev, dtype=torch.float32)
+        P, IP, s = _capi.ptr, _capi.iptr, _capi.stream()
+        g_verts = None if g_verts is None else _capi.f32c(g_verts)
+        g_joints = None if g_joints is None else _capi.f32c(g_joints)
+        is_rotmat = 0 if pose2rot else 1
+        picked = g_verts is None and self._n_picked > 0
+        if picked:
+            t = self._picked_tables()
+        else:
+            t = dict(V=self.num_verts, N=self._N, np=self._np, bmat=self._bmat, v_template=self._v_template_flat, w_idx=self._w_idx,
+                     w_val=self._w_val, csrt=(self._csrt_ptr, self._csrt_row, self._csrt_val))
+        mp = _capi.query_workspace(_capi.WS_SMPL_MP, M)
+        xt = torch.empty(self._kp, mp, **f32)
+        a = torch.empty(M, J, 12, **f32)
+        j_posed = torch.empty(M, J, 3, **f32)
+        fwd_args = (P(g), P(b), is_rotmat, P(be), self.num_betas, P(self._j_template), P(self._j_shapedirs),
+                    IP(self._parents_i32), IP(self._depth_i32), J)
+        _capi.call("hps_smpl_pose_prep", *fwd_args, P(xt), self._kp, mp, P(a), P(j_posed), None, M, s)
+        ld = t["np"]
+        v_posed = torch.empty(M, ld, **f32)          # becomes g_vposed in place
+        _capi.call("hps_smpl_blend", P(xt), P(t["bmat"]), P(t["v_template"]), P(v_posed), M, t["N"], self._kp, mp, t["np"], ld, s)
+        g_a = torch.empty(M, J, 12, **f32)
+        g_tr = torch.empty(M, 3, **f32) if needs[3] else None
+        ws = torch.empty(_capi.query_workspace(_capi.WS_SMPL_LBS_BWD, M, t["V"], J) // 4, **f32)
+        csrt = t["csrt"] if g_joints is not None else (None, None, None)
+        _capi.call("hps_smpl_lbs_backward", P(v_posed), ld, P(a), IP(t["w_idx"]), P(t["w_val"]), self._lbs_k, J, P(g_verts),
+                   P(g_joints), self._n_joint_rows, IP(csrt[0]), IP(csrt[1]), P(csrt[2]), P(g_a), P(g_tr), P(ws), M, t["V"], s)
+        g_g = g_b = g_be = g_xt = None
+        if any(needs[:3]):
+            g_xt = torch.empty(self._kp, mp, **f32)
+            ws2 = torch.empty(_capi.query_workspace(_capi.WS_SMPL_BLEND_BWD, M, self._kp, t["np"]) // 4, **f32)
+            _capi.call("hps_smpl_blend_backward", P(t["bmat"]), P(v_posed), P(g_xt), P(ws2), M, self._kp, mp, t["np"], ld, s)
+            g_g = torch.empty_like(g) if needs[0] else None
+            g_b = torch.empty_like(b) if needs[1] else None
+            g_be = torch.empty_like(be) if needs[2] else None
+            _capi.call("hps_smpl_pose_prep_backward", *fwd_args, P(g_a), P(g_joints), self._n_joint_rows, P(g_xt), mp, P(g_g),
+                       P(g_b), P(g_be), M, s)
+        if self.keep_intermediates:                                         # tests / profiling only
+            self._last_backward = dict(route="picked" if picked else "dense", M=M, g_a=g_a, g_xt=g_xt, g_vposed=v_posed)
+        return (g_g, g_b, g_be, g_tr)
+
     # ------------------------------------------------------------------------------------------
     def forward(self, betas=None, body_pose=None, global_orient=None, transl=None, pose2rot=True,
                 return_verts=True, return_full_pose=False, **kwargs):
         """smplx SMPL.forward semantics as used by the reference (models/smpl_official.py:27-41):
         omitted arguments default to the zero module parameters; betas with fewer rows than the pose
-        are expanded; ``pose2rot=False`` takes rotation matrices, otherwise axis-angle."""
+        are expanded; ``pose2rot=False`` takes rotation matrices, otherwise axis-angle.
+
+        Differentiable: with grad mode on and any of betas / body_pose / global_orient / transl (the module's own parameters
+        included) requiring grad, the call goes through a torch.autograd.Function.  Its forward launches the kernels of a no_grad
+        call in their K = 217 forms (hps_smpl_mesh_fused[_picks], or blend + lbs with ``fused_mesh = False``, then hps_smpl_joints) and
+        returns the same bits; ``mesh_arith = "bf16x3"`` and ``shared_shape`` do not apply on this route.  The backward saves the
+        inputs only, recomputes xt / a / v_posed and runs hps_smpl_lbs_backward, hps_smpl_blend_backward and
+        hps_smpl_pose_prep_backward; when only ``joints`` received a cotangent it runs them on the regressor vertices alone
+        (``_last_backward["route"] == "picked"`` under ``keep_intermediates``).  For ``pose2rot=False`` the pose gradients are those of
+        the unconstrained matrix entries.  No host synchronisation either way.  The private hooks of the inference pipeline
+        (``_shared_shapes``, ``_before_mesh``, ``_after_mesh``, ``_defer_joints``) cannot be combined with it: ValueError."""
         dev = self.v_template.device
         _capi.require_device(self.v_template, "SMPL buffers (call .to('cuda'))")
         J = self.NUM_JOINTS
@@ -233,6 +344,16 @@ class SMPL(DeviceStateModule):
         if be.shape[1] != self.num_betas:
             raise ValueError("betas must have %d columns" % self.num_betas)
         tr = None if transl is None else _capi.f32c(transl).reshape(M, 3)
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (g, b, be, tr)):
+            hooks = [h for h in ("_shared_shapes", "_before_mesh", "_after_mesh", "_defer_joints") if kwargs.get(h) is not None]
+            if hooks:
+                raise ValueError("SMPL.forward: %s cannot be combined with inputs that require grad (the hooks belong to the "
+                                 "inference pipeline, which has no backward)" % ", ".join(hooks))
+            # (betas were expanded and every input brought to fp32 (M, -1) above, OUTSIDE the Function: autograd sums / casts back)
+            verts, joints = _SMPLFunction.apply(self, bool(pose2rot), g, b, be, tr)
+            return SMPLOutput(vertices=verts if return_verts else None, joints=joints,
+                              full_pose=torch.cat([g, b], dim=1) if return_full_pose else None,
+                              betas=betas, global_orient=global_orient, body_pose=body_pose)
 
         V, N = self.num_verts, self._N
         mp = _capi.query_workspace(_capi.WS_SMPL_MP, M)                  # padded mesh count of the blend operand
@@ -256,7 +377,7 @@ class SMPL(DeviceStateModule):
             raise ValueError("mesh_arith must be 'f32' or 'bf16x3', got %r" % (self.mesh_arith,))
         # bf16x3: the shared-shape form (207 pose rows), or -- no shared shapes, SMPL configuration, no translation -- the same kernel over
         # all 217 rows with v_template as the one "shaped template" (the shape blend inside the GEMM, as in the fp32 K = 217 form)
-        split = self.mesh_arith == "bf16x3" and use_picks and tr is None and self.fused_mesh
+        split = self.mesh_arith == "bf16x3" and use_picks and tr is None and self.fused_mesh and not kwargs.get("_k217")
         split_rows = (self.num_betas, self._n_pose) if shared is not None else (0, self.num_betas + self._n_pose)      # (first row, rows)
         xsplit = bsplit = None
         if shared is not None:

@@ -97,9 +97,11 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_HEAD_F      (d0 = B, d1 = largest level size)        f_level_dev / f_host_pinned of hps_head_pose_levels
  *   HPS_WS_HEAD_USV    (d0 = B, d1 = largest level size)        usv_level_dev / usv_host_pinned of hps_head_pose_levels
  *   HPS_WS_MF_LOSS     (d0 = n_pose)                            workspace of hps_mf_loss_forward / hps_mf_loss_backward
+ *   HPS_WS_SMPL_LBS_BWD   (d0 = M, d1 = V, d2 = num_joints)     workspace of hps_smpl_lbs_backward (per-chunk partial sums of g_a)
+ *   HPS_WS_SMPL_BLEND_BWD (d0 = M, d1 = kp, d2 = np)            workspace of hps_smpl_blend_backward (per-slice partial sums of g_xt)
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
-       HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8 };
+       HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -235,6 +237,58 @@ int hps_joints_and_uncertainty(const float* picked, const float* j_posed, const 
 int hps_smpl_joints(const float* verts, const float* j_posed, const int32_t* csr_ptr,
                     const int32_t* csr_col, const float* csr_val, int n_rows, int num_joints,
                     const float* transl, float* joints, int M, int V, hps_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * SMPL backward  (the reference differentiates its SMPL with torch autograd: train/train_poseMF_shapeGaussian_net.py:268-271
+ * mode mesh, :304-308 sample meshes of which only .joints is used, loss at :346)
+ * ----------------------------------------------------------------------------------------
+ * Cotangents: g_verts (M,V,3) of the vertices and g_joints (M, num_joints + n_rows, 3) of hps_smpl_joints' output; either may be
+ * NULL.  With C the CSR matrix of hps_smpl_joints:  gV' = g_verts + C^T g_joints[num_joints:].  The three calls run in this order
+ * on what hps_smpl_pose_prep (xt, a) and hps_smpl_blend (v_posed) recompute from the forward's inputs.  Every reduction is
+ * per-workgroup partial sums in `workspace` added in a fixed order by a second launch: no floating-point atomics, bitwise
+ * repeatable, and a mesh's result does not depend on M. */
+
+/* Backward of hps_smpl_lbs / the skinning epilogue of the fused kernels (smplx 0.1.26 lbs: T = W @ A, v_homo = T @ v_posed_homo)
+ * and of the translation (SMPL.forward: vertices + transl, joints + transl), with T_v = sum_k w_val[v,k] A[w_idx[v,k]]:
+ *   v_posed[m, 3v..] <- g_vposed_v = T_v.R^T gV'_v   IN PLACE (the lane that reads v_posed_v writes g_vposed_v); the columns
+ *                       [3V, ld_vposed) of every row are written as zeros (hps_smpl_blend_backward contracts over them)
+ *   g_a (M,J,12)      : g_a[j].R = sum_v W[v,j] gV'_v (x) v_posed_v,  g_a[j].t = sum_v W[v,j] gV'_v   (row-major 3x4 like a)
+ *   g_transl (M,3)    : sum_v gV'_v + sum_{j < num_joints} g_joints[j] (the partial sums are added in float64 and rounded once);
+ *                       optional (NULL: not wanted)
+ * csrt_ptr (V+1,), csrt_row, csrt_val: C^T in CSR form over the V vertices (entries of a vertex in the order of C's rows);
+ * needed with g_joints only.  The vertex sums run as v_mfma_f32_32x32x2_f32 products (rows = joints, columns = two meshes' 12
+ * entries) over chunks of 128 vertices; workspace: hps_query_workspace(HPS_WS_SMPL_LBS_BWD, M, V, num_joints) bytes.
+ * K = 4, 8, 12, 24; num_joints <= 31; n_rows <= 96 (HPS_E_UNSUPPORTED beyond).  V may be any vertex subset with its own w_idx / w_val / csrt (the joints-only route:
+ * the distinct regressor vertices). */
+int hps_smpl_lbs_backward(float* v_posed, int ld_vposed, const float* a, const int32_t* w_idx, const float* w_val, int K,
+                          int num_joints, const float* g_verts, const float* g_joints, int n_rows, const int32_t* csrt_ptr,
+                          const int32_t* csrt_row, const float* csrt_val, float* g_a, float* g_transl, float* workspace, int M,
+                          int V, hps_stream_t stream);
+
+/* Backward of hps_smpl_blend / the GEMM of the fused kernels (smplx lbs: blend_shapes einsum 'bl,mkl->bmk' and
+ * torch.matmul(pose_feature, posedirs)) with respect to its mesh operand:
+ *   g_xt[k, m] = sum_n bmat[k, n] * g_vposed[m, n]      k < kp; columns m in [M, mp) are written as zeros
+ * rows [0, num_betas) are the direct shape gradient, the following 9 (J - 1) rows the pose-feature gradient.  bmat (kp, np) as
+ * for hps_smpl_blend (np a multiple of 128, zero padded), g_vposed (M, ld_g) with ld_g >= np, a multiple of 4, and FINITE values
+ * in its padding columns (hps_smpl_lbs_backward leaves zeros); mp = M rounded up to 128.  fp32 MFMA, the forward blend's
+ * 2 kp np FLOP per mesh; the contraction is cut into slices of 512 columns (a workgroup = one slice x 128 meshes, so small M
+ * still spreads over np / 512 workgroups) whose partial sums are added in slice order.
+ * workspace: hps_query_workspace(HPS_WS_SMPL_BLEND_BWD, M, kp, np) bytes. */
+int hps_smpl_blend_backward(const float* bmat, const float* g_vposed, float* g_xt, float* workspace, int M, int kp, int mp,
+                            int np, int ld_g, hps_stream_t stream);
+
+/* Backward of hps_smpl_pose_prep (smplx lbs: batch_rodrigues, vertices2joints folded into j_template / j_shapedirs, pose_feature,
+ * batch_rigid_transform).  glob .. num_joints: the forward's inputs (it recomputes rotations, rest joints and world transforms).
+ * g_a (M,J,12) from hps_smpl_lbs_backward; g_joints (M, num_joints + n_rows, 3) or NULL: its first num_joints rows are the
+ * cotangent of j_posed; g_xt (kp, mp) from hps_smpl_blend_backward or NULL.  Walks the kinematic levels from the leaves to the root.
+ *   g_glob, g_body : shaped like glob / body.  is_rotmat: 9 values per joint, the derivative with respect to the unconstrained matrix
+ *                    entries (what torch autograd gives); otherwise 3 per joint through batch_rodrigues including its
+ *                    angle = ||r + 1e-8|| (finite at r = 0).  Either may be NULL.
+ *   g_betas (M, num_betas) = g_xt[:num_betas]^T + j_shapedirs^T g_J, optional. */
+int hps_smpl_pose_prep_backward(const float* glob, const float* body, int is_rotmat, const float* betas, int num_betas,
+                                const float* j_template, const float* j_shapedirs, const int32_t* parents, const int32_t* depth,
+                                int num_joints, const float* g_a, const float* g_joints, int n_rows, const float* g_xt, int mp,
+                                float* g_glob, float* g_body, float* g_betas, int M, hps_stream_t stream);
 
 /* Per-vertex uncertainty of utils/sampling_utils.py:189-190, batched over images:
  * verts (B,N,V,3) -> unc (B,V) = mean_s || verts[b,s,v] - mean_s' verts[b,s',v] ||. */
