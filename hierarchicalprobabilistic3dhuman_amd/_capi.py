@@ -92,6 +92,10 @@ _PROTOTYPES = {
     "hps_mf_nll": [_P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _P, _P],
     "hps_mf_loss_forward": [_P, _P, _P, _P],
     "hps_mf_loss_backward": [_P, _P, _P, _P],
+    "hps_head_forward_refine": [_P, _I] + [_P] * 9 + [_I] + [_P] * 6 + [_c.c_float] + [_P] * 13 + [_I] * 7 + [_P],
+    "hps_head_pose_levels_backward": [_P, _I, _I, _P, _P, _I] + [_P] * 21 + [_I, _I, _I, _P],
+    "hps_head_trunk_backward": [_P, _I] + [_P] * 20 + [_I] * 7 + [_P],
+    "hps_rot6d_to_rotmat_backward": [_P, _P, _P, _I, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t}
@@ -288,6 +292,7 @@ def call(name, *args):
 WS_CONV_SPLITK, WS_SMPL_MP, WS_SMPL_XT, WS_SMPL_A, WS_SMPL_VPOSED, WS_HEAD_F, WS_HEAD_USV = range(7)
 WS_MF_LOSS = 8
 WS_SMPL_LBS_BWD, WS_SMPL_BLEND_BWD = 9, 10
+WS_HEAD_LEVELS_BWD, WS_HEAD_TRUNK_BWD = 11, 12
 
 
 def query_workspace(what, d0=0, d1=0, d2=0):

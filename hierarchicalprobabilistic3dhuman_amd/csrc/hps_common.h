@@ -21,6 +21,9 @@ int64_t mf_loss_ws_bytes(int64_t rows);
 // bytes of the hps_smpl_lbs_backward / hps_smpl_blend_backward workspaces (csrc/smpl_backward.hip; HPS_WS_SMPL_LBS_BWD / _BLEND_BWD)
 int64_t lbs_backward_ws_bytes(int64_t M, int64_t V, int64_t J);
 int64_t blend_backward_ws_bytes(int64_t M, int64_t kp, int64_t np);
+// bytes of the hps_head_pose_levels_backward / hps_head_trunk_backward workspaces (csrc/head_backward.hip; HPS_WS_HEAD_LEVELS_BWD / _TRUNK_BWD)
+int64_t head_levels_backward_ws_bytes(int64_t B, int64_t total_in, int64_t NJ);
+int64_t head_trunk_backward_ws_bytes(int64_t B, int64_t wide, int64_t nt);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

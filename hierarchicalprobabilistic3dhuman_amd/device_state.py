@@ -24,7 +24,8 @@ class DeviceStateModule(nn.Module):
 
     def invalidate(self, *_):
         """Drop the derived device state; the next forward rebuilds it from the current parameters and switches.  Call it by hand
-        after editing parameters in place.  (Also the load_state_dict post hook: nn.Module.load_state_dict recurses with
+        after editing parameters in place (PoseMFShapeGaussianNet does it itself for its head parameters once it has run a
+        differentiable forward: it compares their version counters on every forward).  (Also the load_state_dict post hook: nn.Module.load_state_dict recurses with
         _load_from_state_dict and never calls a child's load_state_dict, but it runs the children's post hooks.)"""
         self._device_state = {}
 

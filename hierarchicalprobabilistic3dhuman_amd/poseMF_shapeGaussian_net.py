@@ -21,6 +21,17 @@ mathematics, they feed the child joints' MLPs through U_proper (:126-130), and t
                       synchronisation.
   "host"              the reference's very routine: MKL sgesdd on the host, one D2H / sync / H2D round trip per kinematic
                       level.
+
+Training (the reference's step, train/train_poseMF_shapeGaussian_net.py:262-349).  With grad mode on and ``input_feats`` or a head
+parameter requiring grad, the head runs inside a torch.autograd.Function: its forward launches exactly the kernels of a no_grad
+call (same bits for all eight outputs, in either latency mode and either SVD mode), its backward is hps_head_forward_refine (the head
+again in float64), hps_head_pose_levels_backward and hps_head_trunk_backward (csrc/head_backward.hip) and needs only the features and
+the saved pose_U's signs, so the host-SVD mode is differentiable
+too.  The one difference from the reference: ``pose_U`` and ``pose_V`` are marked non-differentiable (the loss detaches them and the
+sampler draws without grad).  The encoder is not differentiable: with ``input`` given the features are a constant.
+From the first differentiable forward on, the module compares its head parameters' ``_version`` counters with the ones recorded by
+``prepare()`` on every forward (no_grad ones included) and rebuilds the kernel-side copies when an optimiser step changed them;
+modules that never take the differentiable route do not look and behave as before.
 """
 import os
 
@@ -57,6 +68,33 @@ def immediate_parents_to_all_parents(immediate_parents):
         joint, parent = smpl_idx - 1, immediate_parents[smpl_idx] - 1
         all_parents[joint] = [parent] + all_parents[parent] if parent >= 0 else []
     return all_parents
+
+
+class _HeadFunction(torch.autograd.Function):
+    """The head (:95-162) for autograd: forward = the module's own kernel sequence, backward = the head again in float64 and the two device
+    backward composites (_head_backward), without the kernels whose result ``ctx.needs_input_grad`` does not ask for.
+    Inputs after ``feats``: the head parameters in the order of ``PoseMFShapeGaussianNet._head_params()``."""
+
+    @staticmethod
+    def forward(ctx, net, p, feats, *params):
+        outs = net._head(feats, p)
+        pose_F, pose_U, pose_S, pose_V, mode, loc, scale, glob, cam = outs
+        ctx.net, ctx.p = net, p                        # p owns the kernel-side weights the backward reads
+        ctx.save_for_backward(feats, pose_U, scale, *params)      # the backward evaluates the head again (in float64) from these
+        ctx.mark_non_differentiable(pose_U, pose_V)
+        ctx.set_materialize_grads(False)               # an output without a cotangent arrives as None: a NULL pointer for the kernels
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_F, _g_U, g_S, _g_V, g_mode, g_loc, g_scale, g_glob, g_cam):
+        feats, pose_U, scale = ctx.saved_tensors[:3]
+        need = ctx.needs_input_grad
+        g_feats, g_params = ctx.net._head_backward(ctx.p, feats, pose_U, scale, g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam,
+                                                   want_feats=need[2], want_params=any(need[3:]))
+        if g_params is None:
+            return (None, None, g_feats) + (None,) * len(need[3:])
+        return (None, None, g_feats) + tuple(g if n else None for g, n in zip(g_params, need[3:]))
 
 
 class PoseMFShapeGaussianNet(DeviceStateModule):
@@ -100,6 +138,7 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         self.svd_mode = "device"       # "device": in-kernel gesdd-faithful SVD; "host": MKL sgesdd round trip (the routine itself)
         self.svd_flavor = None         # None: the rounding flavour of this host's MKL (calibrated); 0 / 1 force one
         self.latency_mode = False      # set_latency_mode(): encoder on direct kernels with many K slices, joint MLPs on wide workgroups
+        self._track_versions = False   # set by the first differentiable forward: parameters may now change in place (optimiser steps)
 
     def set_latency_mode(self, on=True):
         """One switch for one-image-at-a-time deployments (the reference's run_predict operating point): the encoder's latency mode
@@ -164,13 +203,121 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         p["level_joints"] = torch.tensor([j for l in self.levels for j in l], dtype=torch.int32, device=dev)
         p["level_sizes_host"] = torch.tensor([len(l) for l in self.levels], dtype=torch.int32)
         p["max_level_size"] = max(len(l) for l in self.levels)
+        if self._track_versions:
+            p["versions"] = self._head_versions()
         self._prepared = p
         return p
 
+    def _head_params(self):
+        """The head's parameters in the order _HeadFunction takes them and _head_backward returns their gradients."""
+        ps = [self.fc1.weight, self.fc1.bias, self.fc_shape.weight, self.fc_shape.bias, self.fc_glob.weight, self.fc_glob.bias,
+              self.fc_cam.weight, self.fc_cam.bias, self.fc_embed.weight, self.fc_embed.bias]
+        for m in self.fc_pose:
+            ps += [m[0].weight, m[0].bias, m[2].weight, m[2].bias]
+        return ps
+
+    def _head_versions(self):
+        return tuple(w._version for w in self._head_params())
+
+    def _prepare_backward(self, p):
+        """What only the backward needs, built at the first backward of a prepared state: the weights in nn.Linear's own layout (the
+        forward holds them transposed), the descendant table (who reads joint a's U_proper / S_proper / mode, and at which position of
+        its ancestor list) and the offsets of the joints' MLP inputs."""
+        q = p.get("bwd")
+        if q is not None:
+            return q
+        dev = self.fc1.weight.device
+        c = lambda w: w.detach().float().contiguous()
+        i32 = lambda v: torch.tensor(v if v else [0], dtype=torch.int32, device=dev)
+        nj, embed_dim = self.num_joints, self.config.MODEL.EMBED_DIM
+        desc_ptr, desc_joint, desc_pos = [0], [], []
+        for a in range(nj):
+            for d in range(nj):
+                if a in self.parents_dict[d]:
+                    desc_joint.append(d)
+                    desc_pos.append(self.parents_dict[d].index(a))
+            desc_ptr.append(len(desc_joint))
+        in_off = [0]
+        for j in range(nj):
+            in_off.append(in_off[-1] + embed_dim + 21 * len(self.parents_dict[j]))
+        q = dict(fc1_w=c(self.fc1.weight), embed_w=c(self.fc_embed.weight),
+                 sgc_w=c(torch.cat([self.fc_shape.weight, self.fc_glob.weight, self.fc_cam.weight], dim=0)),
+                 desc_ptr=i32(desc_ptr), desc_joint=i32(desc_joint), desc_pos=i32(desc_pos), in_off=i32(in_off),
+                 in_off_host=in_off, total_in=in_off[-1])
+        p["bwd"] = q
+        return q
+
+    def _head_backward(self, p, feats, pose_U, scale, g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam, want_feats=True, want_params=True):
+        """(g_feats, parameter gradients in _head_params() order) from the cotangents of pose_F, pose_S, pose_rotmats_mode, the
+        Gaussian's loc / scale, glob and cam (None = zero): hps_head_forward_refine (the forward again in float64, signs of the singular
+        vectors from the saved pose_U), hps_head_pose_levels_backward, then hps_head_trunk_backward.  ``want_feats`` / ``want_params``
+        False (frozen features / all head parameters frozen): that result is None and its kernels are not launched."""
+        q = self._prepare_backward(p)
+        B, dev = feats.shape[0], feats.device
+        nj, embed_dim = self.num_joints, self.config.MODEL.EMBED_DIM
+        nsh, ng, nc = self.num_shape_params, self.num_glob_params, self.num_cam_params
+        nt = 2 * nsh + ng + nc
+        nf, hidden = feats.shape[1], p["fc1_wt"].shape[1]
+        P, VP, s = _capi.ptr, _capi._P, _capi.stream()
+        f32 = dict(device=dev, dtype=torch.float32)
+        G = lambda g: None if g is None else _capi.f32c(g)
+        g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam = G(g_F), G(g_S), G(g_mode), G(g_loc), G(g_scale), G(g_glob), G(g_cam)
+        tail = embed_dim // 2 + 9 * (embed_dim // 2) + 9
+        # the forward again in float64 (hps_head_forward_refine): the values the backward differentiates at
+        f64 = dict(device=dev, dtype=torch.float64)
+        D = lambda t: _capi.ptr(t, torch.float64)
+        delta = float(self.config.MODEL.DELTA_I_WEIGHT) if self.config.MODEL.DELTA_I else 0.0
+        x_f, sgc_f, embed_f = torch.empty(B, hidden, **f32), torch.empty(B, nt, **f32), torch.empty(B, embed_dim, **f32)
+        x_d, sgc_d, embed_d = torch.empty(B, hidden, **f64), torch.empty(B, nt, **f64), torch.empty(B, embed_dim, **f64)
+        Up_d, Sp_d, mode_d = torch.empty(B, nj, 9, **f64), torch.empty(B, nj, 3, **f64), torch.empty(B, nj, 9, **f64)
+        U_d, S_d, V_d = torch.empty(B, nj, 9, **f64), torch.empty(B, nj, 3, **f64), torch.empty(B, nj, 9, **f64)
+        _capi.call("hps_head_forward_refine", P(feats), nf, P(p["fc1_wt"]), P(p["fc1_b"]), P(p["sgc_wt"]), P(p["sgc_b"]), P(p["sgc_add"]),
+                   P(p["embed_wt"]), P(p["embed_b"]), _capi.iptr(p["level_joints"]), VP(p["level_sizes_host"].data_ptr()),
+                   len(p["levels"]), _capi.iptr(p["anc_ptr"]), _capi.iptr(p["anc_idx"]), VP(p["w1t_ptrs"].data_ptr()),
+                   VP(p["b1_ptrs"].data_ptr()), VP(p["w2_ptrs"].data_ptr()), VP(p["b2_ptrs"].data_ptr()), delta, P(pose_U), P(x_f),
+                   P(sgc_f), P(embed_f), D(x_d), D(sgc_d), D(embed_d), D(Up_d), D(Sp_d), D(mode_d), D(U_d), D(S_d), D(V_d), B, nf, hidden,
+                   nt, embed_dim, embed_dim // 2, nj, s)
+        g_embed = torch.empty(B, embed_dim, **f32)
+        # one flat buffer for the 92 fc_pose gradients (one allocation, one launch); the tensors handed out are views of it
+        g_pose = torch.empty((embed_dim // 2) * q["total_in"] + nj * tail, **f32) if want_params else None
+        ws = torch.empty(_capi.query_workspace(_capi.WS_HEAD_LEVELS_BWD, B, q["total_in"], nj) // 4, **f32)
+        _capi.call("hps_head_pose_levels_backward", D(embed_d), embed_dim, embed_dim // 2, _capi.iptr(p["level_joints"]),
+                   VP(p["level_sizes_host"].data_ptr()), len(p["levels"]), _capi.iptr(p["anc_ptr"]), _capi.iptr(p["anc_idx"]),
+                   _capi.iptr(q["desc_ptr"]), _capi.iptr(q["desc_joint"]), _capi.iptr(q["desc_pos"]), _capi.iptr(q["in_off"]),
+                   VP(p["w1t_ptrs"].data_ptr()), VP(p["b1_ptrs"].data_ptr()), VP(p["w2_ptrs"].data_ptr()), D(Up_d), D(Sp_d),
+                   D(mode_d), D(U_d), D(S_d), D(V_d), P(g_F), P(g_S), P(g_mode), P(g_embed), P(g_pose), P(ws), B, nj,
+                   q["total_in"], s)
+        E = lambda *shape: torch.empty(*shape, **f32) if want_params else None
+        g_feats = torch.empty(B, nf, **f32) if want_feats else None
+        g_fc1_w, g_fc1_b = E(hidden, nf), E(hidden)
+        g_sgc_w, g_sgc_b = E(nt, hidden), E(nt)
+        g_embed_w, g_embed_b = E(embed_dim, nf + nt), E(embed_dim)
+        ws2 = torch.empty(_capi.query_workspace(_capi.WS_HEAD_TRUNK_BWD, B, nf + hidden + embed_dim, nt) // 4, **f32)
+        _capi.call("hps_head_trunk_backward", P(feats), nf, P(x_f), P(sgc_f), P(embed_f), P(scale), P(q["fc1_w"]), P(q["sgc_w"]),
+                   P(q["embed_w"]), P(g_embed), P(g_loc), P(g_scale), P(g_glob), P(g_cam), P(g_feats), P(g_fc1_w), P(g_fc1_b),
+                   P(g_sgc_w), P(g_sgc_b), P(g_embed_w), P(g_embed_b), P(ws2), B, nf, hidden, nsh, ng, nc, embed_dim, s)
+        if not want_params:
+            return g_feats, None
+        a, b = 2 * nsh, 2 * nsh + ng
+        grads = [g_fc1_w, g_fc1_b, g_sgc_w[:a], g_sgc_b[:a], g_sgc_w[a:b], g_sgc_b[a:b], g_sgc_w[b:], g_sgc_b[b:], g_embed_w, g_embed_b]
+        hid = embed_dim // 2
+        for j in range(nj):
+            o = hid * q["in_off_host"][j] + j * tail
+            in_dim = q["in_off_host"][j + 1] - q["in_off_host"][j]
+            grads += [g_pose[o:o + hid * in_dim].view(hid, in_dim), g_pose[o + hid * in_dim:o + hid * in_dim + hid],
+                      g_pose[o + hid * in_dim + hid:o + hid * in_dim + hid + 9 * hid].view(9, hid), g_pose[o + hid * in_dim + 10 * hid:o + hid * in_dim + 10 * hid + 9]]
+        return g_feats, grads
+
     # ------------------------------------------------------------------------------------------
     def _trunk(self, feats, p):
+        """(embed, the Gaussian over the betas, glob, cam) of _trunk_launch."""
+        embed, loc, scale, glob, cam = self._trunk_launch(feats, p)
+        return embed, Normal(loc=loc, scale=scale, validate_args=False), glob, cam
+
+    def _trunk_launch(self, feats, p):
         """:95-110: fc1 / ELU, the Gaussian over the betas, glob, cam, the embedding -- three launches (hps_head_trunk); the Gaussian's
-        mean / exp(log std), glob and cam come out contiguous: no concatenation buffer, no torch.exp, no clones on the head's stream."""
+        mean / exp(log std), glob and cam come out contiguous: no concatenation buffer, no torch.exp, no clones on the head's stream.
+        Returns embed, loc, scale, glob, cam."""
         B, dev = feats.shape[0], feats.device
         nsh, ng, nc = self.num_shape_params * 2, self.num_glob_params, self.num_cam_params
         embed_dim = self.config.MODEL.EMBED_DIM
@@ -188,7 +335,7 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         _capi.call("hps_head_trunk", P(feats), nf, P(p["fc1_wt"]), P(p["fc1_b"]), P(p["sgc_wt"]), P(p["sgc_b"]), P(p["sgc_add"]),
                    P(p["embed_wt"]), P(p["embed_b"]), P(x), P(sgc), P(embed), P(shape_mean), P(shape_scale), P(glob), P(cam), B, nf,
                    hidden, self.num_shape_params, ng, nc, embed_dim, s)
-        return embed, Normal(loc=shape_mean, scale=shape_scale, validate_args=False), glob, cam
+        return embed, shape_mean, shape_scale, glob, cam
 
     def _pose_buffers(self, B, dev):
         """pose_F, pose_U, pose_S, pose_V, U_proper, S_proper, mode: every joint is in exactly one level and ancestors come from earlier
@@ -200,19 +347,36 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
                 torch.empty(B, nj, 3, 3, **f32))
 
     def forward(self, input, input_feats=None):
-        """models/poseMF_shapeGaussian_net.py:85-162.  input: (B,C,D,D); ``input_feats`` skips the encoder."""
+        """models/poseMF_shapeGaussian_net.py:85-162.  input: (B,C,D,D); ``input_feats`` skips the encoder.
+
+        Differentiable with respect to ``input_feats`` and the head's parameters (module docstring); ``pose_U`` / ``pose_V`` carry no
+        gradient.  The encoder is not differentiable: with ``input`` given the features are a constant of the graph."""
         if input_feats is None:
             input_feats = self.image_encoder(input)
         _capi.require_device(input_feats, "input_feats")
+        differentiable = torch.is_grad_enabled() and (input_feats.requires_grad or any(w.requires_grad for w in self._head_params()))
+        if differentiable:
+            self._track_versions = True
+        if self._track_versions and self._prepared is not None and self._prepared.get("versions") != self._head_versions():
+            self.invalidate()                                     # an optimiser step (or any in-place edit) since prepare()
         p = self._prepared or self.prepare()
         feats = _capi.f32c(input_feats)
+        if differentiable:
+            outs = _HeadFunction.apply(self, p, feats, *self._head_params())
+        else:
+            outs = self._head(feats, p)
+        pose_F, pose_U, pose_S, pose_V, mode, loc, scale, glob, cam = outs
+        return pose_F, pose_U, pose_S, pose_V, mode, Normal(loc=loc, scale=scale, validate_args=False), glob, cam
+
+    def _head(self, feats, p):
+        """The head's launches on fp32 contiguous features: (pose_F, pose_U, pose_S, pose_V, mode, loc, scale, glob, cam)."""
         B = feats.shape[0]
         dev = feats.device
         nj = self.num_joints
         embed_dim = self.config.MODEL.EMBED_DIM
         P, s = _capi.ptr, _capi.stream()
         f32 = dict(device=dev, dtype=torch.float32)
-        embed, shape_dist, glob, cam = self._trunk(feats, p)
+        embed, loc, scale, glob, cam = self._trunk_launch(feats, p)
 
         # hierarchical pose prediction (:121-160), one kinematic level at a time
         pose_F, pose_U, pose_S, pose_V, U_proper, S_proper, mode = self._pose_buffers(B, dev)
@@ -242,7 +406,7 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
                        P(pose_V), P(f_dev), P(usv_dev), fh, uh, B, nj, _SVD_THREADS,
                        ((_capi.SVD_DEVICE_FMA if self._flavor() == _capi.SVD_ROUNDING_FMA else _capi.SVD_DEVICE) |
                         (_capi.HEAD_WIDE_WORKGROUPS if self.latency_mode else 0)) if device_svd else _capi.SVD_HOST, s)
-            return pose_F, pose_U, pose_S, pose_V, mode, shape_dist, glob, cam
+            return pose_F, pose_U, pose_S, pose_V, mode, loc, scale, glob, cam
         for lvl in p["levels"]:
             n_level = lvl.numel()
             if device_svd:
@@ -270,4 +434,4 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
             usv.view(B * n_level, 21).copy_(usv_host, non_blocking=True)
             _capi.call("hps_head_svd_finish", P(usv), _capi.iptr(lvl), n_level, P(pose_U), P(pose_S), P(pose_V),
                        P(U_proper), P(S_proper), P(mode), B, nj, s)
-        return pose_F, pose_U, pose_S, pose_V, mode, shape_dist, glob, cam
+        return pose_F, pose_U, pose_S, pose_V, mode, loc, scale, glob, cam

@@ -9,16 +9,42 @@ import torch
 from . import _capi
 
 
+def _rot6d_launch(x6):
+    out = torch.empty(x6.shape[0], 3, 3, device=x6.device, dtype=torch.float32)
+    _capi.call("hps_rot6d_to_rotmat", _capi.ptr(x6), _capi.ptr(out), x6.shape[0], _capi.stream())
+    return out
+
+
+class _Rot6dFunction(torch.autograd.Function):
+    """rot6d_to_rotmat for autograd: the forward is the no_grad call's kernel, the backward hps_rot6d_to_rotmat_backward."""
+
+    @staticmethod
+    def forward(ctx, x6):
+        ctx.save_for_backward(x6)
+        return _rot6d_launch(x6)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        x6, = ctx.saved_tensors
+        g = _capi.f32c(g_out)
+        g_x6 = torch.empty_like(x6)
+        _capi.call("hps_rot6d_to_rotmat_backward", _capi.ptr(x6), _capi.ptr(g), _capi.ptr(g_x6), x6.shape[0], _capi.stream())
+        return g_x6
+
+
 def rot6d_to_rotmat(x):
     """utils/rigid_transform_utils.py:80-94: (B,6) or (B,24*6) -> (B',3,3).
 
     The reference's ``torch.cross`` without ``dim`` (line 93) is silently wrong at exactly B == 3;
-    the cross product along dim 1 is computed here for every B."""
+    the cross product along dim 1 is computed here for every B.
+
+    Differentiable: with grad mode on and ``x`` requiring grad the same kernel runs inside a torch.autograd.Function (same bits)."""
     _capi.require_device(x, "rot6d_to_rotmat input")
     x6 = _capi.f32c(x).reshape(-1, 6)
-    out = torch.empty(x6.shape[0], 3, 3, device=x.device, dtype=torch.float32)
-    _capi.call("hps_rot6d_to_rotmat", _capi.ptr(x6), _capi.ptr(out), x6.shape[0], _capi.stream())
-    return out
+    if torch.is_grad_enabled() and x6.requires_grad:
+        return _Rot6dFunction.apply(x6)
+    return _rot6d_launch(x6)
 
 
 def rotmat_to_rot6d(R, stack_columns=False):

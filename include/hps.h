@@ -99,9 +99,13 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_MF_LOSS     (d0 = n_pose)                            workspace of hps_mf_loss_forward / hps_mf_loss_backward
  *   HPS_WS_SMPL_LBS_BWD   (d0 = M, d1 = V, d2 = num_joints)     workspace of hps_smpl_lbs_backward (per-chunk partial sums of g_a)
  *   HPS_WS_SMPL_BLEND_BWD (d0 = M, d1 = kp, d2 = np)            workspace of hps_smpl_blend_backward (per-slice partial sums of g_xt)
+ *   HPS_WS_HEAD_LEVELS_BWD (d0 = B, d1 = total_in, d2 = num_body_joints)  workspace of hps_head_pose_levels_backward
+ *   HPS_WS_HEAD_TRUNK_BWD  (d0 = B, d1 = num_feats + hidden + embed_dim, d2 = 2 num_shape + num_glob + num_cam)
+ *                                                               workspace of hps_head_trunk_backward
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
-       HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10 };
+       HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
+       HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -357,6 +361,9 @@ int hps_infer_assemble(const float* mode, const float* glob_rotmats, const float
 int hps_quat_to_rotmat(const float* quat, float* rotmat, int n, hps_stream_t stream);
 /* utils/rigid_transform_utils.py:80-94 (cross product along dim 1 for every batch size) */
 int hps_rot6d_to_rotmat(const float* x6, float* rotmat, int n, hps_stream_t stream);
+/* utils/rigid_transform_utils.py:80-94 differentiated: g_x6 (n,6) from x6 (n,6) and the cotangent g_rotmat (n,3,3) of the
+ * rotation matrices; the cross product runs along dim 1 for every n, as in hps_rot6d_to_rotmat. */
+int hps_rot6d_to_rotmat_backward(const float* x6, const float* g_rotmat, float* g_x6, int n, hps_stream_t stream);
 /* smplx.lbs.batch_rodrigues (reference import: predict/predict_poseMF_shapeGaussian_net.py:7) */
 int hps_batch_rodrigues(const float* aa, float* rotmat, int n, hps_stream_t stream);
 
@@ -586,6 +593,74 @@ int hps_head_pose_levels(const float* embed, int embed_dim, int hidden, const in
                          float* pose_s, float* pose_v, float* f_level_dev, float* usv_level_dev,
                          float* f_host_pinned, float* usv_host_pinned, int B, int num_body_joints,
                          int svd_threads, int svd_mode, hps_stream_t stream);
+
+/* ---- backward of the head (what the reference's training step, train/train_poseMF_shapeGaussian_net.py:262-349, gets from
+ * torch autograd).  No floating-point atomics, no synchronisation, bitwise repeatable; the gradient of one image's features
+ * depends on that image alone (same bits at any B); parameter gradients are summed over the images in ascending order with
+ * float64 accumulators. ---- */
+
+/* The forward of the head again in float64, the first step of its backward: models/poseMF_shapeGaussian_net.py:95-160 with float64
+ * sums and float64 values between the stages, a float64 3x3 SVD (one-sided Jacobi) whose column signs are taken from the forward's
+ * pose_U (pose_u_pin, fp32 (B,NJ,3,3)).  Why float64: the gradient's error is the head's second derivative times the error of the
+ * values it is evaluated at, and torch.svd's backward multiplies by 1 / (s_j^2 - s_i^2); the fp32 forward's rounding in F (about
+ * 2^-23 |F|) is amplified by that factor at every joint and handed down the kinematic chain, while the float64 values leave the
+ * backward's own fp32 roundings as the only error.  Weights as in hps_head_trunk / hps_head_pose_levels.
+ * Outputs: x_f (B, hidden_trunk), sgc_f (B, num_sgc), embed_f (B, embed_dim) in fp32 for hps_head_trunk_backward; float64 x_d, sgc_d,
+ * embed_d and u_proper / s_proper / mode / pose_u / pose_s / pose_v (B,NJ,..) for hps_head_pose_levels_backward.  3 + n_levels
+ * launches, no synchronisation. */
+int hps_head_forward_refine(const float* feats, int ldf, const float* fc1_wt, const float* fc1_b, const float* sgc_wt,
+                            const float* sgc_b, const float* sgc_add, const float* embed_wt, const float* embed_b,
+                            const int32_t* level_joints, const int32_t* level_sizes_host, int n_levels,
+                            const int32_t* anc_ptr, const int32_t* anc_idx, const float* const* w1t_ptrs,
+                            const float* const* b1_ptrs, const float* const* w2_ptrs, const float* const* b2_ptrs,
+                            float delta_i_weight, const float* pose_u_pin, float* x_f, float* sgc_f, float* embed_f,
+                            double* x_d, double* sgc_d, double* embed_d, double* u_proper, double* s_proper, double* mode,
+                            double* pose_u, double* pose_s, double* pose_v, int B, int num_feats, int hidden_trunk,
+                            int num_sgc, int embed_dim, int hidden, int num_body_joints, hps_stream_t stream);
+
+/* models/poseMF_shapeGaussian_net.py:121-160 differentiated, kinematic levels from the leaves to the root in one call (one launch
+ * per level as in hps_head_pose_levels, then one launch for g_embed and one for the parameter gradients).  Per joint: the
+ * cotangents of pose_F (:154), pose_S (:156) and pose_rotmats_mode (:160) (g_pose_f (B,NJ,3,3), g_pose_s (B,NJ,3), g_mode
+ * (B,NJ,3,3); each may be NULL = zero), plus what the joint's descendants left on its U_proper / S_proper / mode (:126-128),
+ * go back through mode = U_p V_p^T (:152), the proper fix (:144-150, det U and det V are constants, :139-140), torch.svd's
+ * backward (:137, distinct singular values) and the joint's MLP (:130-135; the hidden activations are computed again).
+ * From a preceding hps_head_forward_refine (float64): embed, u_proper, s_proper, mode, pose_u, pose_s, pose_v; level_joints / level_sizes_host / anc_ptr /
+ * anc_idx / w1t_ptrs / b1_ptrs / w2_ptrs as in hps_head_pose_levels.
+ * desc_ptr (NJ+1), desc_joint, desc_pos (device int32): for joint a the joints d that have a among their ancestors, ascending,
+ * with the position of a in d's ancestor list.  in_off (NJ+1, device int32): prefix sums of in_dim_j = embed_dim + 21 * (number
+ * of ancestors of j); total_in = in_off[NJ].
+ * Outputs: g_embed (B, embed_dim), the cotangent of the embedding (:110) for hps_head_trunk_backward; g_fc_pose: flat buffer of
+ * 128 * total_in + NJ * (128 + 9 * 128 + 9) floats, joint j's [g_W1 (128, in_dim_j) | g_b1 (128) | g_W2 (9, 128) | g_b2 (9)]
+ * in nn.Linear's layout at 128 * in_off[j] + j * (128 + 9 * 128 + 9); NULL: the parameter gradients are not wanted, their launch
+ * is skipped.
+ * workspace: hps_query_workspace(HPS_WS_HEAD_LEVELS_BWD, B, total_in, num_body_joints) bytes. */
+int hps_head_pose_levels_backward(const double* embed, int embed_dim, int hidden, const int32_t* level_joints,
+                                  const int32_t* level_sizes_host, int n_levels, const int32_t* anc_ptr,
+                                  const int32_t* anc_idx, const int32_t* desc_ptr, const int32_t* desc_joint,
+                                  const int32_t* desc_pos, const int32_t* in_off, const float* const* w1t_ptrs,
+                                  const float* const* b1_ptrs, const float* const* w2_ptrs, const double* u_proper,
+                                  const double* s_proper, const double* mode, const double* pose_u, const double* pose_s,
+                                  const double* pose_v, const float* g_pose_f, const float* g_pose_s, const float* g_mode,
+                                  float* g_embed, float* g_fc_pose, float* workspace, int B, int num_body_joints,
+                                  int total_in, hps_stream_t stream);
+
+/* models/poseMF_shapeGaussian_net.py:95-110 differentiated.  feats and shape_scale from the forward; x, sgc, embed: the fp32 outputs
+ * x_f, sgc_f, embed_f of hps_head_forward_refine.  fc1_w (hidden, num_feats), sgc_w (2 num_shape + num_glob + num_cam, hidden) = fc_shape | fc_glob | fc_cam stacked,
+ * embed_w (embed_dim, num_feats + 2 num_shape + num_glob + num_cam): the weights in nn.Linear's own layout.
+ * Cotangents (each may be NULL = zero): g_embed (B, embed_dim), g_loc / g_scale (B, num_shape) of the Gaussian's loc and scale
+ * (scale = exp(log std), :101), g_glob (B, num_glob), g_cam (B, num_cam); the last four reach fc1 directly (:98-107) and through
+ * the concatenation into fc_embed (:108).
+ * Outputs: g_feats (B, num_feats) and the parameter gradients in the layouts of fc1_w / sgc_w / embed_w and their biases (the
+ * rows of g_sgc_w / g_sgc_b are fc_shape's, then fc_glob's, then fc_cam's).
+ * g_feats may be NULL (frozen features); the six parameter gradients may be NULL all together (frozen parameters): what is not
+ * wanted is not launched.
+ * workspace: hps_query_workspace(HPS_WS_HEAD_TRUNK_BWD, B, num_feats + hidden + embed_dim, 2 num_shape + num_glob + num_cam). */
+int hps_head_trunk_backward(const float* feats, int ldf, const float* x, const float* sgc, const float* embed,
+                            const float* shape_scale, const float* fc1_w, const float* sgc_w, const float* embed_w,
+                            const float* g_embed, const float* g_loc, const float* g_scale, const float* g_glob,
+                            const float* g_cam, float* g_feats, float* g_fc1_w, float* g_fc1_b, float* g_sgc_w,
+                            float* g_sgc_b, float* g_embed_w, float* g_embed_b, float* workspace, int B, int num_feats,
+                            int hidden, int num_shape, int num_glob, int num_cam, int embed_dim, hps_stream_t stream);
 
 /* (B,C,H,W) -> interior of the (B, H + 2P, W + 2P, C) NHWC frame; C in {4, 18, 64}
  * (predict/predict_poseMF_shapeGaussian_net.py:103 hands the net an NCHW proxy representation). */
