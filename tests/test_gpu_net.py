@@ -12,6 +12,7 @@ from oracle import ref_cpu as O
 from hierarchicalprobabilistic3dhuman_amd import configs, _capi
 from hierarchicalprobabilistic3dhuman_amd.resnet import _ConvBN
 from conftest import maxerr
+from conv_scenario import assert_halo_untouched
 from devlib import plain_conv, plain_forward, head_levels_fused, sync_workspaces
 
 pytestmark = pytest.mark.gpu
@@ -126,8 +127,7 @@ def test_padded_conv_kernel(cfg, dev):
         cb.padded(xp, ipad, out, opad, residual=_frame(resh, opad), relu=True)
         inner = out[:, opad:opad + Ho, opad:opad + Ho]
         assert maxerr(inner.permute(0, 3, 1, 2), want) <= tol
-        if opad:        # the halo is never written
-            assert float((out[:, 0] - 7).abs().max()) == 0 and float((out[:, :, -1] - 7).abs().max()) == 0
+        assert_halo_untouched(out, opad, 7.0)        # the halo is never written: all four sides
         out2 = torch.zeros_like(out)
         cb.padded(xp, ipad, out2, opad, relu=False)
         assert maxerr(out2[:, opad:opad + Ho, opad:opad + Ho].permute(0, 3, 1, 2), want_nores) <= tol
@@ -209,7 +209,8 @@ def test_down_sample_rides_in_the_blocks_first_convolution(cfg, dev):
         got, got_d = torch.full_like(sep, 7.0), torch.full_like(sep, 7.0)
         c1.padded_with_down(xp, ipad, got, 1, down, got_d)
         assert torch.equal(got, sep) and torch.equal(got_d, sep_d), (variant, ks, latency)
-        assert float((got[:, 0] - 7).abs().max()) == 0 and float((got_d[:, :, -1] - 7).abs().max()) == 0        # the halo is never written
+        assert_halo_untouched(got, 1, 7.0)           # the halo is never written: all four sides of both frames
+        assert_halo_untouched(got_d, 1, 7.0)
         tol = 1e-4 * max(1.0, float(want.abs().max()))
         assert maxerr(got[:, 1:-1, 1:-1].permute(0, 3, 1, 2), want) <= tol and maxerr(got_d[:, 1:-1, 1:-1].permute(0, 3, 1, 2), want_d) <= tol
     c1.ksplit = 0
@@ -521,8 +522,7 @@ def test_winograd_conv_kernel(cfg, dev):
         cb.padded(xp, 1, out, opad, residual=_frame(resh, opad), relu=True)
         inner = out[:, opad:opad + H, opad:opad + H]
         assert maxerr(inner.permute(0, 3, 1, 2), want) <= 1e-5 * scale_ref
-        if opad:        # the halo is never written
-            assert float((out[:, 0] - 7).abs().max()) == 0 and float((out[:, :, -1] - 7).abs().max()) == 0
+        assert_halo_untouched(out, opad, 7.0)        # the halo is never written: all four sides
         out2 = torch.zeros_like(out)
         cb.padded(xp, 1, out2, opad, relu=False)
         assert maxerr(out2[:, opad:opad + H, opad:opad + H].permute(0, 3, 1, 2), want_nores) <= 1e-5 * scale_ref
@@ -580,8 +580,7 @@ def test_winograd_stem_kernel(cfg, dev):
         _capi.call("hps_stem_winograd", P(frames), P(cb.stem_u), P(cb.scale), P(cb.shift), P(out), B, H, W, opad, 1, s)
         inner = out[:, opad:opad + H // 2, opad:opad + W // 2]
         assert float((inner.cpu().double() - want).abs().max()) <= 2e-6 * scale_ref
-        if opad:        # the halo is never written
-            assert float((out[:, 0] - 7).abs().max()) == 0 and float((out[:, :, -1] - 7).abs().max()) == 0
+        assert_halo_untouched(out, opad, 7.0)        # the halo is never written: all four sides
     lin = torch.empty(B, H // 2, W // 2, 64, device=dev)
     _capi.call("hps_stem_winograd", P(frames), P(cb.stem_u), P(cb.scale), P(cb.shift), P(lin), B, H, W, 0, 0, s)
     assert maxerr(lin, want_lin.to(dev)) <= 1e-5 * scale_ref
@@ -635,7 +634,7 @@ def test_stem_with_the_max_pool_in_its_epilogue(cfg, dev):
     _capi.call("hps_stem_winograd_pooled", P(frames), P(cb.stem_u), P(cb.scale), P(cb.shift), P(got), P(side), B, H, W, 1, 1, s)
     torch.cuda.synchronize()
     assert torch.equal(got, want)
-    assert float((got[:, 0] - 7).abs().max()) == 0 and float((got[:, :, -1] - 7).abs().max()) == 0
+    assert_halo_untouched(got, 1, 7.0)
     ref = F.max_pool2d(full.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
     assert torch.equal(got[:, 1:-1, 1:-1], ref)
     # ... and fed by the NCHW input itself (hps_stem_winograd_pooled_nchw gathers the phase windows: no phase split, no frames): equal again
