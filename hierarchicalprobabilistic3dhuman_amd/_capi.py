@@ -96,9 +96,18 @@ _PROTOTYPES = {
     "hps_head_pose_levels_backward": [_P, _I, _I, _P, _P, _I] + [_P] * 21 + [_I, _I, _I, _P],
     "hps_head_trunk_backward": [_P, _I] + [_P] * 20 + [_I] * 7 + [_P],
     "hps_rot6d_to_rotmat_backward": [_P, _P, _P, _I, _P],
+    "hps_conv_wgrad": [_P] * 4 + [_I] * 12 + [_P],
+    "hps_conv_wgrad_slice_pixels": [_I, _I],
+    "hps_conv_wgrad_workspace": [_I] * 9,
+    "hps_conv_dgrad": [_P] * 4 + [_I] * 12 + [_P],
+    "hps_relu_gate_pad": [_P] * 4 + [_I] * 6 + [_P],
+    "hps_relu_gate_workspace": [_I] * 4,
+    "hps_maxpool3x3s2_backward": [_P] * 3 + [_I] * 5 + [_P],
+    "hps_global_avgpool_backward": [_P] * 2 + [_I] * 5 + [_P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
-             "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t}
+             "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
+             "hps_conv_wgrad_workspace": _c.c_size_t, "hps_relu_gate_workspace": _c.c_size_t}
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 

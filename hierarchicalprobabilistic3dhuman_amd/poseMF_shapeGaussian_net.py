@@ -28,7 +28,9 @@ call (same bits for all eight outputs, in either latency mode and either SVD mod
 again in float64), hps_head_pose_levels_backward and hps_head_trunk_backward (csrc/head_backward.hip) and needs only the features and
 the saved pose_U's signs, so the host-SVD mode is differentiable
 too.  The one difference from the reference: ``pose_U`` and ``pose_V`` are marked non-differentiable (the loss detaches them and the
-sampler draws without grad).  The encoder is not differentiable: with ``input`` given the features are a constant.
+sampler draws without grad).  With ``input`` given the encoder is part of the graph too (resnet.py: its own autograd function, device
+backward kernels): the loss reaches every convolution and BatchNorm affine parameter and the input itself -- fine-tuning with frozen
+BatchNorm statistics (eval mode; ``.train()`` stays refused), not the reference's ``model.train()`` step.
 From the first differentiable forward on, the module compares its head parameters' ``_version`` counters with the ones recorded by
 ``prepare()`` on every forward (no_grad ones included) and rebuilds the kernel-side copies when an optimiser step changed them;
 modules that never take the differentiable route do not look and behave as before.
@@ -350,7 +352,8 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         """models/poseMF_shapeGaussian_net.py:85-162.  input: (B,C,D,D); ``input_feats`` skips the encoder.
 
         Differentiable with respect to ``input_feats`` and the head's parameters (module docstring); ``pose_U`` / ``pose_V`` carry no
-        gradient.  The encoder is not differentiable: with ``input`` given the features are a constant of the graph."""
+        gradient.  With ``input`` given the chain goes on through the encoder (ResNet.forward is differentiable with respect to its
+        input and its convolution / BatchNorm affine parameters, eval-mode statistics)."""
         if input_feats is None:
             input_feats = self.image_encoder(input)
         _capi.require_device(input_feats, "input_feats")

@@ -3,9 +3,19 @@ models/resnet.py, executed as implicit-GEMM convolutions on the gfx950 fp32 matr
 
 The ``nn.Conv2d`` / ``nn.BatchNorm2d`` children only hold parameters (so that
 ``load_state_dict(checkpoint['best_model_state_dict'])`` and default initialisation behave exactly as in
-the reference); their own forward is never used.  Inference only: BatchNorm uses running statistics
+the reference); their own forward is never used.  BatchNorm always uses running statistics
 (the reference runs the encoder under ``model.eval()``, predict/...:55) and is fused, together with the
-residual add and ReLU, into the convolution epilogue.
+residual add and ReLU, into the convolution epilogue; ``.train()`` is refused.
+
+Fine-tuning with frozen statistics.  With grad mode on and the input or an encoder parameter requiring grad, ``ResNet.forward`` runs
+inside a torch.autograd.Function: its forward issues exactly the launches of a no_grad call (same bits, in every kernel mode) and
+saves only the input and the parameters.  The backward (csrc/conv_backward.hip) evaluates the encoder once more into a frame set of
+its own -- the activation frames belong to the module and the next forward overwrites them, and the fused stem never writes the
+full-resolution map the max pool's backward needs -- with the forward's kernel family per layer and only the bit-identical fusions
+switched off, so the ReLU masks and pool winners are those of the function the caller evaluated.  This is NOT the reference's
+``model.train()`` step: batch statistics are a different forward and stay out of scope.  From the first differentiable forward on
+the module compares its parameters' ``_version`` counters with those recorded by ``prepare()`` and refolds the filters after an
+optimiser step, as PoseMFShapeGaussianNet does for the head.
 """
 import torch
 from torch import nn
@@ -275,6 +285,30 @@ class FilledStemFrames:
         pass
 
 
+class _EncoderFunction(torch.autograd.Function):
+    """ResNet.forward for autograd: forward = the module's own launches (the bits of a no_grad call), saving only the input and the
+    parameters; backward = the recompute and the device backward kernels (ResNet._backward), without the kernels whose result
+    ``ctx.needs_input_grad`` does not ask for.  Inputs after ``x``: the parameters in the order of ``ResNet._enc_params()``."""
+
+    @staticmethod
+    def forward(ctx, net, prep, gate, x, *params):
+        xc = _capi.f32c(x.detach())
+        feats = net._forward_padded(prep, xc, gate=gate)
+        ctx.net, ctx.prep, ctx.x_dtype = net, prep, x.dtype             # prep owns the folded filters the recompute reads
+        ctx.save_for_backward(xc, *params)
+        return feats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_feats):
+        x = ctx.saved_tensors[0]
+        need = ctx.needs_input_grad
+        g_x, g_params = ctx.net._backward(ctx.prep, x, g_feats, list(need[3:]))
+        if g_x is not None and g_x.dtype != ctx.x_dtype:
+            g_x = g_x.to(ctx.x_dtype)
+        return (None, None, None, g_x) + tuple(g_params)
+
+
 class BasicBlock(nn.Module):
     """models/resnet.py:40-78 (parameter container; executed by ResNet._run_block)."""
     expansion = 1
@@ -333,6 +367,7 @@ class ResNet(DeviceStateModule):
         # profiles/r06_ab.txt).  False = phase split + frame-fed kernel (the cross-check of the tests; callers that fill the frames
         # themselves -- stem_frames -- use the frame-fed kernel either way).
         self.stem_reads_nchw = True
+        self._track_versions = False   # set by the first differentiable forward: parameters may now change in place (optimiser steps)
 
     def _make_layer(self, planes, blocks, stride=1):
         downsample = None
@@ -375,6 +410,8 @@ class ResNet(DeviceStateModule):
         for c in [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]:
             c.latency = self._latency
             c.use_winograd = self._winograd and not self._latency      # latency mode runs every layer on the direct kernel
+        if self._track_versions:
+            prep["versions"] = self._enc_versions()
         self._prepared = prep
         return prep
 
@@ -489,15 +526,16 @@ class ResNet(DeviceStateModule):
         fs["generation"] = fs.get("generation", 0) + 1
         return FilledStemFrames(fs["in"], (B, C, H, W), device, owner=fs, generation=fs["generation"])
 
-    def _forward_padded(self, prep, x, gate=None):
+    def _forward_padded(self, prep, x, gate=None, fs=None):
         """``gate``: optional callable invoked after the input relayout has been enqueued and before the first convolution
         (InferencePipeline: the HBM-bound relayout may run beside the previous batch's MFMA-bound mesh kernel; the
-        convolutions wait)."""
+        convolutions wait).  ``fs``: run on this frame set instead of the module's own for the shape (the backward's recompute)."""
         filled = isinstance(x, FilledStemFrames)
         B, C, H, W = x.shape
         s = _capi.stream()
         P = _capi.ptr
-        fs = self._frame_set(prep, B, C, H, W, x.device, frames=filled)
+        if fs is None:
+            fs = self._frame_set(prep, B, C, H, W, x.device, frames=filled)
         if filled and (not fs["stem_wino"] or fs["in"].data_ptr() != x.frames.data_ptr()):
             raise _capi.HpsError("FilledStemFrames belong to another stream / shape / kernel selection than this forward (fill the "
                                  "frames stem_frames() returned on the stream the encoder runs on)")
@@ -581,14 +619,221 @@ class ResNet(DeviceStateModule):
     def forward(self, x, _gate=None):
         """models/resnet.py:202-217: (B,C,H,W) NCHW fp32 -> (B,512)."""
         if self.training:
-            raise RuntimeError("the MI355X encoder path is inference-only (eval-mode BatchNorm); call .eval()")
+            raise RuntimeError("the MI355X encoder path runs eval-mode BatchNorm only (running statistics, also when fine-tuning); call .eval()")
+        filled = isinstance(x, FilledStemFrames)
+        differentiable = torch.is_grad_enabled() and not filled and (
+            (isinstance(x, torch.Tensor) and x.requires_grad) or any(w.requires_grad for w in self._enc_params()))
+        if differentiable:
+            self._track_versions = True
+        if self._track_versions and self._prepared is not None and self._prepared.get("versions") != self._enc_versions():
+            self.invalidate()                                     # an optimiser step (or any in-place edit) since prepare()
         prep = self._prepared or self.prepare()
-        if isinstance(x, FilledStemFrames):
+        if filled:
             return self._forward_padded(prep, x, gate=_gate)
         _capi.require_device(x, "encoder input")
+        if differentiable:
+            return _EncoderFunction.apply(self, prep, _gate, x, *self._enc_params())
         # every (C, H, W) runs on the product kernels: shapes the stem's fast paths do not take get a channel-padded, even-width input
         # frame (hps_nchw_to_padded_nhwc_generic) in front of the row-mode / direct stem
         return self._forward_padded(prep, _capi.f32c(x), gate=_gate)
+
+    # ---- backward (csrc/conv_backward.hip) ----
+    def _enc_layers(self):
+        """(name, conv, bn) of every convolution in the order of prepare(): the stem, then conv1 / conv2 / downsample per block."""
+        out = [("stem", self.conv1, self.bn1)]
+        for li, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), 1):
+            for bi, blk in enumerate(layer):
+                out.append(("layer%d.%d.c1" % (li, bi), blk.conv1, blk.bn1))
+                out.append(("layer%d.%d.c2" % (li, bi), blk.conv2, blk.bn2))
+                if blk.downsample is not None:
+                    out.append(("layer%d.%d.down" % (li, bi), blk.downsample[0], blk.downsample[1]))
+        return out
+
+    def _enc_params(self):
+        """The parameters in the order _EncoderFunction takes them and _backward returns their gradients: conv weight, BatchNorm
+        weight, BatchNorm bias per convolution of _enc_layers()."""
+        return [w for _, conv, bn in self._enc_layers() for w in (conv.weight, bn.weight, bn.bias)]
+
+    def _enc_versions(self):
+        return tuple(t._version for _, conv, bn in self._enc_layers()
+                     for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+    def _block_names(self):
+        return ["layer%d.%d" % (li, bi) for li, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), 1)
+                for bi in range(len(layer))]
+
+    def _backward_frames(self, prep, B, C, H, W, device):
+        """The backward's own frames for a batch shape on the current stream: an activation set for the recompute (stem output
+        written out, max pool as a launch of its own; phase split + frame-fed kernel where the forward took the Winograd stem -- the
+        same values as the fused launches) and one cotangent frame per activation frame, halos zeroed once."""
+        # the launch list points at ``prep``'s filters: a backward that outlives a kernel-mode switch keeps its own set
+        key = (B, C, H, W, _capi.stream().value, id(prep))
+
+        def build():
+            stem = prep["stem"]
+            fs = self._new_frame_set(prep, B, C, H, W, device, stem.stem_winograd_ok(C, H, W), False, False)
+            z = lambda *shape: torch.zeros(*shape, device=device, dtype=torch.float32)
+            g = {"xin": z(B, H + 6, W + 6, C), "stem": torch.empty_like(fs["stem"]), "pool": torch.zeros_like(fs["pool"]), "blocks": []}
+            y = fs["pool"]
+            for (c1, c2, down), ent in zip(prep["blocks"], fs["blocks"]):
+                g["blocks"].append({"c1": torch.zeros_like(ent["c1"]), "c2": torch.zeros_like(ent["c2"]),
+                                    "tmp": torch.zeros_like(y) if down is not None else None})
+                y = ent["c2"]
+            return fs, g, prep
+        return self._derived("backward_frames", key, build, limit=6)[:2]
+
+    def _recompute(self, prep, x):
+        """The forward again on the backward's frame set: (features, activation frames, cotangent frames)."""
+        B, C, H, W = x.shape
+        fs, g = self._backward_frames(prep, B, C, H, W, x.device)
+        return self._forward_padded(prep, x, fs=fs), fs, g
+
+    def activations(self, x):
+        """(features, {name: NCHW clone}) of the recompute the backward differentiates -- the very code path: 'stem' (conv1 + bn1 +
+        relu), 'pool', and per block 'layerL.j.c1' (after its ReLU), 'layerL.j.c2' (the block's output) and 'layerL.j.down'.  The
+        ReLU masks (map > 0) and the pool winners of the device's function are read off these maps (the tests pin their float64
+        restatement to them)."""
+        if self.training:
+            raise RuntimeError("the MI355X encoder path runs eval-mode BatchNorm only; call .eval()")
+        _capi.require_device(x, "encoder input")
+        with torch.no_grad():
+            if self._track_versions and self._prepared is not None and self._prepared.get("versions") != self._enc_versions():
+                self.invalidate()
+            prep = self._prepared or self.prepare()
+            feats, fs, _ = self._recompute(prep, _capi.f32c(x))
+            nchw = lambda t, p: (t[:, p:t.shape[1] - p, p:t.shape[2] - p] if p else t).permute(0, 3, 1, 2).clone()
+            maps = {"stem": nchw(fs["stem"], 0), "pool": nchw(fs["pool"], 1)}
+            for name, ent in zip(self._block_names(), fs["blocks"]):
+                maps[name + ".c1"], maps[name + ".c2"] = nchw(ent["c1"], 1), nchw(ent["c2"], 1)
+                if ent["down"] is not None:
+                    maps[name + ".down"] = nchw(ent["down"], 1)
+        return feats, maps
+
+    @staticmethod
+    def _prepare_backward(prep):
+        """What only the backward needs, built at the first backward of a prepared state: per convolution the filter as
+        (KH, KW, Cout, Cin) with the folded BatchNorm scale of the output channel multiplied in (float64, rounded once) -- the B
+        operand of hps_conv_dgrad."""
+        q = prep.get("bwd")
+        if q is None:
+            q = prep["bwd"] = {}
+        return q
+
+    def _dgrad_filter(self, prep, name, conv, cb):
+        q = self._prepare_backward(prep)
+        if name not in q:
+            w = conv.weight.detach().double() * cb.scale.double()[:, None, None, None]
+            q[name] = w.permute(2, 3, 0, 1).float().contiguous()
+        return q[name]
+
+    def _backward(self, prep, x, g_feats, needs):
+        """(input gradient or None, parameter gradients in _enc_params() order, None where ``needs`` does not ask) for the cotangent
+        ``g_feats`` (B, 512).  ``needs``: [input] + one flag per parameter.  Kernels whose result nobody wants are not launched: no
+        weight gradient for a frozen convolution, no data gradient below the lowest layer that wants one, the stem's data
+        gradient only for an input that requires grad."""
+        P, s = _capi.ptr, _capi.stream()
+        lib = _capi.load(dev=_capi._use_dev)
+        B, C, H, W = x.shape
+        dev = x.device
+        _, fs, gf = self._recompute(prep, x)
+        layers = self._enc_layers()
+        want = {name: needs[1 + 3 * i:4 + 3 * i] for i, (name, _, _) in enumerate(layers)}
+        mods = {name: (conv, bn) for name, conv, bn in layers}
+        grads = {}
+        ws_cache = {}
+
+        def scratch(nbytes, dtype):
+            n = max(1, nbytes // (8 if dtype == torch.float64 else 4))
+            t = ws_cache.get(dtype)
+            if t is None or t.numel() < n:
+                t = ws_cache[dtype] = torch.empty(n, device=dev, dtype=dtype)
+            return t
+
+        def gate(g, y, Bh, h, w, c, gpad, ypad, want_sums):
+            """g <- g * (y > 0) in place; the per-channel sums of the gated cotangent when a shift / scale gradient wants them."""
+            sums = torch.empty(c, device=dev, dtype=torch.float32) if want_sums else None
+            ws = scratch(int(lib.hps_relu_gate_workspace(Bh, h, w, c)), torch.float64) if want_sums else None
+            _capi.call("hps_relu_gate_pad", P(g), P(y), _capi.ptr(ws, torch.float64) if want_sums else None, P(sums), Bh, h, w, c, gpad, ypad, s)
+            return sums
+
+        def params(name, cb, xf, ipad, cx, cin, hin, win, g, gpad, sums):
+            """Gradients of one convolution's weight and BatchNorm affine from its gated cotangent frame ``g`` and input frame ``xf``."""
+            conv, bn = mods[name]
+            w_w, w_g, w_b = want[name]
+            if not (w_w or w_g or w_b):
+                return
+            d = torch.float64
+            inv_std = torch.rsqrt(bn.running_var.detach().to(d) + bn.eps)
+            dW = dscale = None
+            if w_w or w_g:
+                G = torch.empty(cb.cout, cb.kh, cb.kw, cin, device=dev, dtype=torch.float32)
+                ws = scratch(int(lib.hps_conv_wgrad_workspace(B, hin, win, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad)), torch.float32)
+                _capi.call("hps_conv_wgrad", P(xf), P(g), P(G), P(ws), B, hin, win, ipad, cx, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad,
+                           gpad, s)
+                Gd = G.permute(0, 3, 1, 2).to(d)                                        # (Cout, Cin, KH, KW), the weight's layout
+                if w_w:
+                    dW = (Gd * cb.scale.to(d)[:, None, None, None]).to(conv.weight.dtype).contiguous()
+                if w_g:
+                    dscale = (Gd * conv.weight.detach().to(d)).sum((1, 2, 3))
+            dg = (inv_std * (dscale - bn.running_mean.detach().to(d) * sums.to(d))).to(bn.weight.dtype) if w_g else None
+            db = sums.to(bn.bias.dtype) if w_b else None
+            grads[name] = (dW, dg, db)
+
+        def dgrad(name, cb, g, gpad, other, dx, dpad, cdx, cin, hin, win):
+            conv, _ = mods[name]
+            _capi.call("hps_conv_dgrad", P(g), P(self._dgrad_filter(prep, name, conv, cb)), P(other), P(dx), B, hin, win, cin, cb.cout,
+                       cb.kh, cb.kw, cb.stride, cb.pad, gpad, dpad, cdx, s)
+
+        # which blocks still have somebody below them asking for a gradient
+        names = self._block_names()
+        below = [needs[0] or any(want["stem"])]
+        for name, (c1, c2, down) in zip(names, prep["blocks"]):
+            here = any(want[name + ".c1"]) or any(want[name + ".c2"]) or (down is not None and any(want[name + ".down"]))
+            below.append(below[-1] or here)
+        h, w = fs["hw"]
+        last = fs["blocks"][-1]["c2"]
+        _capi.call("hps_global_avgpool_backward", P(_capi.f32c(g_feats)), P(gf["blocks"][-1]["c2"]), B, h, w, last.shape[3], 1, s)
+        for k in range(len(names) - 1, -1, -1):
+            name, (c1, c2, down), ent, ge = names[k], prep["blocks"][k], fs["blocks"][k], gf["blocks"][k]
+            y_in = fs["blocks"][k - 1]["c2"] if k else fs["pool"]
+            g_in = gf["blocks"][k - 1]["c2"] if k else gf["pool"]
+            hin, win, cin = y_in.shape[1] - 2, y_in.shape[2] - 2, y_in.shape[3]
+            ho, wo = ent["c2"].shape[1] - 2, ent["c2"].shape[2] - 2
+            sums_d = want[name + ".c2"][1] or want[name + ".c2"][2] or (down is not None and (want[name + ".down"][1] or want[name + ".down"][2]))
+            sums2 = gate(ge["c2"], ent["c2"], B, ho, wo, c2.cout, 1, 1, sums_d)                  # g2: the block's ReLU, both branches
+            params(name + ".c2", c2, ent["c1"], 1, c2.cin_p, c2.cin_p, ho, wo, ge["c2"], 1, sums2)
+            if down is not None:
+                params(name + ".down", down, y_in, 1, cin, cin, hin, win, ge["c2"], 1, sums2)
+            if not (below[k] or any(want[name + ".c1"])):
+                break                                                                            # nobody below wants anything
+            dgrad(name + ".c2", c2, ge["c2"], 1, None, ge["c1"], 1, c2.cin_p, c2.cin_p, ho, wo)
+            sums1 = gate(ge["c1"], ent["c1"], B, ho, wo, c1.cout, 1, 1, want[name + ".c1"][1] or want[name + ".c1"][2])
+            params(name + ".c1", c1, y_in, 1, cin, cin, hin, win, ge["c1"], 1, sums1)
+            if not below[k]:
+                break
+            # the identity / down-sample branch's gradient first, the main branch's data gradient adds it in its epilogue (fixed order)
+            if down is not None:
+                dgrad(name + ".down", down, ge["c2"], 1, None, ge["tmp"], 1, cin, cin, hin, win)
+                other = ge["tmp"]
+            else:
+                other = ge["c2"]
+            dgrad(name + ".c1", c1, ge["c1"], 1, other, g_in, 1, cin, cin, hin, win)
+        else:
+            stem = prep["stem"]
+            hs, wst = fs["stem"].shape[1], fs["stem"].shape[2]
+            _capi.call("hps_maxpool3x3s2_backward", P(fs["stem"]), P(gf["pool"]), P(gf["stem"]), B, hs, wst, stem.cout, 1, s)
+            sums0 = gate(gf["stem"], fs["stem"], B, hs, wst, stem.cout, 0, 0, want["stem"][1] or want["stem"][2])
+            if want["stem"][0] or want["stem"][1]:
+                _capi.call("hps_nchw_to_padded_nhwc_generic", P(x), P(gf["xin"]), B, C, C, H, W, W, 3, s)
+            params("stem", stem, gf["xin"], 3, C, C, H, W, gf["stem"], 0, sums0)
+            if needs[0]:
+                dx = torch.empty(B, H, W, C, device=dev, dtype=torch.float32)
+                dgrad("stem", stem, gf["stem"], 0, None, dx, 0, C, C, H, W)
+                grads["input"] = dx.permute(0, 3, 1, 2).contiguous()
+        out = []
+        for name, _, _ in layers:
+            out += list(grads.get(name, (None, None, None)))
+        return grads.get("input"), out
 
 
 def resnet18(in_channels, pretrained=False, progress=True, **kwargs):

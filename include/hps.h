@@ -682,6 +682,47 @@ int hps_maxpool3x3s2_pad(const float* x, float* y, int B, int H, int W, int C, i
 int hps_global_avgpool_pad(const float* x, float* y, int B, int H, int W, int C, int P, hps_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Backward of the encoder  (torch autograd through models/resnet.py:62-78, 202-217; csrc/conv_backward.hip)
+ * A layer is y = act(conv(x, w) scale + shift [+ residual]) with eval-mode BatchNorm folded into scale / shift.  With g the cotangent
+ * behind the ReLU gate: G = corr(x, g) (hps_conv_wgrad), dW = scale_c G[c], dscale_c = <w[c], G[c]>, dshift_c = sum of g_c
+ * (hps_relu_gate_pad), dx = conv^T(g, w scale) (hps_conv_dgrad).  No atomics: every result is bitwise repeatable.
+ * ---------------------------------------------------------------------------------------- */
+
+/* Weight-gradient GEMM on the fp32 matrix cores: G (Cout, KH, KW, Cin) =
+ *   sum over b, oy, ox of g[b, oy, ox, co] * x[b, oy stride + ky - pad, ox stride + kx - pad, ci]
+ * x: (B, H + 2 ipad, W + 2 ipad, Cx) frame with a zero halo, ipad >= pad, Cx >= Cin channels per pixel (the first Cin are used);
+ * g: (B, Ho + 2 gpad, Wo + 2 gpad, Cout) frame (its halo is not read).  The contraction over the B Ho Wo pixels is cut into slices
+ * of hps_conv_wgrad_slice_pixels(Ho, Wo) pixels -- a rule on the map alone: the map's pixel count clamped to [128, 512] --; the
+ * slices' fp32 partials go to ``workspace`` (hps_conv_wgrad_workspace bytes) and are added in slice order in float64, rounded once.
+ * Any Cin, Cout, filter size and stride (every layer of the net: 3x3 / 1, 3x3 / 2, 1x1 / 2, the 7x7 / 2 stem with Cin = 18). */
+int hps_conv_wgrad(const float* x, const float* g, float* G, float* workspace, int B, int H, int W, int ipad, int Cx, int Cin,
+                   int Cout, int KH, int KW, int stride, int pad, int gpad, hps_stream_t stream);
+int hps_conv_wgrad_slice_pixels(int Ho, int Wo);
+size_t hps_conv_wgrad_workspace(int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad);
+
+/* Data gradient, gather form: interior of the (B, H + 2 dpad, W + 2 dpad, Cdx) frame dx (channels 0 .. Cin-1) =
+ *   sum over ky, kx, co of g[b, (iy + pad - ky) / stride, (ix + pad - kx) / stride, co] * wt[ky][kx][co][ci]   (+ other, same frame)
+ * over the taps whose output pixel exists (in range and in phase with the stride); wt (KH, KW, Cout, Cin) is the layer's filter with
+ * the BatchNorm scale of channel co folded in; ``other`` (may be NULL) is the gradient of the block's other branch, added last.
+ * g as in hps_conv_wgrad; Cout % 8 == 0.  fp32 chains of 64 output channels, added in (tap, channel block) order. */
+int hps_conv_dgrad(const float* g, const float* wt, const float* other, float* dx, int B, int H, int W, int Cin, int Cout, int KH,
+                   int KW, int stride, int pad, int gpad, int dpad, int Cdx, hps_stream_t stream);
+
+/* ReLU gate in place: interior of g (B, H + 2 gpad, W + 2 gpad, C) <- g where y > 0 (strict, as torch), else 0; y (B, H + 2 ypad,
+ * W + 2 ypad, C) is the layer's output.  sums (C,), optional together with workspace (hps_relu_gate_workspace bytes, float64): the
+ * per-channel sums of the gated cotangent (d shift) -- float64 per 64 pixels, then float64 over the chunks in order, rounded once. */
+int hps_relu_gate_pad(float* g, const float* y, double* workspace, float* sums, int B, int H, int W, int C, int gpad, int ypad,
+                      hps_stream_t stream);
+size_t hps_relu_gate_workspace(int B, int H, int W, int C);
+
+/* nn.MaxPool2d(3, 2, 1) differentiated: x (B,H,W,C) plain NHWC, the pool's input; gpool the (B, Ho + 2 gpad, Wo + 2 gpad, C) frame of
+ * the output's cotangent; dx (B,H,W,C): each window's cotangent goes to its first maximum in row-major order (torch's rule). */
+int hps_maxpool3x3s2_backward(const float* x, const float* gpool, float* dx, int B, int H, int W, int C, int gpad, hps_stream_t stream);
+
+/* AdaptiveAvgPool2d((1,1)) differentiated: interior of the (B, H + 2P, W + 2P, C) frame <- gfeat (B,C) / (H W). */
+int hps_global_avgpool_backward(const float* gfeat, float* gframe, int B, int H, int W, int C, int P, hps_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Proxy-representation front end  
  * ---------------------------------------------------------------------------------------- */
 
