@@ -16,6 +16,8 @@ min(s1^2 - s2^2, s2^2 - s3^2, s3) >= 0.02 for all 23 joints are used (torch.svd'
 quarter of the candidates must pass, so the filter cannot hide a failure.
 The accuracy rule is smpl_grad_scenario.bound / check.  References are computed once per case and shared (callers must not modify
 them).
+``head`` also takes another kinematic tree and a HeadOps (the steps tests/head_forward_scenario.py evaluates in other summation
+orders, or deliberately wrong); the gradient tests pass neither.
 """
 import functools
 
@@ -39,11 +41,11 @@ def parents():
     return tuple([-1] + [int(p) for p in kt[1:]])
 
 
-def make_net(recipe):
-    """A fresh net of the recipe (CPU, eval mode)."""
+def make_net(recipe, tree=None, config=None):
+    """A fresh net of the recipe (CPU, eval mode); tree: immediate parents (default parents()), config: default get_cfg_defaults()."""
     assert recipe in ("default", "spread")
     torch.manual_seed(0)
-    net = PoseMFShapeGaussianNet(list(parents()), configs.get_cfg_defaults()).eval()
+    net = PoseMFShapeGaussianNet(list(parents() if tree is None else tree), configs.get_cfg_defaults() if config is None else config).eval()
     if recipe == "spread":
         with torch.no_grad():
             for m in net.fc_pose:
@@ -63,45 +65,85 @@ def param_names(sd):
     return [k for k in sd if k.startswith(HEAD_PREFIXES)]
 
 
-def head(sd, feats, pin_U=None, num_betas=10, delta_i_weight=None):
-    """models/poseMF_shapeGaussian_net.py:95-162 restated in the dtype of ``sd`` / ``feats``; pin_U (B,23,3,3): the factors whose
-    column signs the SVDs are pinned to.  Returns a dict: the OUTPUTS plus pose_U, pose_V."""
+class HeadOps:
+    """The steps of ``head`` that tests/head_forward_scenario.py evaluates in other (legitimate or deliberately wrong) ways.  The
+    defaults are the head as the reference states it; the backward tests never pass another."""
+
+    def linear(self, x, w, b, name, addend=None):
+        """Layer ``name`` ("fc1", "fc_shape", "fc_glob", "fc_cam", "fc_embed", "fc_pose.<j>.0", "fc_pose.<j>.2"); addend: init_glob /
+        init_cam."""
+        y = F.linear(x, w, b)
+        return y if addend is None else y + addend
+
+    def scale(self, log_std):
+        return torch.exp(log_std)
+
+    def ancestors(self, a):
+        """The order in which a joint's ancestors enter its input (nearest first, the root excluded)."""
+        return a
+
+    def child_input(self, embed, up, sp, mode):
+        """(B, .) blocks: the embedding and the ancestors' U_proper (9 each), S_proper (3 each), mode (9 each)."""
+        return torch.cat([embed, up, sp, mode], dim=1)
+
+    def svd(self, Fj):
+        """(U, S, V) of the (B, 3, 3) matrices, singular values descending, any column signs."""
+        return torch.svd(Fj)
+
+    def pin_sign(self, dots, joint):
+        """Column signs from dots = <U[:, k], U_pin[:, k]> (B, 3)."""
+        assert float(dots.abs().min()) >= 0.99, ("singular vectors of joint %d do not match the pinned run" % joint, float(dots.abs().min()))
+        return torch.sign(dots)
+
+    def proper(self, U, S, V, dU, dV):
+        """(U_proper, S_proper, mode) from the raw factors and the constants det U, det V = +-1 (B,)."""
+        one = torch.ones_like(dU)
+        Up = U * torch.stack([one, one, dU], dim=1)[:, None, :]
+        Vp = V * torch.stack([one, one, dV], dim=1)[:, None, :]
+        Sp = S * torch.stack([one, one, dU * dV], dim=1)
+        return Up, Sp, torch.matmul(Up, Vp.transpose(-1, -2))
+
+
+def head(sd, feats, pin_U=None, num_betas=10, delta_i_weight=None, tree=None, ops=None):
+    """models/poseMF_shapeGaussian_net.py:95-162 restated in the dtype of ``sd`` / ``feats``; pin_U (B,NJ,3,3): the factors whose
+    column signs the SVDs are pinned to; tree: immediate parents (default parents(), 23 body joints); ops: a HeadOps.  Returns a
+    dict: the OUTPUTS plus pose_U, pose_V and the intermediate x, sgc = [shape_params | glob | cam], embed, u_proper, s_proper."""
     if delta_i_weight is None:
         cfg = configs.get_cfg_defaults()
         delta_i_weight = float(cfg.MODEL.DELTA_I_WEIGHT) if cfg.MODEL.DELTA_I else 0.0
-    anc = immediate_parents_to_all_parents(list(parents()))
+    ops = HeadOps() if ops is None else ops
+    anc = immediate_parents_to_all_parents(list(parents() if tree is None else tree))
     B, nj = feats.shape[0], len(anc)
-    x = F.elu(F.linear(feats, sd["fc1.weight"], sd["fc1.bias"]))
-    shape_params = F.linear(x, sd["fc_shape.weight"], sd["fc_shape.bias"])
-    loc, scale = shape_params[:, :num_betas], torch.exp(shape_params[:, num_betas:])
-    glob = F.linear(x, sd["fc_glob.weight"], sd["fc_glob.bias"]) + sd["init_glob"]
-    cam = F.linear(x, sd["fc_cam.weight"], sd["fc_cam.bias"]) + sd["init_cam"]
-    embed = F.elu(F.linear(torch.cat([feats, shape_params, glob, cam], dim=1), sd["fc_embed.weight"], sd["fc_embed.bias"]))
+    x = F.elu(ops.linear(feats, sd["fc1.weight"], sd["fc1.bias"], "fc1"))
+    shape_params = ops.linear(x, sd["fc_shape.weight"], sd["fc_shape.bias"], "fc_shape")
+    loc, scale = shape_params[:, :num_betas], ops.scale(shape_params[:, num_betas:])
+    glob = ops.linear(x, sd["fc_glob.weight"], sd["fc_glob.bias"], "fc_glob", sd["init_glob"])
+    cam = ops.linear(x, sd["fc_cam.weight"], sd["fc_cam.bias"], "fc_cam", sd["init_cam"])
+    sgc = torch.cat([shape_params, glob, cam], dim=1)
+    embed = F.elu(ops.linear(torch.cat([feats, sgc], dim=1), sd["fc_embed.weight"], sd["fc_embed.bias"], "fc_embed"))
     eye = torch.eye(3, dtype=feats.dtype)
     Fs, Us, Ss, Vs, Ups, Sps, modes = [], [], [], [], [], [], []
     for j in range(nj):
-        a = anc[j]
+        a = ops.ancestors(anc[j])
         inp = embed
         if a:
-            inp = torch.cat([embed] + [torch.stack([t[i] for i in a], dim=1).reshape(B, -1) for t in (Ups, Sps, modes)], dim=1)
-        h = F.elu(F.linear(inp, sd["fc_pose.%d.0.weight" % j], sd["fc_pose.%d.0.bias" % j]))
-        Fj = F.linear(h, sd["fc_pose.%d.2.weight" % j], sd["fc_pose.%d.2.bias" % j]).view(-1, 3, 3) + delta_i_weight * eye
-        U, S, V = torch.svd(Fj)
+            inp = ops.child_input(embed, *[torch.stack([t[i] for i in a], dim=1).reshape(B, -1) for t in (Ups, Sps, modes)])
+        h = F.elu(ops.linear(inp, sd["fc_pose.%d.0.weight" % j], sd["fc_pose.%d.0.bias" % j], "fc_pose.%d.0" % j))
+        Fj = ops.linear(h, sd["fc_pose.%d.2.weight" % j], sd["fc_pose.%d.2.bias" % j], "fc_pose.%d.2" % j).view(-1, 3, 3) + delta_i_weight * eye
+        U, S, V = ops.svd(Fj)
         if pin_U is not None:
             dots = (U.detach() * pin_U[:, j].to(U.dtype)).sum(dim=1)                  # <U[:, k], U_pin[:, k]> per column
-            assert float(dots.abs().min()) >= 0.99, ("singular vectors of joint %d do not match the pinned run" % j, float(dots.abs().min()))
-            sign = torch.sign(dots)[:, None, :]
+            sign = ops.pin_sign(dots, j)[:, None, :]
             U, V = U * sign, V * sign
         one = torch.ones(B, dtype=feats.dtype)
         dU = torch.where(torch.det(U.detach()) < 0, -one, one)
         dV = torch.where(torch.det(V.detach()) < 0, -one, one)
-        Up = U * torch.stack([one, one, dU], dim=1)[:, None, :]
-        Vp = V * torch.stack([one, one, dV], dim=1)[:, None, :]
-        Sp = S * torch.stack([one, one, dU * dV], dim=1)
+        Up, Sp, mode = ops.proper(U, S, V, dU, dV)
         Fs.append(Fj); Us.append(U); Ss.append(S); Vs.append(V); Ups.append(Up); Sps.append(Sp)
-        modes.append(torch.matmul(Up, Vp.transpose(-1, -2)))
+        modes.append(mode)
     st = lambda ts: torch.stack(ts, dim=1)
-    return dict(pose_F=st(Fs), pose_U=st(Us), pose_S=st(Ss), pose_V=st(Vs), mode=st(modes), loc=loc, scale=scale, glob=glob, cam=cam)
+    return dict(pose_F=st(Fs), pose_U=st(Us), pose_S=st(Ss), pose_V=st(Vs), mode=st(modes), loc=loc, scale=scale, glob=glob, cam=cam,
+                x=x, sgc=sgc, embed=embed, u_proper=st(Ups), s_proper=st(Sps))
 
 
 def min_gap(pose_S):
@@ -117,20 +159,26 @@ def improper_share(out):
     return float((d < 0).double().mean())
 
 
-@functools.lru_cache(maxsize=None)
-def features(recipe, B, seed=FEATURE_SEED):
-    """(fp32 features (B,512), kept, candidates): the first B candidate rows that pass the gap filter."""
+def select_features(sd, B, seed=FEATURE_SEED, **head_args):
+    """The feature rule for the fp32 state ``sd`` (``head_args``: tree, num_betas of ``head``): (fp32 features (B, fc1's width), kept,
+    candidates), the first B of 4 B + 8 candidate rows whose float64 forward passes the gap filter."""
     n = 4 * B + 8
-    cand = torch.rand(n, 512, generator=torch.Generator().manual_seed(seed))
-    sd64 = {k: v.double() for k, v in state(recipe).items()}
+    cand = torch.rand(n, sd["fc1.weight"].shape[1], generator=torch.Generator().manual_seed(seed))
+    sd64 = {k: v.double() for k, v in sd.items()}
     with torch.no_grad():
-        gaps = min_gap(head(sd64, cand.double())["pose_S"])
+        gaps = min_gap(head(sd64, cand.double(), **head_args)["pose_S"])
     keep = gaps >= MIN_GAP
     kept = int(keep.sum())
     assert 4 * kept >= n, "only %d of %d candidate rows pass the gap filter" % (kept, n)
     rows = cand[keep][:B].contiguous()
     assert rows.shape[0] == B and float(gaps[keep][:B].min()) >= MIN_GAP
     return rows, kept, n
+
+
+@functools.lru_cache(maxsize=None)
+def features(recipe, B, seed=FEATURE_SEED):
+    """(fp32 features (B,512), kept, candidates): the first B candidate rows that pass the gap filter."""
+    return select_features(state(recipe), B, seed)
 
 
 @functools.lru_cache(maxsize=None)
