@@ -104,10 +104,18 @@ _PROTOTYPES = {
     "hps_relu_gate_workspace": [_I] * 4,
     "hps_maxpool3x3s2_backward": [_P] * 3 + [_I] * 5 + [_P],
     "hps_global_avgpool_backward": [_P] * 2 + [_I] * 5 + [_P],
+    "hps_bn_batch_stats": [_P] * 4 + [_I] * 5 + [_P],
+    "hps_bn_batch_stats_workspace": [_I] * 4,
+    "hps_bn_train_fold": [_P] * 5 + [_c.c_double, _c.c_double, _c.c_longlong] + [_P] * 5 + [_I, _P],
+    "hps_bn_apply_act_pad": [_P] * 5 + [_I] * 7 + [_P],
+    "hps_bn_train_backward_sums": [_P] * 7 + [_I] * 7 + [_P],
+    "hps_bn_train_backward_sums_workspace": [_I] * 4,
+    "hps_bn_train_backward_dz": [_P] * 7 + [_I] * 7 + [_P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
-             "hps_conv_wgrad_workspace": _c.c_size_t, "hps_relu_gate_workspace": _c.c_size_t}
+             "hps_conv_wgrad_workspace": _c.c_size_t, "hps_relu_gate_workspace": _c.c_size_t,
+             "hps_bn_batch_stats_workspace": _c.c_size_t, "hps_bn_train_backward_sums_workspace": _c.c_size_t}
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 

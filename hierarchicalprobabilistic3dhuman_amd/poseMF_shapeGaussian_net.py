@@ -29,8 +29,10 @@ again in float64), hps_head_pose_levels_backward and hps_head_trunk_backward (cs
 the saved pose_U's signs, so the host-SVD mode is differentiable
 too.  The one difference from the reference: ``pose_U`` and ``pose_V`` are marked non-differentiable (the loss detaches them and the
 sampler draws without grad).  With ``input`` given the encoder is part of the graph too (resnet.py: its own autograd function, device
-backward kernels): the loss reaches every convolution and BatchNorm affine parameter and the input itself -- fine-tuning with frozen
-BatchNorm statistics (eval mode; ``.train()`` stays refused), not the reference's ``model.train()`` step.
+backward kernels): the loss reaches every convolution and BatchNorm affine parameter and the input itself.  By default that is fine-tuning with
+frozen BatchNorm statistics (eval mode; ``.train()`` is refused); ``set_batchnorm_training(True)`` followed by ``.train()`` is the
+reference's ``model.train()`` step: batch statistics in the forward, running buffers updated on the device, the backward through the
+statistics (csrc/bn_train.hip).
 From the first differentiable forward on, the module compares its head parameters' ``_version`` counters with the ones recorded by
 ``prepare()`` on every forward (no_grad ones included) and rebuilds the kernel-side copies when an optimiser step changed them;
 modules that never take the differentiable route do not look and behave as before.
@@ -149,6 +151,12 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         batch size; between the modes they differ in the last bits (other summation orders)."""
         self.latency_mode = bool(on)
         self.image_encoder.set_latency_mode(on)
+
+    def set_batchnorm_training(self, on=True):
+        """Opt in to the reference's ``model.train()`` step (train/train_poseMF_shapeGaussian_net.py:114): the encoder's BatchNorm layers
+        whose ``.training`` is set run on batch statistics and update their running buffers (ResNet.set_batchnorm_training).  Off, the
+        default, ``.train()`` stays refused."""
+        self.image_encoder.set_batchnorm_training(on)
 
     def _flavor(self):
         """Rounding flavour of the in-kernel SVD: ``svd_flavor`` if set (0 reference BLAS rounding, 1 fused), else the one that

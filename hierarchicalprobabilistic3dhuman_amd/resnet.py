@@ -3,17 +3,25 @@ models/resnet.py, executed as implicit-GEMM convolutions on the gfx950 fp32 matr
 
 The ``nn.Conv2d`` / ``nn.BatchNorm2d`` children only hold parameters (so that
 ``load_state_dict(checkpoint['best_model_state_dict'])`` and default initialisation behave exactly as in
-the reference); their own forward is never used.  BatchNorm always uses running statistics
+the reference); their own forward is never used.  By default BatchNorm uses running statistics
 (the reference runs the encoder under ``model.eval()``, predict/...:55) and is fused, together with the
-residual add and ReLU, into the convolution epilogue; ``.train()`` is refused.
+residual add and ReLU, into the convolution epilogue; ``.train()`` is refused unless ``set_batchnorm_training(True)`` opted in.
 
 Fine-tuning with frozen statistics.  With grad mode on and the input or an encoder parameter requiring grad, ``ResNet.forward`` runs
 inside a torch.autograd.Function: its forward issues exactly the launches of a no_grad call (same bits, in every kernel mode) and
 saves only the input and the parameters.  The backward (csrc/conv_backward.hip) evaluates the encoder once more into a frame set of
 its own -- the activation frames belong to the module and the next forward overwrites them, and the fused stem never writes the
 full-resolution map the max pool's backward needs -- with the forward's kernel family per layer and only the bit-identical fusions
-switched off, so the ReLU masks and pool winners are those of the function the caller evaluated.  This is NOT the reference's
-``model.train()`` step: batch statistics are a different forward and stay out of scope.  From the first differentiable forward on
+switched off, so the ReLU masks and pool winners are those of the function the caller evaluated.  This alone is NOT the reference's
+``model.train()`` step.
+
+Training-mode BatchNorm (``ResNet.set_batchnorm_training``, opt-in; csrc/bn_train.hip).  A BatchNorm whose own ``.training`` is set
+runs as ``nn.BatchNorm2d`` does in training mode: its convolution writes the raw map, the batch mean and biased variance are reduced
+in float64 in a fixed order, one fold launch turns them into the epilogue's scale / shift and updates running_mean / running_var /
+num_batches_tracked on the device, and the epilogue runs as a pass of its own.  The autograd function saves each such layer's mean
+and inverse standard deviation (two float64 vectors); the backward's recompute applies them and the backward goes through the
+statistics.  Bitwise repeatable; a training layer's output depends on the whole batch, so the independence of an image's result from
+the batch size holds for eval layers only.  From the first differentiable forward on
 the module compares its parameters' ``_version`` counters with those recorded by ``prepare()`` and refolds the filters after an
 optimiser step, as PoseMFShapeGaussianNet does for the head.
 """
@@ -38,10 +46,9 @@ class _ConvBN:
         flat = torch.zeros(k_pad, cout, device=w.device, dtype=torch.float32)
         flat[:k_real] = wk.reshape(k_real, cout)
         self.wk = flat.contiguous()
-        inv_std = torch.rsqrt(bn.running_var.detach().double() + bn.eps)
-        scale = bn.weight.detach().double() * inv_std
-        self.scale = scale.float().contiguous()
-        self.shift = (bn.bias.detach().double() - bn.running_mean.detach().double() * scale).float().contiguous()
+        self.scale, self.shift = self.fold(bn)
+        # identity pair: a training-mode BatchNorm's convolution writes the exact accumulator (every epilogue is a scale + shift + res)
+        self.ident = (torch.ones(cout, device=w.device, dtype=torch.float32), torch.zeros(cout, device=w.device, dtype=torch.float32))
         self.cin_p, self.cout, self.kh, self.kw = cin_p, cout, kh, kw
         self.stride, self.pad = conv.stride[0], conv.padding[0]
         # n-major filter (Cout, KH*KW*Cin) for the v2 kernel (Cin % 32 == 0: every conv after the stem)
@@ -84,6 +91,19 @@ class _ConvBN:
         self.variant = 0          # tile choice of the v2 / v3 kernels (0 = automatic)
         self.ksplit = 0           # split-K slices of the v3 kernel (0 = automatic, 1 = off)
         self.zeros = torch.zeros(64, device=w.device, dtype=torch.float32)
+
+    @staticmethod
+    def fold(bn):
+        """Eval-mode BatchNorm as fp32 (scale, shift): float64 arithmetic on the running statistics, rounded once."""
+        inv_std = torch.rsqrt(bn.running_var.detach().double() + bn.eps)
+        scale = bn.weight.detach().double() * inv_std
+        return scale.float().contiguous(), (bn.bias.detach().double() - bn.running_mean.detach().double() * scale).float().contiguous()
+
+    def refold(self, bn):
+        """The fold again IN PLACE (the launch lists keep pointing at these tensors): after a training forward moved the statistics."""
+        scale, shift = self.fold(bn)
+        self.scale.copy_(scale)
+        self.shift.copy_(shift)
 
     def _auto_ksplit(self, pixels_per_image):
         """Split K (4 slices) for the late layers whose 128x128 output tiles cannot fill 256 CUs at the benchmark batch
@@ -134,18 +154,20 @@ class _ConvBN:
             return 0
         return int(_capi.load(dev=_capi._use_dev).hps_conv3x3_winograd_workspace(B, H, W, self.cin_p, self.cout))
 
-    def padded(self, xp, ipad, out, opad, residual=None, relu=True, ws=None):
+    def padded(self, xp, ipad, out, opad, residual=None, relu=True, ws=None, ident=False):
         """Halo-padded generation (csrc/conv_pad.hip): xp (B, H+2*ipad, W+2*ipad, Cin) with a zero halo; writes the interior
-        of ``out`` (B, Ho+2*opad, Wo+2*opad, Cout) -- the caller owns the halo (zeroed once); ``residual`` has out's frame."""
+        of ``out`` (B, Ho+2*opad, Wo+2*opad, Cout) -- the caller owns the halo (zeroed once); ``residual`` has out's frame.
+        ``ident``: identity scale / shift instead of the folded BatchNorm (the raw map of a training-mode layer)."""
         B, Hp, Wp, C = xp.shape
         H, W = Hp - 2 * ipad, Wp - 2 * ipad
+        scale, shift = self.ident if ident else (self.scale, self.shift)
         if self.winograd_ok(H, W, ipad):
             assert C == self.cin_p and tuple(out.shape) == (B, H + 2 * opad, W + 2 * opad, self.cout)
             P = _capi.ptr
             need = self.wino_workspace_bytes(B, H, W, ipad)
             if need and (ws is None or ws.numel() * 4 < need):
                 ws = torch.empty(need // 4, device=xp.device, dtype=torch.float32)
-            _capi.call("hps_conv3x3_winograd", P(xp), P(self.wino_u), P(self.scale), P(self.shift),
+            _capi.call("hps_conv3x3_winograd", P(xp), P(self.wino_u), P(scale), P(shift),
                        P(residual) if residual is not None else None, P(out), B, H, W, ipad, C, self.cout, opad, 1 if relu else 0,
                        P(ws) if need else None, _capi.stream())
             return out
@@ -158,7 +180,7 @@ class _ConvBN:
         if ksplit > 1 and ws is None:
             ws = torch.empty(ksplit, B * Ho * Wo, self.cout, device=xp.device, dtype=torch.float32)
         P = _capi.ptr
-        _capi.call("hps_conv2d_bn_act_pad", P(xp), P(self.wrow if row_mode else self.wn), P(self.scale), P(self.shift),
+        _capi.call("hps_conv2d_bn_act_pad", P(xp), P(self.wrow if row_mode else self.wn), P(scale), P(shift),
                    P(residual) if residual is not None else None, P(out), B, H, W, ipad, C, self.cout, self.kh, self.kw,
                    self.stride, self.pad, opad, 1 if relu else 0, 1 if row_mode else 0, self._tile_variant(ksplit),
                    ksplit, P(ws) if ksplit > 1 else None, _capi.stream())
@@ -176,8 +198,9 @@ class _ConvBN:
         """Tile choice of the fused launch: the main convolution's; 0 (automatic) resolves to 128 x 128 or 64 x 64 tiles for Cout >= 128."""
         return self._tile_variant(ksplit)
 
-    def padded_with_down(self, xp, ipad, out, opad, down, out_down, ws=None):
-        """padded(xp -> out, relu) and down.padded(xp -> out_down, no relu) in ONE launch (see folds_down); identical bits."""
+    def padded_with_down(self, xp, ipad, out, opad, down, out_down, ws=None, relu=True, ident=(False, False)):
+        """padded(xp -> out, relu) and down.padded(xp -> out_down, no relu) in ONE launch (see folds_down); identical bits.
+        ``ident``: identity scale / shift for (this convolution, the down-sample) -- see padded."""
         B, Hp, Wp, C = xp.shape
         H, W = Hp - 2 * ipad, Wp - 2 * ipad
         assert self.folds_down(down, H, W, ipad) and C == self.cin_p
@@ -187,8 +210,10 @@ class _ConvBN:
         if ksplit > 1 and ws is None:
             ws = torch.empty(ksplit, B * Ho * Wo, self.cout, device=xp.device, dtype=torch.float32)
         P = _capi.ptr
-        _capi.call("hps_conv2d_bn_act_pad_down", P(xp), P(self.wn), P(self.scale), P(self.shift), P(out), P(down.wn), P(down.scale),
-                   P(down.shift), P(out_down), B, H, W, ipad, C, self.cout, self.kh, self.kw, self.stride, self.pad, opad, 1,
+        sc, sh = self.ident if ident[0] else (self.scale, self.shift)
+        scd, shd = down.ident if ident[1] else (down.scale, down.shift)
+        _capi.call("hps_conv2d_bn_act_pad_down", P(xp), P(self.wn), P(sc), P(sh), P(out), P(down.wn), P(scd),
+                   P(shd), P(out_down), B, H, W, ipad, C, self.cout, self.kh, self.kw, self.stride, self.pad, opad, 1 if relu else 0,
                    self._down_variant(ksplit), ksplit, P(ws) if ksplit > 1 else None, _capi.stream())
         return out, out_down
 
@@ -291,11 +316,19 @@ class _EncoderFunction(torch.autograd.Function):
     ``ctx.needs_input_grad`` does not ask for.  Inputs after ``x``: the parameters in the order of ``ResNet._enc_params()``."""
 
     @staticmethod
-    def forward(ctx, net, prep, gate, x, *params):
+    def forward(ctx, net, prep, gate, flags, x, *params):
         xc = _capi.f32c(x.detach())
-        feats = net._forward_padded(prep, xc, gate=gate)
+        ctx.flags, saved = flags, []
+        if flags is not None:                                            # some BatchNorm runs on batch statistics
+            B, C, H, W = xc.shape
+            feats, stats = net._forward_train(prep, xc, net._train_frames(prep, B, C, H, W, xc.device, flags), flags, update=True)
+            ctx.stat_names = list(stats)
+            saved = [t for name in ctx.stat_names for t in (stats[name][0], stats[name][2])]      # mean, invstd: (C,) float64 each
+        else:
+            feats = net._forward_padded(prep, xc, gate=gate)
         ctx.net, ctx.prep, ctx.x_dtype = net, prep, x.dtype             # prep owns the folded filters the recompute reads
-        ctx.save_for_backward(xc, *params)
+        ctx.n_params = len(params)
+        ctx.save_for_backward(xc, *params, *saved)
         return feats
 
     @staticmethod
@@ -303,10 +336,14 @@ class _EncoderFunction(torch.autograd.Function):
     def backward(ctx, g_feats):
         x = ctx.saved_tensors[0]
         need = ctx.needs_input_grad
-        g_x, g_params = ctx.net._backward(ctx.prep, x, g_feats, list(need[3:]))
+        saved = None
+        if ctx.flags is not None:
+            st = ctx.saved_tensors[1 + ctx.n_params:]
+            saved = {name: (st[2 * i], st[2 * i + 1]) for i, name in enumerate(ctx.stat_names)}
+        g_x, g_params = ctx.net._backward(ctx.prep, x, g_feats, list(need[4:]), flags=ctx.flags, saved=saved)
         if g_x is not None and g_x.dtype != ctx.x_dtype:
             g_x = g_x.to(ctx.x_dtype)
-        return (None, None, None, g_x) + tuple(g_params)
+        return (None, None, None, None, g_x) + tuple(g_params)
 
 
 class BasicBlock(nn.Module):
@@ -327,7 +364,7 @@ class BasicBlock(nn.Module):
 class ResNet(DeviceStateModule):
     """models/resnet.py:125-217 for BasicBlock stacks."""
 
-    SWITCHES = ("_winograd", "_latency", "composite", "fused_pool", "fold_downsample", "stem_reads_nchw")
+    SWITCHES = ("_winograd", "_latency", "composite", "fused_pool", "fold_downsample", "stem_reads_nchw", "_bn_training")
 
     def __init__(self, layers, in_channels):
         super().__init__()
@@ -352,6 +389,7 @@ class ResNet(DeviceStateModule):
         # prepare() re-applies them to the rebuilt _ConvBN objects
         self._winograd = True
         self._latency = False
+        self._bn_training = False      # set_batchnorm_training: BatchNorm layers whose own .training is set run on batch statistics
         self.composite = True     # padded layout: issue the launch list through hps_encoder_run (one call) instead of one by one
         # Winograd stem: form the max pool in the stem kernel's epilogue (hps_stem_winograd_pooled: the full-resolution stem output is never
         # written; identical values).  False: hps_stem_winograd + hps_maxpool3x3s2_pad (the cross-check of the tests)
@@ -398,6 +436,22 @@ class ResNet(DeviceStateModule):
         1e-4 feature tolerance against the reference -- tests/test_gpu_net.py)."""
         self._latency = bool(on)              # switching it off restores whatever set_winograd selected before
         self._prepared or self.prepare()
+
+    def set_batchnorm_training(self, on=True):
+        """Opt-in training-mode BatchNorm (models/resnet.py under ``model.train()``, train/train_poseMF_shapeGaussian_net.py:114).
+        Off (the default): nothing changes, a forward with ``self.training`` set is refused -- an inference caller who forgot
+        ``.eval()`` must not silently normalise a batch-1 predict loop by its own statistics.  On: every convolution's BatchNorm
+        decides by ITS OWN ``bn.training`` flag.  A training layer's convolution writes its raw map (identity scale / shift), then
+        csrc/bn_train.hip: batch statistics (float64, deterministic), one fold launch that also updates running_mean / running_var
+        (unbiased variance, the layer's momentum) and num_batches_tracked on the device, and the epilogue as a pass of its own; an
+        eval layer (``enc.layer1.eval()`` after ``enc.train()`` freezes layer1) runs the folded path and the existing backward.  With
+        no layer training the call issues exactly the eval launches.  The buffers are updated once per forward (also under no_grad),
+        never by the backward's recompute (it applies the statistics the forward saved) and never by training_activations.  Results
+        are bitwise repeatable; a training layer's output of course depends on the whole batch, so the independence of an image's
+        result from the batch size holds for eval layers only.  Like set_winograd a property of the model: it survives .to(),
+        load_state_dict and deepcopy.  FilledStemFrames inputs and ``_gate`` belong to the inference pipeline and are refused while
+        a layer is training."""
+        self._bn_training = bool(on)
 
     def prepare(self):
         cin = self.conv1.in_channels
@@ -618,24 +672,191 @@ class ResNet(DeviceStateModule):
 
     def forward(self, x, _gate=None):
         """models/resnet.py:202-217: (B,C,H,W) NCHW fp32 -> (B,512)."""
-        if self.training:
-            raise RuntimeError("the MI355X encoder path runs eval-mode BatchNorm only (running statistics, also when fine-tuning); call .eval()")
+        flags = self._train_flags()
         filled = isinstance(x, FilledStemFrames)
+        if flags is not None:
+            if filled or _gate is not None:
+                raise RuntimeError("FilledStemFrames inputs and _gate are the inference pipeline's paths; not with a BatchNorm in training mode")
+            self._check_training(flags, x.shape)                  # before any launch, before any buffer is touched
+            _capi.require_device(x, "encoder input")
         differentiable = torch.is_grad_enabled() and not filled and (
             (isinstance(x, torch.Tensor) and x.requires_grad) or any(w.requires_grad for w in self._enc_params()))
         if differentiable:
             self._track_versions = True
-        if self._track_versions and self._prepared is not None and self._prepared.get("versions") != self._enc_versions():
-            self.invalidate()                                     # an optimiser step (or any in-place edit) since prepare()
-        prep = self._prepared or self.prepare()
+        prep = self._current_prep()
         if filled:
             return self._forward_padded(prep, x, gate=_gate)
         _capi.require_device(x, "encoder input")
         if differentiable:
-            return _EncoderFunction.apply(self, prep, _gate, x, *self._enc_params())
+            return _EncoderFunction.apply(self, prep, _gate, flags, x, *self._enc_params())
+        if flags is not None:
+            xc = _capi.f32c(x)
+            B, C, H, W = xc.shape
+            return self._forward_train(prep, xc, self._train_frames(prep, B, C, H, W, xc.device, flags), flags, update=True)[0]
         # every (C, H, W) runs on the product kernels: shapes the stem's fast paths do not take get a channel-padded, even-width input
         # frame (hps_nchw_to_padded_nhwc_generic) in front of the row-mode / direct stem
         return self._forward_padded(prep, _capi.f32c(x), gate=_gate)
+
+    # ---- training-mode BatchNorm (csrc/bn_train.hip) ----
+    def _train_flags(self):
+        """None when every BatchNorm runs on running statistics, else {layer name: its BatchNorm is training} over _enc_layers().
+        Switch off: a module in training mode is refused."""
+        if not self._bn_training:
+            if self.training:
+                raise RuntimeError("the MI355X encoder path runs eval-mode BatchNorm only (running statistics, also when fine-tuning); "
+                                   "call .eval(), or opt in to batch statistics with set_batchnorm_training(True)")
+            return None
+        flags = {name: bool(bn.training) for name, _, bn in self._enc_layers()}
+        return flags if any(flags.values()) else None
+
+    def _layer_maps(self, H, W):
+        """{layer name: (Ho, Wo)} of every convolution's output for an (H, W) input."""
+        hw = lambda h, w, k, s, p: ((h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1)
+        out = {"stem": hw(H, W, 7, 2, 3)}
+        h, w = hw(*out["stem"], 3, 2, 1)
+        for name, conv, _ in self._enc_layers()[1:]:
+            if name.endswith(".c1"):
+                h, w = hw(h, w, conv.kernel_size[0], conv.stride[0], conv.padding[0])
+            out[name] = (h, w)
+        return out
+
+    def _check_training(self, flags, shape):
+        """torch's own refusals for the training layers, raised before any launch and before any buffer is touched."""
+        B, _, H, W = shape
+        maps = self._layer_maps(H, W)
+        for name, _, bn in self._enc_layers():
+            if not flags[name]:
+                continue
+            if bn.momentum is None:
+                raise NotImplementedError("%s: momentum=None (cumulative moving average) is not implemented on the device" % name)
+            if not bn.track_running_stats or bn.running_mean is None:
+                raise NotImplementedError("%s: track_running_stats=False is not implemented on the device" % name)
+            if not bn.affine:
+                raise NotImplementedError("%s: affine=False is not implemented on the device" % name)
+            h, w = maps[name]
+            if B * h * w == 1:
+                raise ValueError("Expected more than 1 value per channel when training, got input size %s (%s)"
+                                 % (torch.Size((B, bn.num_features, h, w)), name))
+
+    def _current_prep(self):
+        """The kernel-side weights for the parameters and statistics as they are now: rebuilt after an optimiser step (version
+        counters, from the first differentiable forward on), eval-mode folds redone in place for the layers whose running statistics
+        a training forward has moved since (the fold kernel writes through data_ptr(): no version counter sees it)."""
+        if self._track_versions and self._prepared is not None and self._prepared.get("versions") != self._enc_versions():
+            self.invalidate()                                     # an optimiser step (or any in-place edit) since prepare()
+        prep = self._prepared or self.prepare()
+        stale = prep.get("stale_bn")
+        if stale:
+            convs = [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]
+            with torch.no_grad():
+                for (name, _, bn), cb in zip(self._enc_layers(), convs):
+                    if name in stale:
+                        cb.refold(bn)
+                        prep.get("bwd", {}).pop(name, None)       # the data gradient's scaled filter
+            stale.clear()
+        return prep
+
+    def _train_frames(self, prep, B, C, H, W, device, flags):
+        """The training forward's frame set for a batch shape on the current stream: as the backward's activation set (unfused stem
+        and pool: the statistics are needed between the convolution and the pool) plus one raw frame per training layer."""
+        key = (B, C, H, W, _capi.stream().value, tuple(flags.values()))
+        return self._derived("train_frames", key, lambda: self._add_raw_frames(
+            self._new_frame_set(prep, B, C, H, W, device, prep["stem"].stem_winograd_ok(C, H, W), False, False), flags), limit=4)
+
+    def _add_raw_frames(self, fs, flags):
+        raw = {"stem": torch.empty_like(fs["stem"]) if flags["stem"] else None}
+        for name, ent in zip(self._block_names(), fs["blocks"]):
+            for k in ("c1", "c2", "down"):
+                raw[name + "." + k] = torch.empty_like(ent[k]) if ent[k] is not None and flags[name + "." + k] else None
+        fs["raw"] = raw
+        return fs
+
+    def _forward_train(self, prep, x, fs, flags, saved=None, update=False):
+        """The forward with batch statistics in the layers ``flags`` names, launch by launch on the frame set ``fs`` (it has raw
+        frames: _add_raw_frames): (features, {name: (mean, biased var or None, invstd, n)}).  The convolution kernels and the rules
+        that pick them are those of the eval forward.  ``saved`` {name: (mean, invstd)}: apply these statistics instead of reducing
+        them (the backward's recompute).  ``update``: the fold launch also updates the layer's running buffers and counter."""
+        B, C, H, W = x.shape
+        s, P = _capi.stream(), _capi.ptr
+        D = lambda t: _capi.ptr(t, torch.float64)
+        lib = _capi.load(dev=_capi._use_dev)
+        dev, f64 = x.device, torch.float64
+        bns = {name: bn for name, _, bn in self._enc_layers()}
+        raw, stats = fs["raw"], {}
+
+        def normalise(name, cb, h, w, pad, out, residual, relu):
+            """raw frame of ``name`` -> statistics -> fold -> out = act(raw scale + shift [+ residual])"""
+            bn, c, z = bns[name], cb.cout, raw[name]
+            scale, shift = torch.empty(c, device=dev), torch.empty(c, device=dev)
+            gamma, beta = _capi.f32c(bn.weight.detach()), _capi.f32c(bn.bias.detach())
+            n = B * h * w
+            if saved is None:
+                mean, var, invstd = (torch.empty(c, device=dev, dtype=f64) for _ in range(3))
+                ws = torch.empty(max(1, int(lib.hps_bn_batch_stats_workspace(B, h, w, c)) // 8), device=dev, dtype=f64)
+                _capi.call("hps_bn_batch_stats", P(z), D(ws), D(mean), D(var), B, h, w, c, pad, s)
+                if update:
+                    _capi.call("hps_bn_train_fold", D(mean), D(var), D(invstd), P(gamma), P(beta), float(bn.eps), float(bn.momentum), n,
+                               P(scale), P(shift), P(bn.running_mean), P(bn.running_var),
+                               _capi.ptr(bn.num_batches_tracked, torch.int64), c, s)
+                else:
+                    _capi.call("hps_bn_train_fold", D(mean), D(var), D(invstd), P(gamma), P(beta), float(bn.eps), 0.0, n, P(scale), P(shift),
+                               None, None, None, c, s)
+            else:
+                (mean, invstd), var = saved[name], None
+                _capi.call("hps_bn_train_fold", D(mean), None, D(invstd), P(gamma), P(beta), float(bn.eps), 0.0, n, P(scale), P(shift),
+                           None, None, None, c, s)
+            _capi.call("hps_bn_apply_act_pad", P(z), P(scale), P(shift), P(residual) if residual is not None else None, P(out), B, h, w, c,
+                       pad, pad, 1 if relu else 0, s)
+            stats[name] = (mean, var, invstd, n)
+
+        stem = prep["stem"]
+        ts = flags["stem"]
+        y = raw["stem"] if ts else fs["stem"]
+        if fs["stem_wino"]:
+            _capi.call("hps_stem_phase_split", P(x), P(fs["in"]), B, C, H, W, s)
+            sc, sh = stem.ident if ts else (stem.scale, stem.shift)
+            _capi.call("hps_stem_winograd", P(fs["in"]), P(stem.stem_u), P(sc), P(sh), P(y), B, H, W, 0, 0 if ts else 1, s)
+        else:
+            if fs["generic_in"] is not None:
+                _, cf, _, wf = fs["generic_in"]
+                _capi.call("hps_nchw_to_padded_nhwc_generic", P(x), P(fs["in"]), B, C, cf, H, W, wf, 3, s)
+            else:
+                _capi.call("hps_nchw_to_padded_nhwc", P(x), P(fs["in"]), B, C, H, W, 3, s)
+            stem.padded(fs["in"], 3, y, 0, relu=not ts, ident=ts)
+        y = fs["stem"]
+        if ts:
+            normalise("stem", stem, y.shape[1], y.shape[2], 0, y, None, True)
+        _capi.call("hps_maxpool3x3s2_pad", P(y), P(fs["pool"]), B, y.shape[1], y.shape[2], y.shape[3], 1, s)
+        y = fs["pool"]
+        for name, (c1, c2, down), ent in zip(self._block_names(), prep["blocks"], fs["blocks"]):      # BasicBlock.forward :62-78
+            t1, t2, td = flags[name + ".c1"], flags[name + ".c2"], down is not None and flags[name + ".down"]
+            hin, win = y.shape[1] - 2, y.shape[2] - 2
+            h, w = c1.out_hw(hin, win)
+            o1 = raw[name + ".c1"] if t1 else ent["c1"]
+            od = raw[name + ".down"] if td else ent["down"]
+            if down is not None and self.fold_downsample and c1.folds_down(down, hin, win, 1):
+                c1.padded_with_down(y, 1, o1, 1, down, od, ws=ent["ws"], relu=not t1, ident=(t1, td))
+            else:
+                if down is not None:
+                    down.padded(y, 1, od, 1, relu=False, ident=td)
+                c1.padded(y, 1, o1, 1, relu=not t1, ws=ent["ws"], ident=t1)
+            if td:
+                normalise(name + ".down", down, h, w, 1, ent["down"], None, False)
+            if t1:
+                normalise(name + ".c1", c1, h, w, 1, ent["c1"], None, True)
+            identity = ent["down"] if down is not None else y
+            if t2:
+                c2.padded(ent["c1"], 1, raw[name + ".c2"], 1, relu=False, ws=ent["ws"], ident=True)
+                normalise(name + ".c2", c2, h, w, 1, ent["c2"], identity, True)
+            else:
+                c2.padded(ent["c1"], 1, ent["c2"], 1, residual=identity, relu=True, ws=ent["ws"])
+            y = ent["c2"]
+        h, w = fs["hw"]
+        feats = torch.empty(B, y.shape[3], device=dev, dtype=torch.float32)
+        _capi.call("hps_global_avgpool_pad", P(y), P(feats), B, h, w, y.shape[3], 1, s)
+        if update:
+            prep.setdefault("stale_bn", set()).update(stats)      # their eval-mode folds no longer match the running statistics
+        return feats, stats
 
     # ---- backward (csrc/conv_backward.hip) ----
     def _enc_layers(self):
@@ -662,12 +883,12 @@ class ResNet(DeviceStateModule):
         return ["layer%d.%d" % (li, bi) for li, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), 1)
                 for bi in range(len(layer))]
 
-    def _backward_frames(self, prep, B, C, H, W, device):
+    def _backward_frames(self, prep, B, C, H, W, device, flags=None):
         """The backward's own frames for a batch shape on the current stream: an activation set for the recompute (stem output
         written out, max pool as a launch of its own; phase split + frame-fed kernel where the forward took the Winograd stem -- the
         same values as the fused launches) and one cotangent frame per activation frame, halos zeroed once."""
         # the launch list points at ``prep``'s filters: a backward that outlives a kernel-mode switch keeps its own set
-        key = (B, C, H, W, _capi.stream().value, id(prep))
+        key = (B, C, H, W, _capi.stream().value, id(prep), tuple(flags.values()) if flags else None)
 
         def build():
             stem = prep["stem"]
@@ -679,6 +900,12 @@ class ResNet(DeviceStateModule):
                 g["blocks"].append({"c1": torch.zeros_like(ent["c1"]), "c2": torch.zeros_like(ent["c2"]),
                                     "tmp": torch.zeros_like(y) if down is not None else None})
                 y = ent["c2"]
+            if flags:        # raw maps of the training layers; their dz frames (out of place: the gated cotangent has other readers)
+                self._add_raw_frames(fs, flags)
+                g["dz_stem"] = torch.empty_like(fs["stem"]) if flags["stem"] else None
+                for name, ent, ge in zip(self._block_names(), fs["blocks"], g["blocks"]):
+                    ge["dz"] = torch.zeros_like(ent["c2"]) if flags[name + ".c1"] or flags[name + ".c2"] else None
+                    ge["dzd"] = torch.zeros_like(ent["c2"]) if ent["down"] is not None and flags[name + ".down"] else None
             return fs, g, prep
         return self._derived("backward_frames", key, build, limit=6)[:2]
 
@@ -693,21 +920,41 @@ class ResNet(DeviceStateModule):
         relu), 'pool', and per block 'layerL.j.c1' (after its ReLU), 'layerL.j.c2' (the block's output) and 'layerL.j.down'.  The
         ReLU masks (map > 0) and the pool winners of the device's function are read off these maps (the tests pin their float64
         restatement to them)."""
-        if self.training:
-            raise RuntimeError("the MI355X encoder path runs eval-mode BatchNorm only; call .eval()")
+        if self._train_flags() is not None:
+            raise RuntimeError("a BatchNorm is in training mode: use training_activations()")
         _capi.require_device(x, "encoder input")
         with torch.no_grad():
-            if self._track_versions and self._prepared is not None and self._prepared.get("versions") != self._enc_versions():
-                self.invalidate()
-            prep = self._prepared or self.prepare()
-            feats, fs, _ = self._recompute(prep, _capi.f32c(x))
-            nchw = lambda t, p: (t[:, p:t.shape[1] - p, p:t.shape[2] - p] if p else t).permute(0, 3, 1, 2).clone()
-            maps = {"stem": nchw(fs["stem"], 0), "pool": nchw(fs["pool"], 1)}
-            for name, ent in zip(self._block_names(), fs["blocks"]):
-                maps[name + ".c1"], maps[name + ".c2"] = nchw(ent["c1"], 1), nchw(ent["c2"], 1)
-                if ent["down"] is not None:
-                    maps[name + ".down"] = nchw(ent["down"], 1)
-        return feats, maps
+            feats, fs, _ = self._recompute(self._current_prep(), _capi.f32c(x))
+            return feats, self._maps_of(fs)
+
+    def _maps_of(self, fs):
+        nchw = lambda t, p: (t[:, p:t.shape[1] - p, p:t.shape[2] - p] if p else t).permute(0, 3, 1, 2).clone()
+        maps = {"stem": nchw(fs["stem"], 0), "pool": nchw(fs["pool"], 1)}
+        for name, ent in zip(self._block_names(), fs["blocks"]):
+            maps[name + ".c1"], maps[name + ".c2"] = nchw(ent["c1"], 1), nchw(ent["c2"], 1)
+            if ent["down"] is not None:
+                maps[name + ".down"] = nchw(ent["down"], 1)
+        return maps
+
+    def training_activations(self, x):
+        """(features, maps, stats) of the training-mode function the backward differentiates -- the very code path (the recompute's
+        frames and launches, statistics reduced instead of taken from a forward), WITHOUT any running-buffer update.  ``maps`` as
+        activations() names them; ``stats[name] = (mean float64 (C,), biased variance float64 (C,), n)`` for every layer whose
+        BatchNorm is training, ``name`` as in _enc_layers().  Needs set_batchnorm_training(True)."""
+        flags = self._train_flags()
+        _capi.require_device(x, "encoder input")
+        if flags is not None:
+            self._check_training(flags, x.shape)
+        with torch.no_grad():
+            prep = self._current_prep()
+            xc = _capi.f32c(x)
+            if flags is None:
+                feats, fs, _ = self._recompute(prep, xc)
+                return feats, self._maps_of(fs), {}
+            B, C, H, W = xc.shape
+            fs, _ = self._backward_frames(prep, B, C, H, W, xc.device, flags)
+            feats, stats = self._forward_train(prep, xc, fs, flags, update=False)
+            return feats, self._maps_of(fs), {name: (mean.clone(), var.clone(), n) for name, (mean, var, _, n) in stats.items()}
 
     @staticmethod
     def _prepare_backward(prep):
@@ -719,23 +966,37 @@ class ResNet(DeviceStateModule):
             q = prep["bwd"] = {}
         return q
 
-    def _dgrad_filter(self, prep, name, conv, cb):
+    def _dgrad_filter(self, prep, name, conv, cb, raw=False):
+        """``raw``: the unscaled filter (a training layer: hps_bn_train_backward_dz has the scale in dz)."""
         q = self._prepare_backward(prep)
-        if name not in q:
-            w = conv.weight.detach().double() * cb.scale.double()[:, None, None, None]
-            q[name] = w.permute(2, 3, 0, 1).float().contiguous()
-        return q[name]
+        key = name + ".raw" if raw else name
+        if key not in q:
+            w = conv.weight.detach().double()
+            if not raw:
+                w = w * cb.scale.double()[:, None, None, None]
+            q[key] = w.permute(2, 3, 0, 1).float().contiguous()
+        return q[key]
 
-    def _backward(self, prep, x, g_feats, needs):
+    def _backward(self, prep, x, g_feats, needs, flags=None, saved=None):
         """(input gradient or None, parameter gradients in _enc_params() order, None where ``needs`` does not ask) for the cotangent
-        ``g_feats`` (B, 512).  ``needs``: [input] + one flag per parameter.  Kernels whose result nobody wants are not launched: no
+        ``g_feats`` (B, 512).  ``flags`` / ``saved``: the layers that ran on batch statistics and the (mean, invstd) the forward saved --
+        the recompute applies them (no reduction, no running-buffer update) and writes the raw maps; such a layer's backward is
+        hps_bn_train_backward_sums (with the ReLU gate in the same sweep where the block allows it) and hps_bn_train_backward_dz, then
+        the weight gradient of dz IS dW and the data gradient takes the unscaled filter.  ``needs``: [input] + one flag per parameter.  Kernels whose result nobody wants are not launched: no
         weight gradient for a frozen convolution, no data gradient below the lowest layer that wants one, the stem's data
         gradient only for an input that requires grad."""
         P, s = _capi.ptr, _capi.stream()
         lib = _capi.load(dev=_capi._use_dev)
         B, C, H, W = x.shape
         dev = x.device
-        _, fs, gf = self._recompute(prep, x)
+        flags = flags or {}
+        if flags:
+            fs, gf = self._backward_frames(prep, B, C, H, W, dev, flags)
+            self._forward_train(prep, x, fs, flags, saved=saved, update=False)
+        else:
+            _, fs, gf = self._recompute(prep, x)
+        D = lambda t: _capi.ptr(t, torch.float64)
+        trains = lambda name: bool(flags.get(name))
         layers = self._enc_layers()
         want = {name: needs[1 + 3 * i:4 + 3 * i] for i, (name, _, _) in enumerate(layers)}
         mods = {name: (conv, bn) for name, conv, bn in layers}
@@ -755,6 +1016,36 @@ class ResNet(DeviceStateModule):
             ws = scratch(int(lib.hps_relu_gate_workspace(Bh, h, w, c)), torch.float64) if want_sums else None
             _capi.call("hps_relu_gate_pad", P(g), P(y), _capi.ptr(ws, torch.float64) if want_sums else None, P(sums), Bh, h, w, c, gpad, ypad, s)
             return sums
+
+        def train_sums(name, cb, g, gpad, y, ypad, h, w):
+            """(d beta, d gamma) float64 (2 C,) of a training layer from the cotangent frame ``g``; with ``y`` the ReLU gate is applied to
+            g in the same sweep."""
+            mean, invstd = saved[name]
+            ws = scratch(int(lib.hps_bn_train_backward_sums_workspace(B, h, w, cb.cout)), torch.float64)
+            sums = torch.empty(2 * cb.cout, device=dev, dtype=torch.float64)
+            _capi.call("hps_bn_train_backward_sums", P(g), P(fs["raw"][name]), P(y) if y is not None else None, D(mean), D(invstd), D(ws),
+                       D(sums), B, h, w, cb.cout, gpad, ypad, ypad, s)
+            return sums
+
+        def train_dz(name, cb, g, gpad, sums, dz, h, w):
+            mean, invstd = saved[name]
+            _capi.call("hps_bn_train_backward_dz", P(g), P(fs["raw"][name]), D(mean), D(invstd), P(_capi.f32c(mods[name][1].weight.detach())),
+                       D(sums), P(dz), B, h, w, cb.cout, gpad, gpad, gpad, s)
+            return dz
+
+        def train_params(name, cb, xf, ipad, cx, cin, hin, win, dz, gpad, sums):
+            """Gradients of a training layer: dW = corr(x, dz), d gamma and d beta are the sums themselves."""
+            conv, bn = mods[name]
+            w_w, w_g, w_b = want[name]
+            dW = None
+            if w_w:
+                G = torch.empty(cb.cout, cb.kh, cb.kw, cin, device=dev, dtype=torch.float32)
+                ws = scratch(int(lib.hps_conv_wgrad_workspace(B, hin, win, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad)), torch.float32)
+                _capi.call("hps_conv_wgrad", P(xf), P(dz), P(G), P(ws), B, hin, win, ipad, cx, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad,
+                           gpad, s)
+                dW = G.permute(0, 3, 1, 2).to(conv.weight.dtype).contiguous()
+            if w_w or w_g or w_b:
+                grads[name] = (dW, sums[cb.cout:].to(bn.weight.dtype) if w_g else None, sums[:cb.cout].to(bn.bias.dtype) if w_b else None)
 
         def params(name, cb, xf, ipad, cx, cin, hin, win, g, gpad, sums):
             """Gradients of one convolution's weight and BatchNorm affine from its gated cotangent frame ``g`` and input frame ``xf``."""
@@ -781,7 +1072,7 @@ class ResNet(DeviceStateModule):
 
         def dgrad(name, cb, g, gpad, other, dx, dpad, cdx, cin, hin, win):
             conv, _ = mods[name]
-            _capi.call("hps_conv_dgrad", P(g), P(self._dgrad_filter(prep, name, conv, cb)), P(other), P(dx), B, hin, win, cin, cb.cout,
+            _capi.call("hps_conv_dgrad", P(g), P(self._dgrad_filter(prep, name, conv, cb, trains(name))), P(other), P(dx), B, hin, win, cin, cb.cout,
                        cb.kh, cb.kw, cb.stride, cb.pad, gpad, dpad, cdx, s)
 
         # which blocks still have somebody below them asking for a gradient
@@ -799,36 +1090,72 @@ class ResNet(DeviceStateModule):
             g_in = gf["blocks"][k - 1]["c2"] if k else gf["pool"]
             hin, win, cin = y_in.shape[1] - 2, y_in.shape[2] - 2, y_in.shape[3]
             ho, wo = ent["c2"].shape[1] - 2, ent["c2"].shape[2] - 2
+            t1, t2, td = trains(name + ".c1"), trains(name + ".c2"), down is not None and trains(name + ".down")
+            more = below[k] or any(want[name + ".c1"])                                           # somebody below c2 wants something
             sums_d = want[name + ".c2"][1] or want[name + ".c2"][2] or (down is not None and (want[name + ".down"][1] or want[name + ".down"][2]))
-            sums2 = gate(ge["c2"], ent["c2"], B, ho, wo, c2.cout, 1, 1, sums_d)                  # g2: the block's ReLU, both branches
-            params(name + ".c2", c2, ent["c1"], 1, c2.cin_p, c2.cin_p, ho, wo, ge["c2"], 1, sums2)
-            if down is not None:
+            g2 = gd = ge["c2"]
+            if t2 and (td or down is None):        # g2: the block's ReLU, both branches -- in the sweep of c2's sums
+                s2 = train_sums(name + ".c2", c2, ge["c2"], 1, ent["c2"], 1, ho, wo)
+                sums2 = None
+            else:
+                sums2 = gate(ge["c2"], ent["c2"], B, ho, wo, c2.cout, 1, 1, sums_d)
+                s2 = train_sums(name + ".c2", c2, ge["c2"], 1, None, 1, ho, wo) if t2 else None
+            if t2:
+                if more or want[name + ".c2"][0]:
+                    g2 = train_dz(name + ".c2", c2, ge["c2"], 1, s2, ge["dz"], ho, wo)
+                train_params(name + ".c2", c2, ent["c1"], 1, c2.cin_p, c2.cin_p, ho, wo, g2, 1, s2)
+            else:
+                params(name + ".c2", c2, ent["c1"], 1, c2.cin_p, c2.cin_p, ho, wo, ge["c2"], 1, sums2)
+            if td:
+                if below[k] or any(want[name + ".down"]):
+                    sd = train_sums(name + ".down", down, ge["c2"], 1, None, 1, ho, wo)
+                    if below[k] or want[name + ".down"][0]:
+                        gd = train_dz(name + ".down", down, ge["c2"], 1, sd, ge["dzd"], ho, wo)
+                    train_params(name + ".down", down, y_in, 1, cin, cin, hin, win, gd, 1, sd)
+            elif down is not None:
                 params(name + ".down", down, y_in, 1, cin, cin, hin, win, ge["c2"], 1, sums2)
-            if not (below[k] or any(want[name + ".c1"])):
+            if not more:
                 break                                                                            # nobody below wants anything
-            dgrad(name + ".c2", c2, ge["c2"], 1, None, ge["c1"], 1, c2.cin_p, c2.cin_p, ho, wo)
-            sums1 = gate(ge["c1"], ent["c1"], B, ho, wo, c1.cout, 1, 1, want[name + ".c1"][1] or want[name + ".c1"][2])
-            params(name + ".c1", c1, y_in, 1, cin, cin, hin, win, ge["c1"], 1, sums1)
+            dgrad(name + ".c2", c2, g2, 1, None, ge["c1"], 1, c2.cin_p, c2.cin_p, ho, wo)
+            g1 = ge["c1"]
+            if t1:
+                s1 = train_sums(name + ".c1", c1, ge["c1"], 1, ent["c1"], 1, ho, wo)
+                if below[k] or want[name + ".c1"][0]:
+                    g1 = train_dz(name + ".c1", c1, ge["c1"], 1, s1, ge["dz"], ho, wo)           # dz2 has been consumed (stream order)
+                train_params(name + ".c1", c1, y_in, 1, cin, cin, hin, win, g1, 1, s1)
+            else:
+                sums1 = gate(ge["c1"], ent["c1"], B, ho, wo, c1.cout, 1, 1, want[name + ".c1"][1] or want[name + ".c1"][2])
+                params(name + ".c1", c1, y_in, 1, cin, cin, hin, win, ge["c1"], 1, sums1)
             if not below[k]:
                 break
             # the identity / down-sample branch's gradient first, the main branch's data gradient adds it in its epilogue (fixed order)
             if down is not None:
-                dgrad(name + ".down", down, ge["c2"], 1, None, ge["tmp"], 1, cin, cin, hin, win)
+                dgrad(name + ".down", down, gd, 1, None, ge["tmp"], 1, cin, cin, hin, win)
                 other = ge["tmp"]
             else:
                 other = ge["c2"]
-            dgrad(name + ".c1", c1, ge["c1"], 1, other, g_in, 1, cin, cin, hin, win)
+            dgrad(name + ".c1", c1, g1, 1, other, g_in, 1, cin, cin, hin, win)
         else:
             stem = prep["stem"]
             hs, wst = fs["stem"].shape[1], fs["stem"].shape[2]
             _capi.call("hps_maxpool3x3s2_backward", P(fs["stem"]), P(gf["pool"]), P(gf["stem"]), B, hs, wst, stem.cout, 1, s)
-            sums0 = gate(gf["stem"], fs["stem"], B, hs, wst, stem.cout, 0, 0, want["stem"][1] or want["stem"][2])
-            if want["stem"][0] or want["stem"][1]:
-                _capi.call("hps_nchw_to_padded_nhwc_generic", P(x), P(gf["xin"]), B, C, C, H, W, W, 3, s)
-            params("stem", stem, gf["xin"], 3, C, C, H, W, gf["stem"], 0, sums0)
+            g0 = gf["stem"]
+            if trains("stem"):
+                if needs[0] or any(want["stem"]):
+                    s0 = train_sums("stem", stem, gf["stem"], 0, fs["stem"], 0, hs, wst)
+                    if needs[0] or want["stem"][0]:
+                        g0 = train_dz("stem", stem, gf["stem"], 0, s0, gf["dz_stem"], hs, wst)
+                    if want["stem"][0]:
+                        _capi.call("hps_nchw_to_padded_nhwc_generic", P(x), P(gf["xin"]), B, C, C, H, W, W, 3, s)
+                    train_params("stem", stem, gf["xin"], 3, C, C, H, W, g0, 0, s0)
+            else:
+                sums0 = gate(gf["stem"], fs["stem"], B, hs, wst, stem.cout, 0, 0, want["stem"][1] or want["stem"][2])
+                if want["stem"][0] or want["stem"][1]:
+                    _capi.call("hps_nchw_to_padded_nhwc_generic", P(x), P(gf["xin"]), B, C, C, H, W, W, 3, s)
+                params("stem", stem, gf["xin"], 3, C, C, H, W, gf["stem"], 0, sums0)
             if needs[0]:
                 dx = torch.empty(B, H, W, C, device=dev, dtype=torch.float32)
-                dgrad("stem", stem, gf["stem"], 0, None, dx, 0, C, C, H, W)
+                dgrad("stem", stem, g0, 0, None, dx, 0, C, C, H, W)
                 grads["input"] = dx.permute(0, 3, 1, 2).contiguous()
         out = []
         for name, _, _ in layers:

@@ -723,6 +723,52 @@ int hps_maxpool3x3s2_backward(const float* x, const float* gpool, float* dx, int
 int hps_global_avgpool_backward(const float* gfeat, float* gframe, int B, int H, int W, int C, int P, hps_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training-mode BatchNorm of the encoder  (csrc/bn_train.hip)
+ * models/resnet.py:48-49, 53-54, 142-143, 184-188: every nn.BatchNorm2d, run under model.train()
+ * (train/train_poseMF_shapeGaussian_net.py:114), i.e. torch's batch_norm(training=True): y = gamma (z - mean) / sqrt(var + eps) + beta
+ * with the batch's per-channel mean and biased variance over the n = B H W pixels, and running <- (1 - momentum) running +
+ * momentum batch with the unbiased variance var n / (n - 1).  A training layer's convolution runs with identity scale / shift, no
+ * residual and no ReLU into a raw frame z; the kernels below work on such (B, H + 2 pad, W + 2 pad, C) NHWC frames (interior only;
+ * halos are neither read nor written).  C = 4, 8, 16, ..., 1024 (a multiple of 4 with 256 % (C / 4) == 0), B H W < 2^31.
+ * No atomics, fixed summation orders: every result is bitwise repeatable.
+ * ---------------------------------------------------------------------------------------- */
+
+/* torch batch_norm's batch statistics: mean (C,) and biased var (C,) of the interior of z, float64.  The B H rows are cut into
+ * min(B H, 2048) contiguous chunks (a rule on B H alone); float64 sums of (z - K) and (z - K)^2 per chunk, K the channel's first
+ * interior pixel (no cancellation when |mean| >> std), chunks added in a fixed order.  workspace: hps_bn_batch_stats_workspace bytes. */
+int hps_bn_batch_stats(const float* z, double* workspace, double* mean, double* var, int B, int H, int W, int C, int pad,
+                       hps_stream_t stream);
+size_t hps_bn_batch_stats_workspace(int B, int H, int W, int C);
+
+/* One launch per layer, torch's BatchNorm bookkeeping (nn.BatchNorm2d.forward in training mode): scale = gamma invstd and
+ * shift = beta - mean scale, computed in float64 and rounded once to fp32; invstd = 1 / sqrt(var + eps) (C,) float64 is WRITTEN
+ * when var is given and READ when var is NULL (the backward's recompute applies saved statistics).  running_mean / running_var
+ * (fp32, both or neither; need var and n >= 2) <- (1 - momentum) running + momentum (mean | var n / (n - 1)), float64 rounded once;
+ * num_batches_tracked (int64 scalar, may be NULL) += 1.  NULL buffers: no update (recompute, ResNet.training_activations). */
+int hps_bn_train_fold(const double* mean, const double* var, double* invstd, const float* gamma, const float* beta, double eps,
+                      double momentum, long long n, float* scale, float* shift, float* running_mean, float* running_var,
+                      long long* num_batches_tracked, int C, hps_stream_t stream);
+
+/* The convolution epilogue of models/resnet.py:62-78 as a pass of its own: interior of y (ypad) = act(z scale + shift [+ residual]),
+ * z a raw frame (zpad), residual (may be NULL) in y's frame; the operations in the order of hps_conv2d_bn_act_pad's epilogue.
+ * In place (y == z, ypad == zpad) is allowed. */
+int hps_bn_apply_act_pad(const float* z, const float* scale, const float* shift, const float* residual, float* y, int B, int H, int W,
+                         int C, int zpad, int ypad, int relu, hps_stream_t stream);
+
+/* torch's batch_norm backward, the reductions: sums[0..C) = d beta = sum g, sums[C..2C) = d gamma = sum g zhat, zhat = (z - mean)
+ * invstd, float64, chunks as in hps_bn_batch_stats.  y (may be NULL): the layer's output frame (models/resnet.py:66, :77 ReLU); then
+ * g <- g where y > 0 else 0 is written back in the same sweep (hps_relu_gate_pad and the sums in one pass).  y NULL: g is only read. */
+int hps_bn_train_backward_sums(float* g, const float* z, const float* y, const double* mean, const double* invstd, double* workspace,
+                               double* sums, int B, int H, int W, int C, int gpad, int zpad, int ypad, hps_stream_t stream);
+size_t hps_bn_train_backward_sums_workspace(int B, int H, int W, int C);
+
+/* torch's batch_norm backward, the map: interior of dz (dpad) = gamma invstd (g - d beta / n - zhat d gamma / n), float64 per element,
+ * rounded once; out of place (the gated g of a block's output, models/resnet.py:75-77, is also the cotangent of the identity branch).
+ * hps_conv_wgrad(x, dz) is then dW itself and hps_conv_dgrad takes the unscaled filter. */
+int hps_bn_train_backward_dz(const float* g, const float* z, const double* mean, const double* invstd, const float* gamma,
+                             const double* sums, float* dz, int B, int H, int W, int C, int gpad, int zpad, int dpad, hps_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Proxy-representation front end  
  * ---------------------------------------------------------------------------------------- */
 
