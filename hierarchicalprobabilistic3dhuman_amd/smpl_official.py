@@ -71,6 +71,11 @@ class SMPL(DeviceStateModule):
         super().__init__()
         if dtype != torch.float32:
             raise ValueError("the gfx950 kernels compute in fp32 (the reference never changes dtype)")
+        if int(num_betas) < 1:
+            # include/hps.h documents 0..16 rows of betas at the C ABI; a module with NO shape coefficients would hand the library the
+            # null pointer of its empty (M, 0) betas tensor, which every entry point refuses -- say so here instead
+            raise ValueError("num_betas must be at least 1, got %r: this module has no form without shape coefficients (its empty betas "
+                             "tensor has no device pointer to give the library); pass zero betas instead" % (num_betas,))
         model = resolve_smpl_model(model_path, gender=gender, num_betas=num_betas)
         self.gender = gender
         self.batch_size = batch_size
@@ -123,6 +128,10 @@ class SMPL(DeviceStateModule):
         self._n_pose = n_pose
         self._kp = _round_up(nb + n_pose, 16)
         self._k_used = _round_up(nb + n_pose, 2)          # rows the fused kernel multiplies (the rest of the 16-row padding is zero)
+        # rows the shared-shape form multiplies: the pose rows alone, rounded up to even ON THEIR OWN (207 -> 208) -- not _k_used - nb,
+        # which is odd for an odd nb (nb = 11: 218 - 11 = 207, refused by the library).  Row nb + 207 of the operands is a zero row of
+        # the 16-row padding whenever the form is taken (_k_used == 218: nb + 208 <= 219 < _kp = 224).
+        self._kp_pose = _round_up(n_pose, 2)
         self._np = _round_up(self._N, 128)
         bmat = np.zeros((self._kp, self._np), np.float64)
         bmat[:nb, :self._N] = shapedirs.reshape(self._N, nb).T                    # row l: d v[n] / d beta_l
@@ -429,7 +438,7 @@ class SMPL(DeviceStateModule):
                 nb = self.num_betas
                 _capi.call("hps_smpl_mesh_fused_shared_shape", _capi._P(xt.data_ptr() + 4 * nb * mp), _capi._P(self._bmat_p.data_ptr() + 4 * nb * self._np_fused),
                            P(v_shaped), _capi.iptr(shared[1]), _capi.iptr(shared[2]), P(a), _capi.iptr(self._w_idx), P(self._w_val), self._lbs_k, J,
-                           P(verts), M, V, self._k_used - nb, mp, self._np_fused, _capi.iptr(self._pick_slot), P(picked), self._n_picked, s)
+                           P(verts), M, V, self._kp_pose, mp, self._np_fused, _capi.iptr(self._pick_slot), P(picked), self._n_picked, s)
             elif use_picks:
                 _capi.call("hps_smpl_mesh_fused_picks", P(xt), P(self._bmat_p), P(self._v_template_flat), P(a),
                            _capi.iptr(self._w_idx), P(self._w_val), self._lbs_k, J, trp, P(verts), M, V, self._k_used, mp,
