@@ -94,6 +94,9 @@ _PROTOTYPES = {
     "hps_mf_loss_backward": [_P, _P, _P, _P],
     "hps_head_forward_refine": [_P, _I] + [_P] * 9 + [_I] + [_P] * 6 + [_c.c_float] + [_P] * 13 + [_I] * 7 + [_P],
     "hps_head_pose_levels_backward": [_P, _I, _I, _P, _P, _I] + [_P] * 21 + [_I, _I, _I, _P],
+    "hps_head_pose_levels_backward_factors": [_P, _I, _I, _P, _P, _I] + [_P] * 23 + [_I, _I, _I, _P],
+    "hps_mf_sample_keep_quat": [_P, _P, _P, _I, _I, _I, _I, _c.c_float, _c.c_float, _P, _P, _P, _c.c_uint64, _c.c_int64, _I, _P, _P, _P, _P],
+    "hps_mf_sample_backward": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _c.c_float, _P, _P, _P, _P],
     "hps_head_trunk_backward": [_P, _I] + [_P] * 20 + [_I] * 7 + [_P],
     "hps_rot6d_to_rotmat_backward": [_P, _P, _P, _I, _P],
     "hps_conv_wgrad": [_P] * 4 + [_I] * 12 + [_P],

@@ -74,9 +74,12 @@ __device__ __forceinline__ void hidden_slices(const T* xs, const float* __restri
 // backward of a square matrix with distinct singular values as torch.svd's autograd evaluates it,
 //   gF = U [ (E o (U^T gU - gU^T U)) S + S (E o (V^T gV - gV^T V)) + diag(gS) ] V^T,   E_ij = 1 / (s_j^2 - s_i^2), i != j.
 // gUp / gSp / gM: what the joint's descendants left on its U_proper / S_proper / mode (gM already includes the caller's).
+// gU_raw / gV_raw: the caller's cotangents of the RAW factors pose_U / pose_V (:137; the sampler's, utils/sampling_utils.py:106-111):
+// they join gU / gV as they are, with no proper-fix factor.
 __device__ __forceinline__ void svd_head_backward(const double* __restrict__ Uf, const double* __restrict__ Sf,
                                                   const double* __restrict__ Vf, double* gUp, const double* gSp, const double* gM,
-                                                  const double* gS_raw, const double* gF_direct, double* gF) {
+                                                  const double* gS_raw, const double* gF_direct, const double* gU_raw,
+                                                  const double* gV_raw, double* gF) {
     double U[9], V[9], S[3];
 #pragma unroll
     for (int e = 0; e < 9; ++e) { U[e] = Uf[e]; V[e] = Vf[e]; }
@@ -99,8 +102,8 @@ __device__ __forceinline__ void svd_head_backward(const double* __restrict__ Uf,
                 a += gM[i * 3 + k] * V[k * 3 + j];
                 b += gM[k * 3 + i] * U[k * 3 + j];
             }
-            gU[i * 3 + j] = (gUp[i * 3 + j] + a * cv) * cu;
-            gV[i * 3 + j] = (b * cu) * cv;
+            gU[i * 3 + j] = (gUp[i * 3 + j] + a * cv) * cu + gU_raw[i * 3 + j];
+            gV[i * 3 + j] = (b * cu) * cv + gV_raw[i * 3 + j];
         }
     double gS[3] = {gS_raw[0] + gSp[0], gS_raw[1] + gSp[1], gS_raw[2] + gSp[2] * (dU * dV)};
     double A[9], Bm[9];                                      // U^T gU, V^T gV
@@ -148,7 +151,8 @@ __global__ __launch_bounds__(BW_NT) void joint_level_backward_kernel(
     const float* const* __restrict__ b1_ptrs, const float* const* __restrict__ w2_ptrs, const double* __restrict__ u_proper,
     const double* __restrict__ s_proper, const double* __restrict__ mode, const double* __restrict__ pose_u,
     const double* __restrict__ pose_s, const double* __restrict__ pose_v, const float* __restrict__ g_pose_f,
-    const float* __restrict__ g_pose_s, const float* __restrict__ g_mode, LevelsWs ws, int B, int NJ) {
+    const float* __restrict__ g_pose_s, const float* __restrict__ g_mode, const float* __restrict__ g_pose_u,
+    const float* __restrict__ g_pose_v, LevelsWs ws, int B, int NJ) {
     __builtin_amdgcn_s_setprio(3);                           // a short latency chain, as the forward levels (csrc/head.hip)
     extern __shared__ __attribute__((aligned(16))) float smem[];
     constexpr int NT = BW_NT, TBL = BW_TBL, HID = BW_HID;
@@ -182,10 +186,12 @@ __global__ __launch_bounds__(BW_NT) void joint_level_backward_kernel(
         for (int e = 0; e < 9; ++e) gF[e] = 0.0;
         if (b < B) {
             const size_t o = (size_t)b * NJ + joint;
-            double gUp[9], gSp[3], gM[9], gS[3], gFd[9];
+            double gUp[9], gSp[3], gM[9], gS[3], gFd[9], gUr[9], gVr[9];
 #pragma unroll
             for (int e = 0; e < 9; ++e) {
                 gUp[e] = 0.0;
+                gUr[e] = g_pose_u ? (double)g_pose_u[o * 9 + e] : 0.0;
+                gVr[e] = g_pose_v ? (double)g_pose_v[o * 9 + e] : 0.0;
                 gM[e] = g_mode ? (double)g_mode[o * 9 + e] : 0.0;
                 gFd[e] = g_pose_f ? (double)g_pose_f[o * 9 + e] : 0.0;
             }
@@ -200,7 +206,7 @@ __global__ __launch_bounds__(BW_NT) void joint_level_backward_kernel(
 #pragma unroll
                 for (int e = 0; e < 3; ++e) gSp[e] += (double)g[9 * Pd + 3 * p + e];
             }
-            svd_head_backward(pose_u + o * 9, pose_s + o * 3, pose_v + o * 9, gUp, gSp, gM, gS, gFd, gF);
+            svd_head_backward(pose_u + o * 9, pose_s + o * 3, pose_v + o * 9, gUp, gSp, gM, gS, gFd, gUr, gVr, gF);
 #pragma unroll
             for (int e = 0; e < 9; ++e) ws.gf[o * 9 + e] = (float)gF[e];
         }
@@ -614,33 +620,33 @@ extern "C" int hps_head_forward_refine(const float* feats, int ldf, const float*
     return HPS_OK;
 }
 
-extern "C" int hps_head_pose_levels_backward(const double* embed, int embed_dim, int hidden, const int32_t* level_joints,
+extern "C" int hps_head_pose_levels_backward_factors(const double* embed, int embed_dim, int hidden, const int32_t* level_joints,
                                              const int32_t* level_sizes_host, int n_levels, const int32_t* anc_ptr,
                                              const int32_t* anc_idx, const int32_t* desc_ptr, const int32_t* desc_joint,
                                              const int32_t* desc_pos, const int32_t* in_off, const float* const* w1t_ptrs,
                                              const float* const* b1_ptrs, const float* const* w2_ptrs, const double* u_proper,
                                              const double* s_proper, const double* mode, const double* pose_u, const double* pose_s,
                                              const double* pose_v, const float* g_pose_f, const float* g_pose_s, const float* g_mode,
-                                             float* g_embed, float* g_fc_pose, float* workspace, int B, int num_body_joints,
+                                             const float* g_pose_u, const float* g_pose_v, float* g_embed, float* g_fc_pose, float* workspace, int B, int num_body_joints,
                                              int total_in, hps_stream_t stream) {
     if (!embed || !level_joints || !level_sizes_host || !anc_ptr || !anc_idx || !desc_ptr || !desc_joint || !desc_pos || !in_off ||
         !w1t_ptrs || !b1_ptrs || !w2_ptrs || !u_proper || !s_proper || !mode || !pose_u || !pose_s || !pose_v || !g_embed || !workspace)
-        return bad_arg("hps_head_pose_levels_backward: null pointer");
-    if (hidden != BW_HID) { set_error("hps_head_pose_levels_backward: hidden=%d unsupported (128 = EMBED_DIM/2)", hidden); return HPS_E_UNSUPPORTED; }
+        return bad_arg("hps_head_pose_levels_backward_factors: null pointer");
+    if (hidden != BW_HID) { set_error("hps_head_pose_levels_backward_factors: hidden=%d unsupported (128 = EMBED_DIM/2)", hidden); return HPS_E_UNSUPPORTED; }
     const int NJ = num_body_joints;
     if (embed_dim <= 0 || NJ <= 0 || n_levels < 0 || total_in < NJ * embed_dim || total_in > NJ * (embed_dim + 21 * NJ))
-        return bad_arg("hps_head_pose_levels_backward: dims");
+        return bad_arg("hps_head_pose_levels_backward_factors: dims");
     int n_total = 0;
     for (int l = 0; l < n_levels; ++l) {
-        if (level_sizes_host[l] < 0) return bad_arg("hps_head_pose_levels_backward: level size");
+        if (level_sizes_host[l] < 0) return bad_arg("hps_head_pose_levels_backward_factors: level size");
         n_total += level_sizes_host[l];
     }
-    if (n_total != NJ) return bad_arg("hps_head_pose_levels_backward: the levels must hold every joint once");
+    if (n_total != NJ) return bad_arg("hps_head_pose_levels_backward_factors: the levels must hold every joint once");
     if (B <= 0) return HPS_OK;
-    if (B > 65535) { set_error("hps_head_pose_levels_backward: B=%d exceeds the grid's 65535 rows; split the batch", B); return HPS_E_UNSUPPORTED; }
+    if (B > 65535) { set_error("hps_head_pose_levels_backward_factors: B=%d exceeds the grid's 65535 rows; split the batch", B); return HPS_E_UNSUPPORTED; }
     const int max_in = embed_dim + 21 * NJ;
     const size_t lds = ((size_t)((max_in * BW_TBL + 3) & ~3) + 2 * BW_HID * BW_TBL + 4 * BW_TBL * BW_HID + BW_TBL * 12) * sizeof(float);
-    if (lds > 64 * 1024) { set_error("hps_head_pose_levels_backward: embed_dim=%d too large", embed_dim); return HPS_E_UNSUPPORTED; }
+    if (lds > 64 * 1024) { set_error("hps_head_pose_levels_backward_factors: embed_dim=%d too large", embed_dim); return HPS_E_UNSUPPORTED; }
     LevelsWs ws;
     ws.gx = workspace;
     ws.xs = ws.gx + (size_t)B * total_in;
@@ -656,17 +662,33 @@ extern "C" int hps_head_pose_levels_backward(const double* embed, int embed_dim,
         if (n_level == 0) continue;
         hipLaunchKernelGGL(joint_level_backward_kernel, dim3(n_level, ceil_div(B, BW_TBL)), dim3(BW_NT), lds, s, embed, embed_dim,
                            level_joints + first, anc_ptr, anc_idx, desc_ptr, desc_joint, desc_pos, in_off, w1t_ptrs, b1_ptrs, w2_ptrs,
-                           u_proper, s_proper, mode, pose_u, pose_s, pose_v, g_pose_f, g_pose_s, g_mode, ws, B, NJ);
-        const int rc = check_launch("hps_head_pose_levels_backward");
+                           u_proper, s_proper, mode, pose_u, pose_s, pose_v, g_pose_f, g_pose_s, g_mode, g_pose_u, g_pose_v, ws, B, NJ);
+        const int rc = check_launch("hps_head_pose_levels_backward_factors");
         if (rc != HPS_OK) return rc;
     }
     hipLaunchKernelGGL(embed_grad_kernel, dim3(ceil_div(embed_dim, 256), B), dim3(256), 0, s, ws.gx, anc_ptr, in_off, g_embed, embed_dim,
                        B, NJ);
-    int rc = check_launch("hps_head_pose_levels_backward");
+    int rc = check_launch("hps_head_pose_levels_backward_factors");
     if (rc != HPS_OK || !g_fc_pose) return rc;               // no parameter gradients wanted
     hipLaunchKernelGGL(joint_wgrad_kernel, dim3(ceil_div(BW_HID * max_in + BW_JOINT_TAIL, 256), NJ), dim3(256), 0, s, anc_ptr, in_off, ws,
                        g_fc_pose, embed_dim, B, NJ);
-    return check_launch("hps_head_pose_levels_backward");
+    return check_launch("hps_head_pose_levels_backward_factors");
+}
+
+// The entry point without cotangents on the raw factors (pose_U / pose_V not differentiable outputs): NULL = zero for both.
+extern "C" int hps_head_pose_levels_backward(const double* embed, int embed_dim, int hidden, const int32_t* level_joints,
+                                             const int32_t* level_sizes_host, int n_levels, const int32_t* anc_ptr,
+                                             const int32_t* anc_idx, const int32_t* desc_ptr, const int32_t* desc_joint,
+                                             const int32_t* desc_pos, const int32_t* in_off, const float* const* w1t_ptrs,
+                                             const float* const* b1_ptrs, const float* const* w2_ptrs, const double* u_proper,
+                                             const double* s_proper, const double* mode, const double* pose_u, const double* pose_s,
+                                             const double* pose_v, const float* g_pose_f, const float* g_pose_s, const float* g_mode,
+                                             float* g_embed, float* g_fc_pose, float* workspace, int B, int num_body_joints,
+                                             int total_in, hps_stream_t stream) {
+    return hps_head_pose_levels_backward_factors(embed, embed_dim, hidden, level_joints, level_sizes_host, n_levels, anc_ptr, anc_idx,
+                                                 desc_ptr, desc_joint, desc_pos, in_off, w1t_ptrs, b1_ptrs, w2_ptrs, u_proper, s_proper,
+                                                 mode, pose_u, pose_s, pose_v, g_pose_f, g_pose_s, g_mode, nullptr, nullptr, g_embed,
+                                                 g_fc_pose, workspace, B, num_body_joints, total_in, stream);
 }
 
 extern "C" int hps_head_trunk_backward(const float* feats, int ldf, const float* x, const float* sgc, const float* embed,

@@ -181,6 +181,171 @@ __global__ __launch_bounds__(512) void mf_sample_kernel(
     }
 }
 
+// ---- the sampler differentiated (utils/sampling_utils.py:21, 51-53, 103-141 under autograd) -----------------------------------------
+// R = U_p Rq(q) V_p^T with q = y / ||y||, y = Gaussian_std(S) * eps (:52-53); the accept test runs under no_grad (:55-62), so the
+// accepted quaternions the forward kept are all the backward needs:
+//   g_Up += g_R V_p Rq^T,  g_Vp += g_R^T U_p Rq,  g_Rq = U_p^T g_R V_p,
+//   g_q  from the quaternion -> matrix polynomial, its own renormalisation included (utils/rigid_transform_utils.py:113-133),
+//   g_sigma_i += q_i (g_q_i - q_i <q, g_q>) / sigma_i                     (||y|| cancels: eps_i / ||y|| = q_i / sigma_i),
+// and once per (image, joint) call: sigma = Omega^-1/2, Omega = 1 + 2 A / b, A = 2 (0, s2 + s3, s1 + s3, s1 + s2) on the proper
+// singular values (:119-124); det U, det V enter as the constants the forward multiplies by (:105-111).
+//
+// Mapping.  A call's N samples are spread over a GROUP of lanes, the group's 21 float64 partial sums (9 g_Up, 9 g_Vp, 3 g_sigma) are
+// added by an xor butterfly (every lane of the group ends with the same bits), and across wavefronts in ascending wave order: one fixed
+// order per output, no atomics; the order depends on N alone, never on B or on the call's position in the batch.
+//   N <= 64 : group = the next power of two >= N lanes, 64 / group calls per one-wave workgroup, one sample per lane.  At the
+//             training point (B 72, N 8, 23 joints: 1656 calls of 8 terms) that is 8 calls per wave: every lane of the 207
+//             one-wave workgroups carries a sample, where a wave per call would leave 56 of 64 idle.  The launch and one round of
+//             ~50-byte-per-lane loads bound it (18 us a call, 8 us in a step's call list), not bandwidth (1 MB in all) and not arithmetic.
+//   N > 64  : group = the workgroup, ceil(N / 128) <= 4 waves per call, lane t takes samples t, t + T, ...  Each sample is 52 bytes
+//             (4 quaternion + 9 g_R floats) read once; a lane's 36 and 16 bytes are contiguous and the neighbouring joints' workgroups
+//             (adjacent blockIdx) use the rest of the same lines, so HBM sees every line once: this regime is bound by the 52 bytes per sample
+//             (at B 64, N 100, 7.9 MB, the call is still 27 us, nearer the launch floor than the bandwidth bound).
+// pose_u_d / pose_s_d / pose_v_d (optional): the factors in float64 from the head's float64 pass -- the fp32 ones of an ill-conditioned
+// SVD are off by 2^-23 / gap, which the second derivative of R in (U, V) turns into gradient error; det U, det V stay the forward's.
+__global__ __launch_bounds__(256) void mf_sample_backward_kernel(
+    const float* __restrict__ pose_u, const float* __restrict__ pose_s, const float* __restrict__ pose_v,
+    const double* __restrict__ pose_u_d, const double* __restrict__ pose_s_d, const double* __restrict__ pose_v_d,
+    const float* __restrict__ quat, const float* __restrict__ g_r, int C, int nj, int N, int group, float b,
+    float* __restrict__ g_pose_u, float* __restrict__ g_pose_s, float* __restrict__ g_pose_v) {
+    __shared__ double sRed[4][21];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = blockDim.x >> 6;
+    // group < 64: several calls per wave; else the whole workgroup is one call
+    const int per_block = group < 64 ? 64 / group : 1;
+    const int call = blockIdx.x * per_block + (group < 64 ? lane / group : 0);
+    const int n0 = group < 64 ? lane % group : tid;
+    const int stride = group < 64 ? group : (int)blockDim.x;
+    const bool valid = call < C;
+    const int c = valid ? call : C - 1;                  // lanes beyond the last call compute on it again and store nothing
+    const int img = c / nj, joint = c % nj;
+
+    double U[9], V[9];
+    float Uf[9], Vf[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { Uf[e] = pose_u[(size_t)c * 9 + e]; Vf[e] = pose_v[(size_t)c * 9 + e]; }
+    const double dU = (double)det3(Uf), dV = (double)det3(Vf);      // the forward's constants (:105), its own fp32 values
+#pragma unroll
+    for (int e = 0; e < 9; ++e) {
+        // the float64 factors of the head's float64 pass where the caller has them (the fp32 ones are off by 2^-23 / gap)
+        U[e] = (pose_u_d ? pose_u_d[(size_t)c * 9 + e] : (double)Uf[e]) * (e % 3 == 2 ? dU : 1.0);
+        V[e] = (pose_v_d ? pose_v_d[(size_t)c * 9 + e] : (double)Vf[e]) * (e % 3 == 2 ? dV : 1.0);
+    }
+
+    double acc[21];
+#pragma unroll
+    for (int e = 0; e < 21; ++e) acc[e] = 0.0;
+    for (int n = n0; n < N; n += stride) {
+        const size_t o = ((size_t)img * N + n) * nj + joint;
+        const float4 q4 = *reinterpret_cast<const float4*>(quat + o * 4);
+        double G[9];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) G[e] = (double)g_r[o * 9 + e];
+        // the polynomial's own renormalisation (rigid_transform_utils.py:121)
+        const double nq = sqrt((double)q4.x * q4.x + (double)q4.y * q4.y + (double)q4.z * q4.z + (double)q4.w * q4.w);
+        const double w = q4.x / nq, x = q4.y / nq, y = q4.z / nq, z = q4.w / nq;
+        double Rq[9];
+        Rq[0] = w * w + x * x - y * y - z * z; Rq[1] = 2 * x * y - 2 * w * z;         Rq[2] = 2 * w * y + 2 * x * z;
+        Rq[3] = 2 * w * z + 2 * x * y;         Rq[4] = w * w - x * x + y * y - z * z; Rq[5] = 2 * y * z - 2 * w * x;
+        Rq[6] = 2 * x * z - 2 * w * y;         Rq[7] = 2 * w * x + 2 * y * z;         Rq[8] = w * w - x * x - y * y + z * z;
+        double GV[9], UR[9], VR[9];                       // g_R V_p, U_p Rq, V_p Rq^T
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double a = 0.0, u = 0.0, v = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    a += G[i * 3 + k] * V[k * 3 + j];
+                    u += U[i * 3 + k] * Rq[k * 3 + j];
+                    v += V[i * 3 + k] * Rq[j * 3 + k];
+                }
+                GV[i * 3 + j] = a; UR[i * 3 + j] = u; VR[i * 3 + j] = v;
+            }
+        double T[9];                                      // g_Rq = U_p^T (g_R V_p)
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                double gu = 0.0, gv = 0.0, t = 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    gu += G[i * 3 + k] * VR[k * 3 + j];   // g_R (V_p Rq^T)
+                    gv += G[k * 3 + i] * UR[k * 3 + j];   // g_R^T (U_p Rq)
+                    t += U[k * 3 + i] * GV[k * 3 + j];
+                }
+                acc[i * 3 + j] += gu;
+                acc[9 + i * 3 + j] += gv;
+                T[i * 3 + j] = t;
+            }
+        // cotangent of the normalised quaternion, then through the renormalisation
+        double gh[4];
+        gh[0] = 2.0 * (w * (T[0] + T[4] + T[8]) + x * (T[7] - T[5]) + y * (T[2] - T[6]) + z * (T[3] - T[1]));
+        gh[1] = 2.0 * (x * (T[0] - T[4] - T[8]) + y * (T[1] + T[3]) + z * (T[2] + T[6]) + w * (T[7] - T[5]));
+        gh[2] = 2.0 * (y * (T[4] - T[0] - T[8]) + x * (T[1] + T[3]) + w * (T[2] - T[6]) + z * (T[5] + T[7]));
+        gh[3] = 2.0 * (z * (T[8] - T[0] - T[4]) + w * (T[3] - T[1]) + x * (T[2] + T[6]) + y * (T[5] + T[7]));
+        const double qh[4] = {w, x, y, z};
+        const double dh = w * gh[0] + x * gh[1] + y * gh[2] + z * gh[3];
+        double gq[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gq[e] = (gh[e] - qh[e] * dh) / nq;
+        // q = y / ||y||, y = sigma eps: g_sigma_i = q_i (g_q_i - q_i <q, g_q>) / sigma_i (the division after the sum)
+        const double qs[4] = {(double)q4.x, (double)q4.y, (double)q4.z, (double)q4.w};
+        const double dq = qs[0] * gq[0] + qs[1] * gq[1] + qs[2] * gq[2] + qs[3] * gq[3];
+#pragma unroll
+        for (int e = 1; e < 4; ++e) acc[17 + e] += qs[e] * (gq[e] - qs[e] * dq);
+    }
+
+    // the group's sum: xor butterfly inside the wave (both partners add the same two values: identical bits on every lane)
+    const int span = group < 64 ? group : 64;
+    for (int m = 1; m < span; m <<= 1) {
+#pragma unroll
+        for (int e = 0; e < 21; ++e) acc[e] += __shfl_xor(acc[e], m, 64);
+    }
+    if (W > 1) {                                          // one call per workgroup: the waves' sums in ascending wave order
+        if (lane == 0) {
+#pragma unroll
+            for (int e = 0; e < 21; ++e) sRed[wave][e] = acc[e];
+        }
+        __syncthreads();
+        if (tid == 0) {
+#pragma unroll
+            for (int e = 0; e < 21; ++e) {
+                double t = sRed[0][e];
+                for (int j = 1; j < W; ++j) t += sRed[j][e];
+                acc[e] = t;
+            }
+        }
+    }
+    if (!valid || n0 != 0) return;                        // the group's first lane finishes and stores
+
+    const size_t cc = (size_t)c;
+    if (g_pose_u) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) g_pose_u[cc * 9 + e] = (float)(acc[e] * (e % 3 == 2 ? dU : 1.0));
+    }
+    if (g_pose_v) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) g_pose_v[cc * 9 + e] = (float)(acc[9 + e] * (e % 3 == 2 ? dV : 1.0));
+    }
+    if (g_pose_s) {
+        const double s0 = pose_s_d ? pose_s_d[cc * 3 + 0] : (double)pose_s[cc * 3 + 0];
+        const double s1 = pose_s_d ? pose_s_d[cc * 3 + 1] : (double)pose_s[cc * 3 + 1];
+        const double s2 = (pose_s_d ? pose_s_d[cc * 3 + 2] : (double)pose_s[cc * 3 + 2]) * (dU * dV);
+        const double A[3] = {2.0 * (s1 + s2), 2.0 * (s0 + s2), 2.0 * (s0 + s1)};        // A[1..3] (:119-121)
+        double gA[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const double om = 1.0 + 2.0 * A[e] / (double)b;                              // :123
+            const double sd = 1.0 / sqrt(om);                                            // :124
+            const double g_sd = acc[18 + e] / sd;
+            gA[e] = (-0.5 * sd / om * g_sd) * (2.0 / (double)b);                         // d Omega^-1/2 = -1/2 Omega^-3/2
+        }
+        g_pose_s[cc * 3 + 0] = (float)(2.0 * (gA[1] + gA[2]));
+        g_pose_s[cc * 3 + 1] = (float)(2.0 * (gA[0] + gA[2]));
+        g_pose_s[cc * 3 + 2] = (float)(2.0 * (gA[0] + gA[1]) * (dU * dV));
+    }
+}
+
 __global__ void quat_to_rotmat_kernel(const float* __restrict__ q, float* __restrict__ r, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -268,25 +433,75 @@ extern "C" int hps_infer_assemble(const float* mode, const float* glob_rotmats, 
     return check_launch("hps_infer_assemble");
 }
 
-extern "C" int hps_mf_sample(const float* pose_u, const float* pose_s, const float* pose_v, const float* bingham_a,
-                             const float* acg_override, int C, int num_joints, int num_samples, int n_prop, float b, float m_star, const float* eps, const float* w,
-                             const int32_t* draw_idx, uint64_t seed, int64_t call_offset, const uint64_t* seed_dev, int max_rounds,
-                             float* r_out, float* quat_out, int32_t* accepted, hps_stream_t stream) {
-    if (!pose_u || !pose_s || !pose_v || !r_out || !accepted) return bad_arg("hps_mf_sample: null pointer");
-    if ((eps != nullptr) != (w != nullptr) || (eps && !draw_idx)) return bad_arg("hps_mf_sample: eps, w and draw_idx go together");
-    if (num_joints <= 0 || C % num_joints != 0) return bad_arg("hps_mf_sample: C must be a multiple of num_joints");
-    if (num_samples <= 0 || n_prop < num_samples || !(b > 0.f)) return bad_arg("hps_mf_sample: num_samples / n_prop / b");
+static int mf_sample_launch(const char* who, const float* pose_u, const float* pose_s, const float* pose_v, const float* bingham_a,
+                            const float* acg_override, int C, int num_joints, int num_samples, int n_prop, float b, float m_star,
+                            const float* eps, const float* w, const int32_t* draw_idx, uint64_t seed, int64_t call_offset,
+                            const uint64_t* seed_dev, int max_rounds, int count_all, float* r_out, float* quat_out, int32_t* accepted,
+                            hps_stream_t stream) {
+    if (!pose_u || !pose_s || !pose_v || !r_out || !accepted) { set_error("bad argument: %s: null pointer", who); return HPS_E_BADARG; }
+    if ((eps != nullptr) != (w != nullptr) || (eps && !draw_idx)) { set_error("bad argument: %s: eps, w and draw_idx go together", who); return HPS_E_BADARG; }
+    if (num_joints <= 0 || C % num_joints != 0) { set_error("bad argument: %s: C must be a multiple of num_joints", who); return HPS_E_BADARG; }
+    if (num_samples <= 0 || n_prop < num_samples || !(b > 0.f)) { set_error("bad argument: %s: num_samples / n_prop / b", who); return HPS_E_BADARG; }
     if (max_rounds < 1) max_rounds = 1;
     if (C == 0) return HPS_OK;
     // wavefronts per call: a function of num_samples alone (results do not depend on it; this only keeps each wave at about
     // four 64-proposal blocks until the N-th accept at the usual acceptance of one in two)
     int waves = (2 * num_samples + 255) / 256;
     waves = waves < 1 ? 1 : (waves > 8 ? 8 : waves);
-    const int count_all = quat_out != nullptr;      // the Bingham entry point reports the round's total (accept_ratio, :67)
     hipLaunchKernelGGL(mf_sample_kernel, dim3(C), dim3(64 * waves), 0, (hipStream_t)stream, pose_u, pose_s, pose_v,
                        bingham_a, acg_override, num_joints, num_samples, n_prop, b, m_star, eps, w, draw_idx, seed, call_offset, seed_dev,
                        max_rounds, count_all, r_out, quat_out, accepted);
-    return check_launch("hps_mf_sample");
+    return check_launch(who);
+}
+
+extern "C" int hps_mf_sample(const float* pose_u, const float* pose_s, const float* pose_v, const float* bingham_a,
+                             const float* acg_override, int C, int num_joints, int num_samples, int n_prop, float b, float m_star, const float* eps, const float* w,
+                             const int32_t* draw_idx, uint64_t seed, int64_t call_offset, const uint64_t* seed_dev, int max_rounds,
+                             float* r_out, float* quat_out, int32_t* accepted, hps_stream_t stream) {
+    const int count_all = quat_out != nullptr;      // the Bingham entry point reports the round's total (accept_ratio, :67)
+    return mf_sample_launch("hps_mf_sample", pose_u, pose_s, pose_v, bingham_a, acg_override, C, num_joints, num_samples, n_prop, b,
+                            m_star, eps, w, draw_idx, seed, call_offset, seed_dev, max_rounds, count_all, r_out, quat_out, accepted,
+                            stream);
+}
+
+// The training route's forward: hps_mf_sample's launch with the accepted quaternions kept for hps_mf_sample_backward and WITHOUT
+// count_all -- the round is decided at the N-th accept, as in the launch without quat_out.
+extern "C" int hps_mf_sample_keep_quat(const float* pose_u, const float* pose_s, const float* pose_v, int C, int num_joints,
+                                       int num_samples, int n_prop, float b, float m_star, const float* eps, const float* w,
+                                       const int32_t* draw_idx, uint64_t seed, int64_t call_offset, int max_rounds, float* r_out,
+                                       float* quat_out, int32_t* accepted, hps_stream_t stream) {
+    if (!quat_out) return bad_arg("hps_mf_sample_keep_quat: null pointer");
+    return mf_sample_launch("hps_mf_sample_keep_quat", pose_u, pose_s, pose_v, nullptr, nullptr, C, num_joints, num_samples, n_prop, b,
+                            m_star, eps, w, draw_idx, seed, call_offset, nullptr, max_rounds, 0, r_out, quat_out, accepted, stream);
+}
+
+extern "C" int hps_mf_sample_backward(const float* pose_u, const float* pose_s, const float* pose_v, const double* pose_u_d,
+                                      const double* pose_s_d, const double* pose_v_d, const float* quat, const float* g_r, int C,
+                                      int num_joints, int num_samples, float b, float* g_pose_u, float* g_pose_s, float* g_pose_v,
+                                      hps_stream_t stream) {
+    if (!pose_u || !pose_s || !pose_v || !quat || !g_r) return bad_arg("hps_mf_sample_backward: null pointer");
+    if ((pose_u_d != nullptr) != (pose_s_d != nullptr) || (pose_u_d != nullptr) != (pose_v_d != nullptr))
+        return bad_arg("hps_mf_sample_backward: the float64 factors are all NULL or all given");
+    if (num_joints <= 0 || C < 0 || C % num_joints != 0) return bad_arg("hps_mf_sample_backward: C must be a multiple of num_joints");
+    if (num_samples <= 0 || !(b > 0.f)) return bad_arg("hps_mf_sample_backward: num_samples / b");
+    if (C == 0 || (!g_pose_u && !g_pose_s && !g_pose_v)) return HPS_OK;
+    const int N = num_samples;
+    int group = 1, threads = 64;
+    long blocks;
+    if (N <= 64) {
+        while (group < N) group <<= 1;
+        blocks = ((long)C * group + 63) / 64;
+        if (group == 64) blocks = C;
+    } else {
+        group = 64;                                  // the whole workgroup
+        int waves = (N + 127) / 128;
+        threads = 64 * (waves > 4 ? 4 : waves);
+        blocks = C;
+    }
+    if (blocks > 0x7fffffffL) { set_error("hps_mf_sample_backward: C=%d too large", C); return HPS_E_UNSUPPORTED; }
+    hipLaunchKernelGGL(mf_sample_backward_kernel, dim3((unsigned)blocks), dim3(threads), 0, (hipStream_t)stream, pose_u, pose_s, pose_v,
+                       pose_u_d, pose_s_d, pose_v_d, quat, g_r, C, num_joints, N, group, b, g_pose_u, g_pose_s, g_pose_v);
+    return check_launch("hps_mf_sample_backward");
 }
 
 extern "C" int hps_quat_to_rotmat(const float* quat, float* rotmat, int n, hps_stream_t stream) {

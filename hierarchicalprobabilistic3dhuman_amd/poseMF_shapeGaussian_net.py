@@ -27,8 +27,11 @@ parameter requiring grad, the head runs inside a torch.autograd.Function: its fo
 call (same bits for all eight outputs, in either latency mode and either SVD mode), its backward is hps_head_forward_refine (the head
 again in float64), hps_head_pose_levels_backward and hps_head_trunk_backward (csrc/head_backward.hip) and needs only the features and
 the saved pose_U's signs, so the host-SVD mode is differentiable
-too.  The one difference from the reference: ``pose_U`` and ``pose_V`` are marked non-differentiable (the loss detaches them and the
-sampler draws without grad).  With ``input`` given the encoder is part of the graph too (resnet.py: its own autograd function, device
+too.  By default ``pose_U`` and ``pose_V`` are marked non-differentiable (the stage-1 loss detaches them);
+``set_differentiable_factors(True)`` makes them differentiable outputs as in the reference, for its stage-2 step
+(train/train_poseMF_shapeGaussian_net.py:292-320): the reparameterised sampler (sampling_utils.pose_matrix_fisher_sampling_torch) hands
+its cotangents of the raw factors to the head's backward, where they join torch.svd's backward (hps_head_pose_levels_backward_factors).
+With ``input`` given the encoder is part of the graph too (resnet.py: its own autograd function, device
 backward kernels): the loss reaches every convolution and BatchNorm affine parameter and the input itself.  By default that is fine-tuning with
 frozen BatchNorm statistics (eval mode; ``.train()`` is refused); ``set_batchnorm_training(True)`` followed by ``.train()`` is the
 reference's ``model.train()`` step: batch statistics in the forward, running buffers updated on the device, the backward through the
@@ -74,6 +77,25 @@ def immediate_parents_to_all_parents(immediate_parents):
     return all_parents
 
 
+class _RefinedHead:
+    """The float64 pass of one differentiable forward (PoseMFShapeGaussianNet._refine), run at most once, by whichever backward asks
+    first: the head's own, or the reparameterised sampler's (sampling_utils._SampleFunction), which differentiates at the float64 factors
+    for the reason the head does -- the fp32 factors are off by 2^-23 / (gap of the singular values), and the sampler's second derivative
+    turns that into the gradient's error.  Travels on the factor tensors a forward with set_differentiable_factors(True) returns."""
+
+    def __init__(self, net, p, feats, pose_U, pose_S, pose_V):
+        self.net, self.p = net, p
+        self.feats, self.pose_U = feats.detach(), pose_U.detach()
+        self.ptrs = (pose_U.data_ptr(), pose_S.data_ptr(), pose_V.data_ptr())
+        self.result = None
+
+    def get(self):
+        if self.result is None:
+            self.result = self.net._refine(self.p, self.feats, self.pose_U)
+            self.feats = self.pose_U = None
+        return self.result
+
+
 class _HeadFunction(torch.autograd.Function):
     """The head (:95-162) for autograd: forward = the module's own kernel sequence, backward = the head again in float64 and the two device
     backward composites (_head_backward), without the kernels whose result ``ctx.needs_input_grad`` does not ask for.
@@ -85,17 +107,21 @@ class _HeadFunction(torch.autograd.Function):
         pose_F, pose_U, pose_S, pose_V, mode, loc, scale, glob, cam = outs
         ctx.net, ctx.p = net, p                        # p owns the kernel-side weights the backward reads
         ctx.save_for_backward(feats, pose_U, scale, *params)      # the backward evaluates the head again (in float64) from these
-        ctx.mark_non_differentiable(pose_U, pose_V)
+        ctx.refined = None
+        if net.differentiable_factors:
+            ctx.refined = _RefinedHead(net, p, feats, pose_U, pose_S, pose_V)
+        else:
+            ctx.mark_non_differentiable(pose_U, pose_V)
         ctx.set_materialize_grads(False)               # an output without a cotangent arrives as None: a NULL pointer for the kernels
         return outs
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, g_F, _g_U, g_S, _g_V, g_mode, g_loc, g_scale, g_glob, g_cam):
+    def backward(ctx, g_F, g_U, g_S, g_V, g_mode, g_loc, g_scale, g_glob, g_cam):
         feats, pose_U, scale = ctx.saved_tensors[:3]
         need = ctx.needs_input_grad
         g_feats, g_params = ctx.net._head_backward(ctx.p, feats, pose_U, scale, g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam,
-                                                   want_feats=need[2], want_params=any(need[3:]))
+                                                   want_feats=need[2], want_params=any(need[3:]), g_U=g_U, g_V=g_V, refined=ctx.refined)
         if g_params is None:
             return (None, None, g_feats) + (None,) * len(need[3:])
         return (None, None, g_feats) + tuple(g if n else None for g, n in zip(g_params, need[3:]))
@@ -142,6 +168,7 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         self.svd_mode = "device"       # "device": in-kernel gesdd-faithful SVD; "host": MKL sgesdd round trip (the routine itself)
         self.svd_flavor = None         # None: the rounding flavour of this host's MKL (calibrated); 0 / 1 force one
         self.latency_mode = False      # set_latency_mode(): encoder on direct kernels with many K slices, joint MLPs on wide workgroups
+        self.differentiable_factors = False   # set_differentiable_factors(): pose_U / pose_V carry a gradient (the stage-2 step)
         self._track_versions = False   # set by the first differentiable forward: parameters may now change in place (optimiser steps)
 
     def set_latency_mode(self, on=True):
@@ -157,6 +184,12 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         whose ``.training`` is set run on batch statistics and update their running buffers (ResNet.set_batchnorm_training).  Off, the
         default, ``.train()`` stays refused."""
         self.image_encoder.set_batchnorm_training(on)
+
+    def set_differentiable_factors(self, on=True):
+        """Opt in to ``pose_U`` / ``pose_V`` as differentiable outputs, as the reference's stage-2 step needs them
+        (train/train_poseMF_shapeGaussian_net.py:292-320: the sampled rotations depend on them, utils/sampling_utils.py:105-111, 140-141).
+        Off, the default, they are marked non-differentiable.  The forward's launches and bits are the same either way."""
+        self.differentiable_factors = bool(on)
 
     def _flavor(self):
         """Rounding flavour of the in-kernel SVD: ``svd_flavor`` if set (0 reference BLAS rounding, 1 fused), else the one that
@@ -257,23 +290,15 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         p["bwd"] = q
         return q
 
-    def _head_backward(self, p, feats, pose_U, scale, g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam, want_feats=True, want_params=True):
-        """(g_feats, parameter gradients in _head_params() order) from the cotangents of pose_F, pose_S, pose_rotmats_mode, the
-        Gaussian's loc / scale, glob and cam (None = zero): hps_head_forward_refine (the forward again in float64, signs of the singular
-        vectors from the saved pose_U), hps_head_pose_levels_backward, then hps_head_trunk_backward.  ``want_feats`` / ``want_params``
-        False (frozen features / all head parameters frozen): that result is None and its kernels are not launched."""
-        q = self._prepare_backward(p)
+    def _refine(self, p, feats, pose_U):
+        """hps_head_forward_refine: the head again in float64 from the fp32 features (signs of the singular vectors from ``pose_U``), the
+        values the backward differentiates at.  Returns its outputs by name."""
         B, dev = feats.shape[0], feats.device
         nj, embed_dim = self.num_joints, self.config.MODEL.EMBED_DIM
-        nsh, ng, nc = self.num_shape_params, self.num_glob_params, self.num_cam_params
-        nt = 2 * nsh + ng + nc
+        nt = 2 * self.num_shape_params + self.num_glob_params + self.num_cam_params
         nf, hidden = feats.shape[1], p["fc1_wt"].shape[1]
         P, VP, s = _capi.ptr, _capi._P, _capi.stream()
         f32 = dict(device=dev, dtype=torch.float32)
-        G = lambda g: None if g is None else _capi.f32c(g)
-        g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam = G(g_F), G(g_S), G(g_mode), G(g_loc), G(g_scale), G(g_glob), G(g_cam)
-        tail = embed_dim // 2 + 9 * (embed_dim // 2) + 9
-        # the forward again in float64 (hps_head_forward_refine): the values the backward differentiates at
         f64 = dict(device=dev, dtype=torch.float64)
         D = lambda t: _capi.ptr(t, torch.float64)
         delta = float(self.config.MODEL.DELTA_I_WEIGHT) if self.config.MODEL.DELTA_I else 0.0
@@ -287,15 +312,40 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
                    VP(p["b1_ptrs"].data_ptr()), VP(p["w2_ptrs"].data_ptr()), VP(p["b2_ptrs"].data_ptr()), delta, P(pose_U), P(x_f),
                    P(sgc_f), P(embed_f), D(x_d), D(sgc_d), D(embed_d), D(Up_d), D(Sp_d), D(mode_d), D(U_d), D(S_d), D(V_d), B, nf, hidden,
                    nt, embed_dim, embed_dim // 2, nj, s)
+        return dict(x_f=x_f, sgc_f=sgc_f, embed_f=embed_f, embed_d=embed_d, Up_d=Up_d, Sp_d=Sp_d, mode_d=mode_d, U_d=U_d, S_d=S_d, V_d=V_d)
+
+    def _head_backward(self, p, feats, pose_U, scale, g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam, want_feats=True, want_params=True,
+                       g_U=None, g_V=None, refined=None):
+        """(g_feats, parameter gradients in _head_params() order) from the cotangents of pose_F, pose_S, pose_rotmats_mode, the
+        Gaussian's loc / scale, glob and cam, and of the raw factors pose_U / pose_V (``g_U`` / ``g_V``) (None = zero): hps_head_forward_refine (the forward again in float64, signs of the singular
+        vectors from the saved pose_U), hps_head_pose_levels_backward_factors, then hps_head_trunk_backward.  ``want_feats`` / ``want_params``
+        False (frozen features / all head parameters frozen): that result is None and its kernels are not launched.  ``refined``: the
+        step's _RefinedHead when the sampler's backward may already have run the float64 pass (it is run once)."""
+        q = self._prepare_backward(p)
+        B, dev = feats.shape[0], feats.device
+        nj, embed_dim = self.num_joints, self.config.MODEL.EMBED_DIM
+        nsh, ng, nc = self.num_shape_params, self.num_glob_params, self.num_cam_params
+        nt = 2 * nsh + ng + nc
+        nf, hidden = feats.shape[1], p["fc1_wt"].shape[1]
+        P, VP, s = _capi.ptr, _capi._P, _capi.stream()
+        f32 = dict(device=dev, dtype=torch.float32)
+        G = lambda g: None if g is None else _capi.f32c(g)
+        g_F, g_S, g_mode, g_loc, g_scale, g_glob, g_cam = G(g_F), G(g_S), G(g_mode), G(g_loc), G(g_scale), G(g_glob), G(g_cam)
+        g_U, g_V = G(g_U), G(g_V)
+        tail = embed_dim // 2 + 9 * (embed_dim // 2) + 9
+        D = lambda t: _capi.ptr(t, torch.float64)
+        r = refined.get() if refined is not None else self._refine(p, feats, pose_U)
+        x_f, sgc_f, embed_f, embed_d = r["x_f"], r["sgc_f"], r["embed_f"], r["embed_d"]
+        Up_d, Sp_d, mode_d, U_d, S_d, V_d = r["Up_d"], r["Sp_d"], r["mode_d"], r["U_d"], r["S_d"], r["V_d"]
         g_embed = torch.empty(B, embed_dim, **f32)
         # one flat buffer for the 92 fc_pose gradients (one allocation, one launch); the tensors handed out are views of it
         g_pose = torch.empty((embed_dim // 2) * q["total_in"] + nj * tail, **f32) if want_params else None
         ws = torch.empty(_capi.query_workspace(_capi.WS_HEAD_LEVELS_BWD, B, q["total_in"], nj) // 4, **f32)
-        _capi.call("hps_head_pose_levels_backward", D(embed_d), embed_dim, embed_dim // 2, _capi.iptr(p["level_joints"]),
+        _capi.call("hps_head_pose_levels_backward_factors", D(embed_d), embed_dim, embed_dim // 2, _capi.iptr(p["level_joints"]),
                    VP(p["level_sizes_host"].data_ptr()), len(p["levels"]), _capi.iptr(p["anc_ptr"]), _capi.iptr(p["anc_idx"]),
                    _capi.iptr(q["desc_ptr"]), _capi.iptr(q["desc_joint"]), _capi.iptr(q["desc_pos"]), _capi.iptr(q["in_off"]),
                    VP(p["w1t_ptrs"].data_ptr()), VP(p["b1_ptrs"].data_ptr()), VP(p["w2_ptrs"].data_ptr()), D(Up_d), D(Sp_d),
-                   D(mode_d), D(U_d), D(S_d), D(V_d), P(g_F), P(g_S), P(g_mode), P(g_embed), P(g_pose), P(ws), B, nj,
+                   D(mode_d), D(U_d), D(S_d), D(V_d), P(g_F), P(g_S), P(g_mode), P(g_U), P(g_V), P(g_embed), P(g_pose), P(ws), B, nj,
                    q["total_in"], s)
         E = lambda *shape: torch.empty(*shape, **f32) if want_params else None
         g_feats = torch.empty(B, nf, **f32) if want_feats else None
@@ -359,8 +409,8 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
     def forward(self, input, input_feats=None):
         """models/poseMF_shapeGaussian_net.py:85-162.  input: (B,C,D,D); ``input_feats`` skips the encoder.
 
-        Differentiable with respect to ``input_feats`` and the head's parameters (module docstring); ``pose_U`` / ``pose_V`` carry no
-        gradient.  With ``input`` given the chain goes on through the encoder (ResNet.forward is differentiable with respect to its
+        Differentiable with respect to ``input_feats`` and the head's parameters (module docstring); ``pose_U`` / ``pose_V`` carry a
+        gradient only after ``set_differentiable_factors(True)``.  With ``input`` given the chain goes on through the encoder (ResNet.forward is differentiable with respect to its
         input and its convolution / BatchNorm affine parameters, eval-mode statistics)."""
         if input_feats is None:
             input_feats = self.image_encoder(input)
@@ -374,6 +424,10 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         feats = _capi.f32c(input_feats)
         if differentiable:
             outs = _HeadFunction.apply(self, p, feats, *self._head_params())
+            refined = outs[1].grad_fn.refined if outs[1].grad_fn is not None else None
+            if refined is not None:                           # for the sampler's backward (sampling_utils._SampleFunction)
+                for t in outs[1:4]:
+                    t._hps_refined = refined
         else:
             outs = self._head(feats, p)
         pose_F, pose_U, pose_S, pose_V, mode, loc, scale, glob, cam = outs

@@ -12,6 +12,14 @@ Random numbers
       (seed, global image index, joint, round, proposal): independent of batch size and of how images
       are sharded over GPUs.  ``seed=None`` takes the seed from torch's global CPU generator, so
       torch.manual_seed() still controls it.
+
+Training (the reference's stage-2 step, train/train_poseMF_shapeGaussian_net.py:292-320).  The reference writes the sampler as a
+reparameterisation (utils/sampling_utils.py:21, 51-53): y = Gaussian_std(S) * eps, q = y / ||y||, R = U_p quat_to_rotmat(q) V_p^T with
+the accept test under no_grad.  With grad mode on and pose_U, pose_S or pose_V requiring grad, pose_matrix_fisher_sampling_torch runs
+inside a torch.autograd.Function: the forward is the same launch (hps_mf_sample_keep_quat: same rotations bit for bit on both noise
+routes, the accepted quaternions kept), the backward one launch of hps_mf_sample_backward (csrc/mf_sample.hip).  Factors that are the
+outputs of a PoseMFShapeGaussianNet forward with set_differentiable_factors(True) are differentiated at that forward's float64 pass
+(the head's backward shares it); any other tensors at their fp32 values.
 """
 import numpy as np
 import torch
@@ -33,28 +41,38 @@ def _m_star(b):
 
 
 def _launch(pose_U, pose_S, pose_V, num_samples, n_prop, b, eps=None, w=None, draw_idx=None, seed=0,
-            call_offset=0, bingham_a=None, want_quat=False, acg_override=None, m_star=None, out=None, seed_dev=None):
+            call_offset=0, bingham_a=None, want_quat=False, acg_override=None, m_star=None, out=None, seed_dev=None,
+            keep_quat=False):
+    """One launch.  ``want_quat``: the Bingham entry point's quaternions (hps_mf_sample counts every proposal of the round then);
+    ``keep_quat``: the training route's (hps_mf_sample_keep_quat: the round still ends at the N-th accept)."""
     B, nj = pose_U.shape[:2]
     C = B * nj
     dev = pose_U.device
     if out is not None:        # caller-provided destination (e.g. the sample rows of the flattened SMPL pose buffer)
         assert out.shape == (B, num_samples, nj, 3, 3) and out.is_contiguous() and out.dtype == torch.float32
     R = out if out is not None else torch.empty(B, num_samples, nj, 3, 3, device=dev, dtype=torch.float32)
-    quat = torch.empty(B, num_samples, nj, 4, device=dev, dtype=torch.float32) if want_quat else None
+    quat = torch.empty(B, num_samples, nj, 4, device=dev, dtype=torch.float32) if want_quat or keep_quat else None
     accepted = torch.empty(C, device=dev, dtype=torch.int32)
     P = _capi.ptr
     ev = None
     if launch_events is not None:
         ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
         ev[0].record()
-    _capi.call("hps_mf_sample", P(pose_U), P(pose_S), P(pose_V), P(bingham_a) if bingham_a is not None else None,
-               P(acg_override) if acg_override is not None else None,
-               C, nj, num_samples, n_prop, float(b), _m_star(b) if m_star is None else float(m_star),
-               P(eps) if eps is not None else None, P(w) if w is not None else None,
-               _capi.iptr(draw_idx) if draw_idx is not None else None,
-               philox_key(seed), int(call_offset),
-               _capi.ptr(seed_dev, torch.int64) if seed_dev is not None else None, _MAX_ROUNDS,
-               P(R), P(quat) if quat is not None else None, _capi.iptr(accepted), _capi.stream())
+    if keep_quat:
+        assert bingham_a is None and acg_override is None and seed_dev is None and out is None
+        _capi.call("hps_mf_sample_keep_quat", P(pose_U), P(pose_S), P(pose_V), C, nj, num_samples, n_prop, float(b),
+                   _m_star(b) if m_star is None else float(m_star), P(eps) if eps is not None else None,
+                   P(w) if w is not None else None, _capi.iptr(draw_idx) if draw_idx is not None else None,
+                   philox_key(seed), int(call_offset), _MAX_ROUNDS, P(R), P(quat), _capi.iptr(accepted), _capi.stream())
+    else:
+        _capi.call("hps_mf_sample", P(pose_U), P(pose_S), P(pose_V), P(bingham_a) if bingham_a is not None else None,
+                   P(acg_override) if acg_override is not None else None,
+                   C, nj, num_samples, n_prop, float(b), _m_star(b) if m_star is None else float(m_star),
+                   P(eps) if eps is not None else None, P(w) if w is not None else None,
+                   _capi.iptr(draw_idx) if draw_idx is not None else None,
+                   philox_key(seed), int(call_offset),
+                   _capi.ptr(seed_dev, torch.int64) if seed_dev is not None else None, _MAX_ROUNDS,
+                   P(R), P(quat) if quat is not None else None, _capi.iptr(accepted), _capi.stream())
     if ev is not None:
         ev[1].record()
         launch_events.append(ev)
@@ -62,7 +80,7 @@ def _launch(pose_U, pose_S, pose_V, num_samples, n_prop, b, eps=None, w=None, dr
 
 
 def _host_stream_sampling(pose_U, pose_S, pose_V, num_samples, n_prop, b, bingham_a=None, want_quat=False, acg_override=None,
-                          m_star=None, out=None):
+                          m_star=None, out=None, keep_quat=False):
     """Reference-order host noise; rare discarded rounds (fewer than N accepted, :68-69) shift every later
     call one draw further down the stream, exactly as the sequential reference loop would."""
     B, nj = pose_U.shape[:2]
@@ -82,7 +100,7 @@ def _host_stream_sampling(pose_U, pose_S, pose_V, num_samples, n_prop, b, bingha
         w = torch.stack(w_l).to(dev)
         R, quat, accepted = _launch(pose_U, pose_S, pose_V, num_samples, n_prop, b, eps=eps, w=w,
                                     draw_idx=assign.to(dev), bingham_a=bingham_a, want_quat=want_quat,
-                                    acg_override=acg_override, m_star=m_star, out=out)
+                                    acg_override=acg_override, m_star=m_star, out=out, keep_quat=keep_quat)
         fails = (accepted.cpu() < num_samples).nonzero().flatten()
         if fails.numel() == 0:
             return R, quat, accepted
@@ -133,6 +151,53 @@ def bingham_sampling_for_matrix_fisher_torch(A, num_samples, Omega=None, Gaussia
     return quat[0, :, 0, :], accept_ratio
 
 
+def _record_accepted(accepted, num_samples):
+    """Book a Philox launch for check_sampling() (see pose_matrix_fisher_sampling_torch)."""
+    global last_accepted
+    last_accepted = (accepted, num_samples)
+    ev = torch.cuda.Event()
+    ev.record()
+    _pending.append((accepted, num_samples, ev))
+    if len(_pending) > _PENDING_MAX:
+        _fold_pending(_PENDING_MAX // 2)
+
+
+class _SampleFunction(torch.autograd.Function):
+    """pose_matrix_fisher_sampling_torch for autograd: forward = the sampler's launch with the accepted quaternions kept, backward =
+    hps_mf_sample_backward, writing only the cotangents ``ctx.needs_input_grad`` asks for."""
+
+    @staticmethod
+    def forward(ctx, U, S, V, num_samples, n_prop, b, sample_on_cpu, seed, call_offset, refined):
+        if sample_on_cpu:
+            R, quat, _ = _host_stream_sampling(U, S, V, num_samples, n_prop, b, keep_quat=True)
+        else:
+            R, quat, accepted = _launch(U, S, V, num_samples, n_prop, b, seed=seed, call_offset=call_offset, keep_quat=True)
+            _record_accepted(accepted, num_samples)
+        ctx.save_for_backward(U, S, V, quat)
+        ctx.b = float(b)
+        ctx.refined = refined
+        return R
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_R):
+        U, S, V, quat = ctx.saved_tensors
+        B, N, nj = quat.shape[:3]
+        need = ctx.needs_input_grad
+        g_R = _capi.f32c(g_R)
+        g_U = torch.empty_like(U) if need[0] else None
+        g_S = torch.empty_like(S) if need[1] else None
+        g_V = torch.empty_like(V) if need[2] else None
+        P = _capi.ptr
+        D = lambda t: _capi.ptr(t, torch.float64)
+        # factors that come from a head forward: differentiate at the float64 factors of its float64 pass (run once per step)
+        r = ctx.refined.get() if ctx.refined is not None else None
+        U_d, S_d, V_d = (r["U_d"], r["S_d"], r["V_d"]) if r is not None else (None, None, None)
+        _capi.call("hps_mf_sample_backward", P(U), P(S), P(V), D(U_d), D(S_d), D(V_d), P(quat), P(g_R), B * nj, nj, N, ctx.b, P(g_U),
+                   P(g_S), P(g_V), _capi.stream())
+        return g_U, g_S, g_V, None, None, None, None, None, None, None
+
+
 def pose_matrix_fisher_sampling_torch(pose_U, pose_S, pose_V, num_samples, b=1.5, oversampling_ratio=8,
                                       sample_on_cpu=False, seed=None, image_offset=0, out=None, seed_dev=None):
     """utils/sampling_utils.py:74-143: (B,23,3,3), (B,23,3), (B,23,3,3) -> R_samples (B,N,23,3,3).
@@ -141,11 +206,25 @@ def pose_matrix_fisher_sampling_torch(pose_U, pose_S, pose_V, num_samples, b=1.5
     the Philox route.  ``out``: optional contiguous (B,N,23,3,3) destination the kernel writes into.
     ``seed_dev``: optional (2,) int64 DEVICE tensor [seed, first call = image_offset * 23] read by the kernel at run time instead of
     ``seed`` / ``image_offset`` (GraphedInfer: a launch captured in a hipGraph must not bake the key in); such launches are not
-    recorded for check_sampling() -- the caller reads ``last_accepted`` itself."""
+    recorded for check_sampling() -- the caller reads ``last_accepted`` itself.
+
+    With grad mode on and any of pose_U / pose_S / pose_V requiring grad the result carries the reference's reparameterised gradient
+    (module docstring): the same rotations bit for bit; ``out`` and ``seed_dev`` are refused there (ValueError)."""
     for t, name in ((pose_U, "pose_U"), (pose_S, "pose_S"), (pose_V, "pose_V")):
         _capi.require_device(t, name)
     U, S, V = _capi.f32c(pose_U), _capi.f32c(pose_S), _capi.f32c(pose_V)
     n_prop = num_samples * oversampling_ratio
+    if torch.is_grad_enabled() and (pose_U.requires_grad or pose_S.requires_grad or pose_V.requires_grad):
+        if out is not None or seed_dev is not None:
+            raise ValueError("pose_matrix_fisher_sampling_torch: out= / seed_dev= are not available on the differentiable route "
+                             "(a caller-owned destination or a graph-captured key in a training step); sample under torch.no_grad()")
+        # the factors of a head forward carry that forward's float64 pass (poseMF_shapeGaussian_net._RefinedHead)
+        refined = getattr(pose_U, "_hps_refined", None)
+        if refined is not None and (refined is not getattr(pose_S, "_hps_refined", None) or refined is not getattr(pose_V, "_hps_refined", None)
+                                    or refined.ptrs != (U.data_ptr(), S.data_ptr(), V.data_ptr())):
+            refined = None
+        return _SampleFunction.apply(U, S, V, num_samples, n_prop, b, bool(sample_on_cpu),
+                                     0 if sample_on_cpu else _philox_seed(seed), image_offset * U.shape[1], refined)
     if sample_on_cpu:
         R, _, _ = _host_stream_sampling(U, S, V, num_samples, n_prop, b, out=out)
     else:
@@ -158,15 +237,11 @@ def pose_matrix_fisher_sampling_torch(pose_U, pose_S, pose_V, num_samples, b=1.5
         # Recorded with an event on the LAUNCH stream (several streams may sample: InferencePipeline's partitions); the counts
         # are reduced by check_sampling() / _fold_pending() on whatever stream is current then, after waiting for the event.
         # The tensors stay referenced here until then, so the caching allocator cannot hand their blocks to another stream.
-        global last_accepted
-        last_accepted = (accepted, num_samples)
         if seed_dev is not None:        # (an event recorded during stream capture cannot be waited for outside the graph)
+            global last_accepted
+            last_accepted = (accepted, num_samples)
             return R
-        ev = torch.cuda.Event()
-        ev.record()
-        _pending.append((accepted, num_samples, ev))
-        if len(_pending) > _PENDING_MAX:
-            _fold_pending(_PENDING_MAX // 2)
+        _record_accepted(accepted, num_samples)
     return R
 
 

@@ -348,6 +348,33 @@ int hps_mf_sample(const float* pose_u, const float* pose_s, const float* pose_v,
                   int64_t call_offset, const uint64_t* seed_dev, int max_rounds, float* r_out, float* quat_out,
                   int32_t* accepted, hps_stream_t stream);
 
+/* The training route of the sampler (utils/sampling_utils.py:21, 51-53, 103-141 under autograd; the stage-2 step,
+ * train/train_poseMF_shapeGaussian_net.py:292-320).
+ * hps_mf_sample_keep_quat: the launch of hps_mf_sample(bingham_a = acg_override = seed_dev = NULL) -- the same r_out and accepted
+ * bit for bit on both noise routes -- that also writes the accepted unit quaternions quat_out (B, N, J-1, 4) in the order of r_out,
+ * WITHOUT hps_mf_sample's count_all (there a non-NULL quat_out makes every round evaluate all n_prop proposals for the Bingham entry
+ * point's accept ratio, :67): the round is decided at the N-th accept. */
+int hps_mf_sample_keep_quat(const float* pose_u, const float* pose_s, const float* pose_v, int C, int num_joints, int num_samples,
+                            int n_prop, float b, float m_star, const float* eps, const float* w, const int32_t* draw_idx,
+                            uint64_t seed, int64_t call_offset, int max_rounds, float* r_out, float* quat_out, int32_t* accepted,
+                            hps_stream_t stream);
+
+/* The reparameterised sampler differentiated, one launch: what torch autograd computes for :52-53 (y = Gaussian_std * eps,
+ * q = y / ||y||), :105-111 (proper fix, det U and det V constants), :119-124 (A, Omega, Gaussian_std from pose_S) and :139-141
+ * (R = U_p quat_to_rotmat(q) V_p^T, utils/rigid_transform_utils.py:113-133 with its renormalisation); the accept test (:55-62) is
+ * under no_grad.  Inputs: the forward's pose_u / pose_s / pose_v (C = B (J-1) calls), quat (B, N, J-1, 4) from
+ * hps_mf_sample_keep_quat, g_r (B, N, J-1, 3, 3) the cotangent of r_out.  No noise is needed: ||y|| cancels,
+ * g_sigma_i = sum_n q_i (g_q_i - q_i <q, g_q>) / sigma_i.  Outputs (each may be NULL = not wanted, not written): g_pose_u (C, 3, 3),
+ * g_pose_s (C, 3), g_pose_v (C, 3, 3), cotangents of the RAW factors.  float64 sums over the samples in one fixed order that depends
+ * on num_samples alone (no atomics): bitwise repeatable, an image's result independent of B.  NaN quaternions (a failed call) give
+ * NaN gradients.  pose_u_d / pose_s_d / pose_v_d (all NULL or all given): the same factors in float64 from hps_head_forward_refine
+ * (its pose_u / pose_s / pose_v outputs); the gradient is then evaluated at them -- the fp32 factors of an ill-conditioned SVD are off by
+ * 2^-23 / (gap of the singular values), which the sampler's second derivative turns into gradient error -- while det U, det V stay the
+ * forward's constants from the fp32 factors. */
+int hps_mf_sample_backward(const float* pose_u, const float* pose_s, const float* pose_v, const double* pose_u_d,
+                           const double* pose_s_d, const double* pose_v_d, const float* quat, const float* g_r, int C, int num_joints,
+                           int num_samples, float b, float* g_pose_u, float* g_pose_s, float* g_pose_v, hps_stream_t stream);
+
 /* Inputs of ONE flattened SMPL call over the M = B (N + 2) meshes [mode (B) | T-pose (B) | samples (B N)] of the inference
  * core (predict/predict_poseMF_shapeGaussian_net.py:112-115 mode mesh, :136 T-pose mesh, utils/sampling_utils.py:178-185 sample
  * meshes): body (M, J-1, 3, 3) rows [0, 2B) (mode rotations, then identities; rows [2B, M) are where hps_mf_sample wrote its
@@ -643,6 +670,20 @@ int hps_head_pose_levels_backward(const double* embed, int embed_dim, int hidden
                                   const double* pose_v, const float* g_pose_f, const float* g_pose_s, const float* g_mode,
                                   float* g_embed, float* g_fc_pose, float* workspace, int B, int num_body_joints,
                                   int total_in, hps_stream_t stream);
+
+/* hps_head_pose_levels_backward with cotangents on the raw SVD factors too: g_pose_u / g_pose_v (fp32 (B,NJ,3,3), each may be NULL =
+ * zero) are the cotangents of pose_U / pose_V as models/poseMF_shapeGaussian_net.py:137 returns them (the reference's sampler reads
+ * them, utils/sampling_utils.py:105-111, and torch.svd's backward takes them).  They join gU / gV before U^T gU / V^T gV, without a
+ * proper-fix factor.  Everything else as hps_head_pose_levels_backward, which is this call with both NULL. */
+int hps_head_pose_levels_backward_factors(const double* embed, int embed_dim, int hidden, const int32_t* level_joints,
+                                          const int32_t* level_sizes_host, int n_levels, const int32_t* anc_ptr,
+                                          const int32_t* anc_idx, const int32_t* desc_ptr, const int32_t* desc_joint,
+                                          const int32_t* desc_pos, const int32_t* in_off, const float* const* w1t_ptrs,
+                                          const float* const* b1_ptrs, const float* const* w2_ptrs, const double* u_proper,
+                                          const double* s_proper, const double* mode, const double* pose_u, const double* pose_s,
+                                          const double* pose_v, const float* g_pose_f, const float* g_pose_s, const float* g_mode,
+                                          const float* g_pose_u, const float* g_pose_v, float* g_embed, float* g_fc_pose,
+                                          float* workspace, int B, int num_body_joints, int total_in, hps_stream_t stream);
 
 /* models/poseMF_shapeGaussian_net.py:95-110 differentiated.  feats and shape_scale from the forward; x, sgc, embed: the fp32 outputs
  * x_f, sgc_f, embed_f of hps_head_forward_refine.  fc1_w (hidden, num_feats), sgc_w (2 num_shape + num_glob + num_cam, hidden) = fc_shape | fc_glob | fc_cam stacked,
