@@ -114,6 +114,9 @@ _PROTOTYPES = {
     "hps_bn_train_backward_sums": [_P] * 7 + [_I] * 7 + [_P],
     "hps_bn_train_backward_sums_workspace": [_I] * 4,
     "hps_bn_train_backward_dz": [_P] * 7 + [_I] * 7 + [_P],
+    "hps_seg_bbox_affine": [_P, _c.c_int64, _P, _I, _I, _I, _I, _c.c_float, _P, _P, _P, _P, _P, _P],
+    "hps_train_crop_augment": [_P, _c.c_int64, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
+    "hps_train_joints2d": [_P, _P, _P, _P, _P, _I, _I, _c.c_float, _I, _I, _P, _P, _P, _P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -313,6 +316,7 @@ WS_CONV_SPLITK, WS_SMPL_MP, WS_SMPL_XT, WS_SMPL_A, WS_SMPL_VPOSED, WS_HEAD_F, WS
 WS_MF_LOSS = 8
 WS_SMPL_LBS_BWD, WS_SMPL_BLEND_BWD = 9, 10
 WS_HEAD_LEVELS_BWD, WS_HEAD_TRUNK_BWD = 11, 12
+WS_SEG_BBOX = 13
 
 
 def query_workspace(what, d0=0, d1=0, d2=0):

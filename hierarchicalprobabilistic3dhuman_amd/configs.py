@@ -26,9 +26,26 @@ def _loss_stage(overreg, pose, shape, joints2d, glob_rotmats, verts3d, joints3d)
                                                    VERTS3D=verts3d, JOINTS3D=joints3d))
 
 
+def _synth_data():
+    """configs/poseMF_shapeGaussian_net_config.py:36-80: the values the synthetic-data front end reads (train_augmentation) -- camera,
+    box, proxy-representation and RGB augmentation; probabilities, ranges and class lists only."""
+    proxy_rep = SimpleNamespace(
+        REMOVE_PARTS_CLASSES=list(range(1, 25)),                                     # DensePose part classes
+        REMOVE_PARTS_PROBS=[0.1, 0.1, 0.1, 0.1, 0.1, 0.1, 0.05, 0.05, 0.05, 0.05, 0.1, 0.1,
+                            0.1, 0.1, 0.05, 0.05, 0.05, 0.05, 0.1, 0.1, 0.1, 0.1, 0.05, 0.05],
+        REMOVE_APPENDAGE_JOINTS_PROB=0.5, REMOVE_JOINTS_INDICES=[7, 8, 9, 10, 13, 14, 15, 16], REMOVE_JOINTS_PROB=0.1,
+        DELTA_J2D_DEV_RANGE=[-6, 6], JOINTS_TO_SWAP=[[5, 6], [11, 12]], JOINTS_SWAP_PROB=0.1, OCCLUDE_BOX_DIM=48,
+        OCCLUDE_BOX_PROB=0.1, OCCLUDE_BOTTOM_PROB=0.02, OCCLUDE_TOP_PROB=0.005, OCCLUDE_VERTICAL_PROB=0.05, EXTREME_CROP_PROB=0.1)
+    rgb = SimpleNamespace(OCCLUDE_BOTTOM_PROB=0.02, OCCLUDE_TOP_PROB=0.005, OCCLUDE_VERTICAL_PROB=0.05, PIXEL_CHANNEL_NOISE=0.2)
+    bbox = SimpleNamespace(DELTA_SCALE_RANGE=[-0.3, 0.2], DELTA_CENTRE_RANGE=[-5, 5])
+    return SimpleNamespace(FOCAL_LENGTH=300.0, MEAN_CAM_T=[0.0, -0.2, 2.5],
+                           AUGMENT=SimpleNamespace(BBOX=bbox, PROXY_REP=proxy_rep, RGB=rgb))
+
+
 def get_cfg_defaults():
-    """Values of configs/poseMF_shapeGaussian_net_config.py:8-24 that the inference path reads, and of :83-110 that
-    matrix_fisher_loss.PoseMFShapeGaussianLoss reads (LOSS.STAGE1 / STAGE2: REDUCTION, MF_OVERREG, WEIGHTS)."""
+    """Values of configs/poseMF_shapeGaussian_net_config.py:8-24 that the inference path reads, of :83-110 that
+    matrix_fisher_loss.PoseMFShapeGaussianLoss reads (LOSS.STAGE1 / STAGE2: REDUCTION, MF_OVERREG, WEIGHTS), and of :29, :36-80 that
+    the synthetic-data training front end reads (TRAIN.BATCH_SIZE, TRAIN.SYNTH_DATA)."""
     return SimpleNamespace(
         MODEL=SimpleNamespace(NUM_IN_CHANNELS=18, NUM_RESNET_LAYERS=18, EMBED_DIM=256,
                               DELTA_I=True, DELTA_I_WEIGHT=1.0, NUM_SMPL_BETAS=10),
@@ -37,4 +54,5 @@ def get_cfg_defaults():
                              BBOX_THRESHOLD=0.95, BBOX_SCALE_FACTOR=1.2),
         LOSS=SimpleNamespace(STAGE1=_loss_stage(1.005, 80.0, 50.0, 5000.0, 5000.0, 0.0, 0.0),
                              STAGE2=_loss_stage(1.005, 10.0, 80.0, 30000.0, 5000.0, 5000.0, 5000.0)),
+        TRAIN=SimpleNamespace(BATCH_SIZE=72, SYNTH_DATA=_synth_data()),
     )

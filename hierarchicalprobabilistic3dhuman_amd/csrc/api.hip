@@ -33,6 +33,7 @@ extern "C" int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t
         case HPS_WS_SMPL_BLEND_BWD: return hps::blend_backward_ws_bytes(d0, d1, d2);
         case HPS_WS_HEAD_LEVELS_BWD: return hps::head_levels_backward_ws_bytes(d0, d1, d2);
         case HPS_WS_HEAD_TRUNK_BWD: return hps::head_trunk_backward_ws_bytes(d0, d1, d2);
+        case HPS_WS_SEG_BBOX: return d0 * 32 * 4 * (int64_t)sizeof(int32_t);      // csrc/train_frontend.hip: TF_CHUNKS corner quadruples
 #ifdef HPS_DEV_BUILD
         case HPS_DEV_WS_HEAD_SYNC: return ((d0 + 3) / 4) * (HPS_HEAD_MAX_LEVELS + 1) * (int64_t)sizeof(int32_t);
 #endif

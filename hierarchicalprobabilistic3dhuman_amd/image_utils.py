@@ -14,13 +14,26 @@ def convert_bbox_corners_to_centre_hw_torch(bbox_corners):
     return centres.float(), bbox_corners[:, 2] - bbox_corners[:, 0], bbox_corners[:, 3] - bbox_corners[:, 1]
 
 
+def batch_add_rgb_background(backgrounds, rgb, seg):
+    """utils/image_utils.py:48-59: ``backgrounds`` (B,3,D,D) where ``seg`` (B,D,D) is 0, ``rgb`` elsewhere (body pixels are > 0,
+    out-of-frame pixels -1).  One launch of hps_train_crop_augment with only its composite stage on; device tensors only."""
+    from . import _capi, train_augmentation as ta
+    for t, what in ((backgrounds, "backgrounds"), (rgb, "rgb"), (seg, "seg")):
+        _capi.require_device(t, what)
+    x = _capi.f32c(rgb)
+    out = torch.empty_like(x)
+    ta.crop_augment(_capi.f32c(seg), x, _capi.f32c(backgrounds), None, None, x.shape[-1], ta.BACKGROUND, rgb_out=out)
+    return out
+
+
 def batch_crop_pytorch_affine(input_wh, output_wh, num_to_crop, device, joints2D=None, rgb=None, bbox_centres=None,
                               bbox_heights=None, bbox_widths=None, orig_scale_factor=1.2, **unsupported):
     """utils/image_utils.py:234-372 for the arguments predict_hrnet (:86-95) and the predict harness (:78-87) pass: crop the
     box (centre in (vertical, horizontal) order, height, width; widened to the output aspect ratio, scaled by
     ``orig_scale_factor``) out of ``rgb`` (B,3,H,W) into (B,3,out_h,out_w) by bilinear resampling with zero padding, and
     map ``joints2D`` (B,K,2) = (horizontal, vertical) into the crop.  The bounding-box-from-IUV/seg/joints and the random
-    augmentation branches (:275-307, :315-326) belong to training and are not implemented."""
+    augmentation branches (:275-307, :315-326) belong to training and are not implemented HERE: the training form is
+    train_augmentation.batch_crop_pytorch_affine_train (device kernels)."""
     if unsupported:
         raise NotImplementedError("batch_crop_pytorch_affine: unsupported arguments %s" % sorted(unsupported))
     if bbox_centres is None or bbox_heights is None or bbox_widths is None:

@@ -1,5 +1,5 @@
 """Joint-layout constants and heat-map generation on the hot path, mirroring the reference's
-utils/label_conversions.py (names and values of :17-20; function of :105-124)."""
+utils/label_conversions.py (names and values of :17-35; functions of :38-72 and :105-124)."""
 import torch
 
 from . import _capi
@@ -10,6 +10,20 @@ ALL_JOINTS_TO_COCO_MAP = [24, 26, 25, 28, 27, 16, 17, 18, 19, 20, 21, 1, 2, 4, 5
 ALL_JOINTS_TO_H36M_MAP = list(range(73, 90))
 H36M_TO_J17 = [6, 5, 4, 1, 2, 3, 16, 15, 14, 11, 12, 13, 8, 10, 0, 7, 9]
 H36M_TO_J14 = H36M_TO_J17[:14]
+# 24-part (DensePose) class -> the COCO joint removed with it: utils/label_conversions.py:24-35
+TWENTYFOUR_PART_SEG_TO_COCO_JOINTS_MAP = {19: 7, 21: 7, 20: 8, 22: 8, 4: 9, 3: 10, 12: 13, 14: 13, 11: 14, 13: 14, 5: 15, 6: 16}
+# 24-part class -> 14-part label, index = class (0 = background): utils/label_conversions.py:47-70
+DENSEPOSE_24_TO_14_PART = [0, 1, 1, 11, 12, 14, 13, 8, 6, 8, 6, 9, 7, 9, 7, 2, 4, 2, 4, 3, 5, 3, 5, 10, 10]
+
+
+def convert_densepose_seg_to_14part_labels(densepose_seg):
+    """utils/label_conversions.py:38-72 as a table lookup: 24-part classes (a float or integer tensor of whole numbers) -> 14-part
+    labels, same dtype; anything outside 1..24 (background 0, out-of-frame -1) -> 0.  The fused training front end never forms this
+    plane -- hps_train_crop_augment counts the labels directly."""
+    _capi.require_device(densepose_seg, "densepose_seg")
+    table = torch.tensor(DENSEPOSE_24_TO_14_PART, device=densepose_seg.device, dtype=densepose_seg.dtype)
+    inside = (densepose_seg >= 0) & (densepose_seg <= 24)
+    return table[densepose_seg.clamp(0, 24).long()] * inside
 
 
 def convert_2Djoints_to_gaussian_heatmaps_torch(joints2D, img_wh, std=4):

@@ -102,10 +102,11 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_HEAD_LEVELS_BWD (d0 = B, d1 = total_in, d2 = num_body_joints)  workspace of hps_head_pose_levels_backward
  *   HPS_WS_HEAD_TRUNK_BWD  (d0 = B, d1 = num_feats + hidden + embed_dim, d2 = 2 num_shape + num_glob + num_cam)
  *                                                               workspace of hps_head_trunk_backward
+ *   HPS_WS_SEG_BBOX    (d0 = B)                                 ws of hps_seg_bbox_affine (per-chunk integer box corners)
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
        HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
-       HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12 };
+       HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -847,6 +848,86 @@ int hps_heatmaps_to_joints2d(const float* heatmaps, float* joints2d, float* visi
 int hps_sample_joints2d_error(const float* joints, const int32_t* coco_map, int n_joints_all,
                               const float* in_j2d, const float* in_vis, const float* cam, float img_wh,
                               float* err, int N, int K, hps_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Synthetic-data training front end  (train/train_poseMF_shapeGaussian_net.py:199-244; csrc/train_frontend.hip)
+ *
+ * Everything between the renderer's IUV / RGB images and the Canny and heat-map kernels above.  All random DECISIONS of a step are
+ * made on the host, in the reference's order of draws (train_augmentation.draw_augment_plan), and reach the device as one record of
+ * HPS_TRAIN_PLAN_WORDS 32-bit words per image, `plan` (B, HPS_TRAIN_PLAN_WORDS) int32 (f = the word holds a float):
+ *    0      classes (bit c = class c) left out of the bounding box         utils/augmentation/proxy_rep_augmentation.py:238-275
+ *    1      classes removed from the segmentation                          :27-59
+ *    2      f delta scale;  3, 4  f delta centre (vertical, horizontal)    utils/image_utils.py:315-326
+ *    5-8    occlusion box: rows [lo, hi), columns [lo, hi)                 proxy_rep_augmentation.py:94-118
+ *    9-14   segmentation half occlusions: bottom rows [lo, hi), top rows [lo, hi), vertical columns [lo, hi)       :121-183
+ *   15-20   the same three for the RGB image                               utils/augmentation/rgb_augmentation.py:6-68
+ *   21-24   f joint tests that go with 9-14: invisible if v > [21], v < [22], u < [23], u > [24] (+-inf: test off)
+ *   25-28   f the same for 15-20
+ *   29      joints made invisible (bit k = joint k)                        proxy_rep_augmentation.py:50-57, :62-70
+ *   30-32   f channel factors                                              rgb_augmentation.py:71-77
+ *   33-49   source joint of joint k after the swaps                        proxy_rep_augmentation.py:73-91
+ *   50-83   f deviation (u, v) added to joint k                            :7-24
+ * Every range is a Python slice of the reference normalised by slice.indices (int16 truncation and negative starts included); an
+ * empty range is (0, 0).
+ * ---------------------------------------------------------------------------------------- */
+#define HPS_TRAIN_PLAN_WORDS 84
+#define HPS_TRAIN_NUM_JOINTS 17
+#define HPS_TRAIN_NUM_PART_COUNTS 8 /* pixels of the 14-part labels 3, 5, 7, 9, 11, 12, 13, 14, in this order */
+
+/* utils/image_utils.py:277-345 with a bbox_determiner: per image the bounding box of the pixels of `part` (image b's H x W plane at
+ * part + b * part_batch_stride: channel 0 of an IUV batch with stride 3 H W, fp32 holding integers) whose class is non-zero and not
+ * in plan word 0 -- torch.nonzero(bbox_determiner[i] != 0) with min and max, :303-305 -- then :307-345 in fp32, operation by
+ * operation: centre, height and width, aspect fix, orig_scale_factor + delta scale, centre + delta centre.  Writes affine (B,2,3),
+ * the forward map of :330-334, and theta (B,4) = (theta00, theta02, theta11, theta12) of the normalised inverse of :341-345 (the
+ * other two entries are zero).  out_wh: side of the square output.  plan may be NULL (no class left out, zero deltas).
+ * Integer min / max over 32 row chunks, then a finish launch: ws is hps_query_workspace(HPS_WS_SEG_BBOX, B) bytes.  An image without
+ * any such pixel is where the reference raises: its box becomes the whole frame and status[b] (int32, optional) is 1, else 0.
+ * part_counts (B, HPS_TRAIN_NUM_PART_COUNTS) int32, optional: zeroed, ready for hps_train_crop_augment. */
+int hps_seg_bbox_affine(const float* part, int64_t part_batch_stride, const int32_t* plan, int B, int H, int W, int out_wh,
+                        float orig_scale_factor, int32_t* ws, float* affine, float* theta, int32_t* status, int32_t* part_counts,
+                        hps_stream_t stream);
+
+/* Stages of hps_train_crop_augment, applied in this order per output pixel. */
+#define HPS_TRAIN_RESAMPLE 1          /* utils/image_utils.py:348-370: F.affine_grid + F.grid_sample(align_corners=False) by theta:
+                                         nearest (half to even; out of frame -> -1) for part, bilinear zero-padded for rgb.  Without
+                                         it the inputs are read pixel for pixel and every output is H x W (D is ignored) */
+#define HPS_TRAIN_COUNT 128           /* part_counts[b] += pixels of the sampled part per 14-part label (label_conversions.py:38-72) */
+#define HPS_TRAIN_COUNT14 256         /* the same for a plane that already holds 14-part labels */
+#define HPS_TRAIN_CROP_CLASS_MASK 4   /* classes of plan word 0 -> 0 (random_extreme_crop) */
+#define HPS_TRAIN_CLASS_MASK 2        /* classes of plan word 1 -> 0 (random_remove_bodyparts) */
+#define HPS_TRAIN_SEG_OCCLUDE 8       /* box, bottom, top, vertical ranges -> 0 */
+#define HPS_TRAIN_BACKGROUND 16       /* utils/image_utils.py:48-59: background where the part is 0 (-1, out of frame, keeps rgb) */
+#define HPS_TRAIN_RGB_OCCLUDE 32      /* the RGB ranges -> 0 */
+#define HPS_TRAIN_RGB_NOISE 64        /* times the channel factor, clamped at 1.0 from above only */
+#define HPS_TRAIN_ALL_STAGES 511
+
+/* train/train_poseMF_shapeGaussian_net.py:203-244 for the images, one pass: part and rgb (B,3,H,W) are sampled at theta (from
+ * hps_seg_bbox_affine), the part counts taken from the raw sample, the segmentation augmentations applied, the background
+ * (B,3,D,D) composited, the RGB augmentations applied; rgb_out (B,3,D,D), D the side of the square output.  Optional outputs (NULL
+ * skips): part_crop (B,D,D) the
+ * sampled plane, part_aug (B,D,D) the augmented one.  rgb may be NULL when only planes are wanted, part when only the RGB stages
+ * are.  part_counts is added to with integer adds (exact, order-free); the caller -- or hps_seg_bbox_affine -- zeroes it.
+ * Each lane writes four consecutive pixels of a row with one 16-byte store per plane where the address allows, else pixel by pixel. */
+int hps_train_crop_augment(const float* part, int64_t part_batch_stride, const float* rgb, const float* background,
+                           const float* theta, const int32_t* plan, int B, int H, int W, int D, int stages, float* rgb_out,
+                           int32_t* part_counts, float* part_crop, float* part_aug, hps_stream_t stream);
+
+/* Stages of hps_train_joints2d. */
+#define HPS_TRAIN_J_PRE_VIS 1    /* utils/joints2d_utils.py:13-26 on the given joints */
+#define HPS_TRAIN_J_AFFINE 2     /* utils/image_utils.py:359-363 */
+#define HPS_TRAIN_J_POST_VIS 4   /* :13-26 on the transformed joints */
+#define HPS_TRAIN_J_OCCLUDED 8   /* :29-45: joints 7-10, 13-16 need part_counts > pixel_count_threshold */
+#define HPS_TRAIN_J_SEG_AUG 16   /* augment_proxy_representation's joint side: swaps, deviations, removals, half-occlusion tests */
+#define HPS_TRAIN_J_RGB_AUG 32   /* augment_rgb's joint side */
+#define HPS_TRAIN_J_ALL_STAGES 63
+
+/* train/train_poseMF_shapeGaussian_net.py:181-183, :216-244 for the joints: joints2d (B,K,2) = (u, v), K = 17.  Follows
+ * hps_train_crop_augment in stream order when it reads part_counts.  vis_in (B,K) bytes, optional starting visibility.  Outputs, each
+ * optional: joints_target (B,K,2) the transformed joints, joints_input (B,K,2) the augmented ones, vis (B,K) float 0/1 and vis_u8
+ * (B,K) bytes 0/1 -- the final visibility, the loss's joints2D_vis and the heat-map mask alike. */
+int hps_train_joints2d(const float* joints2d, const uint8_t* vis_in, const float* affine, const int32_t* part_counts,
+                       const int32_t* plan, int B, int K, float img_wh, int pixel_count_threshold, int stages, float* joints_target,
+                       float* joints_input, float* vis, uint8_t* vis_u8, hps_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation metrics  
