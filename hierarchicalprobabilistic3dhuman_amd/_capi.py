@@ -152,6 +152,20 @@ class MfLossArgs(_c.Structure):
 MF_REDUCTION_MEAN, MF_REDUCTION_SUM = 0, 1
 ENC_RELAYOUT, ENC_CONV, ENC_MAXPOOL, ENC_AVGPOOL, ENC_CONV_WINOGRAD, ENC_STEM_SPLIT, ENC_STEM_WINOGRAD, ENC_RELAYOUT_GENERIC = 0, 1, 2, 3, 4, 5, 6, 7
 ENC_STEM_WINOGRAD_POOLED, ENC_STEM_WINOGRAD_POOLED_NCHW, ENC_CONV_DOWN = 8, 9, 10
+# op kind -> (entry point, the hps_enc_op fields that are its arguments in front of the stream): the switch of csrc/composite.hip
+ENC_ENTRY = {kind: (entry, tuple(fields.split())) for kind, entry, fields in (
+    (ENC_RELAYOUT, "hps_nchw_to_padded_nhwc", "x y B Cin H W opad"),
+    (ENC_RELAYOUT_GENERIC, "hps_nchw_to_padded_nhwc_generic", "x y B Cin Cout H W KW opad"),
+    (ENC_CONV, "hps_conv2d_bn_act_pad", "x w scale shift residual y B H W ipad Cin Cout KH KW stride pad opad relu row_mode variant ksplit splitk_ws"),
+    (ENC_CONV_DOWN, "hps_conv2d_bn_act_pad_down", "x w scale shift y w_down scale_down shift_down y_down B H W ipad Cin Cout KH KW stride pad opad "
+                                                  "relu variant ksplit splitk_ws"),
+    (ENC_CONV_WINOGRAD, "hps_conv3x3_winograd", "x w scale shift residual y B H W ipad Cin Cout opad relu splitk_ws"),
+    (ENC_STEM_SPLIT, "hps_stem_phase_split", "x y B Cin H W"),
+    (ENC_STEM_WINOGRAD, "hps_stem_winograd", "x w scale shift y B H W opad relu"),
+    (ENC_STEM_WINOGRAD_POOLED, "hps_stem_winograd_pooled", "x w scale shift y splitk_ws B H W opad relu"),
+    (ENC_STEM_WINOGRAD_POOLED_NCHW, "hps_stem_winograd_pooled_nchw", "x w scale shift y splitk_ws B H W opad relu"),
+    (ENC_MAXPOOL, "hps_maxpool3x3s2_pad", "x y B H W Cin opad"),
+    (ENC_AVGPOOL, "hps_global_avgpool_pad", "x y B H W Cin ipad"))}
 SVD_HOST, SVD_DEVICE, SVD_DEVICE_FMA = 0, 1, 2
 SVD_ROUNDING_REFERENCE, SVD_ROUNDING_FMA = 0, 1
 HEAD_WIDE_WORKGROUPS = 0x100
@@ -310,6 +324,24 @@ def call(name, *args):
     if rc != 0:
         msg = lib.hps_last_error()
         raise HpsError("%s failed (code %d): %s" % (name, rc, msg.decode() if msg else ""))
+
+
+def issue_enc_op(op):
+    """One hps_enc_op through its own public entry point (ENC_ENTRY), on the current stream."""
+    entry, fields = ENC_ENTRY[op.kind]
+    call(entry, *[getattr(op, f) for f in fields], stream())
+
+
+def run_enc_ops(ops, first, count, composite=True):
+    """ops[first:first + count] of an EncOp array on the current stream: one hps_encoder_run call across the C ABI, or
+    (``composite`` False, the cross-check of csrc/composite.hip's argument mapping) op by op through the public entry points."""
+    if not composite:
+        for i in range(first, first + count):
+            issue_enc_op(ops[i])
+    elif first == 0:
+        call("hps_encoder_run", ops, count, stream())
+    else:
+        call("hps_encoder_run", _c.cast(_c.byref(ops, first * _c.sizeof(EncOp)), _c.POINTER(EncOp)), count, stream())
 
 
 WS_CONV_SPLITK, WS_SMPL_MP, WS_SMPL_XT, WS_SMPL_A, WS_SMPL_VPOSED, WS_HEAD_F, WS_HEAD_USV = range(7)

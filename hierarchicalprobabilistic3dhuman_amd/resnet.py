@@ -7,6 +7,13 @@ the reference); their own forward is never used.  By default BatchNorm uses runn
 (the reference runs the encoder under ``model.eval()``, predict/...:55) and is fused, together with the
 residual add and ReLU, into the convolution epilogue; ``.train()`` is refused unless ``set_batchnorm_training(True)`` opted in.
 
+One plan for every forward.  ``ResNet._plan`` is the only walk over the network in the forward direction: for a frame set it returns
+the ordered steps, each one launch as a ``_capi.EncOp`` (``_ConvBN.op`` is the only place that picks a convolution's kernel: Winograd
+or direct, row mode, split K, tile) or, behind the convolution of a training-mode layer, a ``_BNStep``.  The eval list is the frame
+set's ``ops`` array and goes to the device as one ``hps_encoder_run`` call, or -- ``composite = False``, the tests' cross-check of
+csrc/composite.hip -- op by op through the public entry points (``_capi.run_enc_ops``); the training forward issues its cached list
+step by step.  ``_ConvBN.padded`` / ``padded_with_down`` build the same op and issue it alone.
+
 Fine-tuning with frozen statistics.  With grad mode on and the input or an encoder parameter requiring grad, ``ResNet.forward`` runs
 inside a torch.autograd.Function: its forward issues exactly the launches of a no_grad call (same bits, in every kernel mode) and
 saves only the input and the parameters.  The backward (csrc/conv_backward.hip) evaluates the encoder once more into a frame set of
@@ -25,6 +32,8 @@ the batch size holds for eval layers only.  From the first differentiable forwar
 the module compares its parameters' ``_version`` counters with those recorded by ``prepare()`` and refolds the filters after an
 optimiser step, as PoseMFShapeGaussianNet does for the head.
 """
+import collections
+
 import torch
 from torch import nn
 
@@ -154,36 +163,57 @@ class _ConvBN:
             return 0
         return int(_capi.load(dev=_capi._use_dev).hps_conv3x3_winograd_workspace(B, H, W, self.cin_p, self.cout))
 
-    def padded(self, xp, ipad, out, opad, residual=None, relu=True, ws=None, ident=False):
-        """Halo-padded generation (csrc/conv_pad.hip): xp (B, H+2*ipad, W+2*ipad, Cin) with a zero halo; writes the interior
-        of ``out`` (B, Ho+2*opad, Wo+2*opad, Cout) -- the caller owns the halo (zeroed once); ``residual`` has out's frame.
-        ``ident``: identity scale / shift instead of the folded BatchNorm (the raw map of a training-mode layer)."""
+    def _route(self, B, H, W, ipad, down=None):
+        """(op kind, split-K slices, scratch bytes) of this layer's launch on (B, H, W) maps with an ``ipad`` halo, ``down`` riding in it:
+        Winograd or the direct kernel, row mode, the K slices.  The one place that decides; op() and the frame sets' scratch follow it."""
+        if down is not None:
+            assert self.folds_down(down, H, W, ipad)
+        elif self.winograd_ok(H, W, ipad):
+            return _capi.ENC_CONV_WINOGRAD, 1, self.wino_workspace_bytes(B, H, W, ipad)
+        Ho, Wo = self.out_hw(H, W)
+        ksplit = 1 if self.wn is None else (self.ksplit if self.ksplit > 0 else self._auto_ksplit(Ho * Wo))
+        return (_capi.ENC_CONV if down is None else _capi.ENC_CONV_DOWN, ksplit,
+                _capi.query_workspace(_capi.WS_CONV_SPLITK, ksplit, B * Ho * Wo, self.cout))
+
+    def workspace_bytes(self, B, H, W, ipad=1, down=None):
+        """Bytes of scratch this layer's launch needs on (B, H, W) maps: split-K slices or the Winograd kernel's K-slice buffer (0: none)."""
+        return self._route(B, H, W, ipad, down)[2]
+
+    def op(self, xp, ipad, out, opad, residual=None, relu=True, ws=None, ident=False, down=None, out_down=None, ident_down=False):
+        """This layer on these frames as ONE hps_enc_op; nothing is launched.  Halo-padded generation (csrc/conv_pad.hip, conv_wino.hip):
+        xp (B, H+2*ipad, W+2*ipad, Cin) with a zero halo; the launch writes the interior of ``out`` (B, Ho+2*opad, Wo+2*opad, Cout) --
+        the caller owns the halo (zeroed once); ``residual`` has out's frame; ``ws`` holds workspace_bytes().  ``ident``: identity
+        scale / shift instead of the folded BatchNorm (the raw map of a training-mode layer).  ``down`` (see folds_down): the block's
+        1x1 down-sample writes ``out_down`` (no ReLU) in the same launch, ``ident_down`` as ident; identical bits."""
         B, Hp, Wp, C = xp.shape
         H, W = Hp - 2 * ipad, Wp - 2 * ipad
-        scale, shift = self.ident if ident else (self.scale, self.shift)
-        if self.winograd_ok(H, W, ipad):
-            assert C == self.cin_p and tuple(out.shape) == (B, H + 2 * opad, W + 2 * opad, self.cout)
-            P = _capi.ptr
-            need = self.wino_workspace_bytes(B, H, W, ipad)
-            if need and (ws is None or ws.numel() * 4 < need):
-                ws = torch.empty(need // 4, device=xp.device, dtype=torch.float32)
-            _capi.call("hps_conv3x3_winograd", P(xp), P(self.wino_u), P(scale), P(shift),
-                       P(residual) if residual is not None else None, P(out), B, H, W, ipad, C, self.cout, opad, 1 if relu else 0,
-                       P(ws) if need else None, _capi.stream())
-            return out
-        row_mode = self.wn is None
-        assert C == (self.row_c if row_mode else self.cin_p)
-        Ho = (H + 2 * self.pad - self.kh) // self.stride + 1
-        Wo = (W + 2 * self.pad - self.kw) // self.stride + 1
-        assert tuple(out.shape) == (B, Ho + 2 * opad, Wo + 2 * opad, self.cout)
-        ksplit = 1 if row_mode else (self.ksplit if self.ksplit > 0 else self._auto_ksplit(Ho * Wo))
-        if ksplit > 1 and ws is None:
-            ws = torch.empty(ksplit, B * Ho * Wo, self.cout, device=xp.device, dtype=torch.float32)
+        kind, ksplit, need = self._route(B, H, W, ipad, down)
+        wino, row_mode = kind == _capi.ENC_CONV_WINOGRAD, self.wn is None
+        Ho, Wo = self.out_hw(H, W)
+        assert C == (self.row_c if row_mode else self.cin_p) and tuple(out.shape) == (B, Ho + 2 * opad, Wo + 2 * opad, self.cout)
+        assert need == 0 or (ws is not None and ws.numel() * 4 >= need)
         P = _capi.ptr
-        _capi.call("hps_conv2d_bn_act_pad", P(xp), P(self.wrow if row_mode else self.wn), P(scale), P(shift),
-                   P(residual) if residual is not None else None, P(out), B, H, W, ipad, C, self.cout, self.kh, self.kw,
-                   self.stride, self.pad, opad, 1 if relu else 0, 1 if row_mode else 0, self._tile_variant(ksplit),
-                   ksplit, P(ws) if ksplit > 1 else None, _capi.stream())
+        scale, shift = self.ident if ident else (self.scale, self.shift)
+        op = _capi.EncOp(kind=kind, x=P(xp), w=P(self.wino_u if wino else self.wrow if row_mode else self.wn), scale=P(scale), shift=P(shift),
+                         residual=P(residual), y=P(out), splitk_ws=P(ws) if need else None, B=B, H=H, W=W, ipad=ipad, Cin=C, Cout=self.cout,
+                         KH=self.kh, KW=self.kw, stride=self.stride, pad=self.pad, opad=opad, relu=1 if relu else 0,
+                         row_mode=1 if row_mode else 0, variant=0 if wino else self._tile_variant(ksplit), ksplit=ksplit)
+        if down is not None:
+            assert residual is None and out_down.shape == out.shape
+            scale, shift = down.ident if ident_down else (down.scale, down.shift)
+            op.w_down, op.scale_down, op.shift_down, op.y_down = P(down.wn), P(scale), P(shift), P(out_down)
+        return op
+
+    def _scratch(self, xp, ipad, ws, down=None):
+        """``ws`` where it holds what the launch on ``xp`` needs, else a buffer of its own (None: none needed)."""
+        need = self.workspace_bytes(xp.shape[0], xp.shape[1] - 2 * ipad, xp.shape[2] - 2 * ipad, ipad, down)
+        if need == 0 or (ws is not None and ws.numel() * 4 >= need):
+            return ws
+        return torch.empty(need // 4, device=xp.device, dtype=torch.float32)
+
+    def padded(self, xp, ipad, out, opad, residual=None, relu=True, ws=None, ident=False):
+        """Launch op(...) through its own entry point, with scratch of its own when the caller gave none (or too little)."""
+        _capi.issue_enc_op(self.op(xp, ipad, out, opad, residual, relu, self._scratch(xp, ipad, ws), ident))
         return out
 
     def folds_down(self, down, H, W, ipad):
@@ -194,66 +224,11 @@ class _ConvBN:
                 and self.kh == self.kw and self.kh % 2 == 1 and self.pad == self.kh // 2 and down.kh == down.kw == 1 and down.pad == 0
                 and down.stride == self.stride and down.cout == self.cout and down.cin_p == self.cin_p and self.cout >= 128)
 
-    def _down_variant(self, ksplit):
-        """Tile choice of the fused launch: the main convolution's; 0 (automatic) resolves to 128 x 128 or 64 x 64 tiles for Cout >= 128."""
-        return self._tile_variant(ksplit)
-
     def padded_with_down(self, xp, ipad, out, opad, down, out_down, ws=None, relu=True, ident=(False, False)):
         """padded(xp -> out, relu) and down.padded(xp -> out_down, no relu) in ONE launch (see folds_down); identical bits.
-        ``ident``: identity scale / shift for (this convolution, the down-sample) -- see padded."""
-        B, Hp, Wp, C = xp.shape
-        H, W = Hp - 2 * ipad, Wp - 2 * ipad
-        assert self.folds_down(down, H, W, ipad) and C == self.cin_p
-        Ho, Wo = self.out_hw(H, W)
-        assert tuple(out.shape) == tuple(out_down.shape) == (B, Ho + 2 * opad, Wo + 2 * opad, self.cout)
-        ksplit = self.ksplit if self.ksplit > 0 else self._auto_ksplit(Ho * Wo)
-        if ksplit > 1 and ws is None:
-            ws = torch.empty(ksplit, B * Ho * Wo, self.cout, device=xp.device, dtype=torch.float32)
-        P = _capi.ptr
-        sc, sh = self.ident if ident[0] else (self.scale, self.shift)
-        scd, shd = down.ident if ident[1] else (down.scale, down.shift)
-        _capi.call("hps_conv2d_bn_act_pad_down", P(xp), P(self.wn), P(sc), P(sh), P(out), P(down.wn), P(scd),
-                   P(shd), P(out_down), B, H, W, ipad, C, self.cout, self.kh, self.kw, self.stride, self.pad, opad, 1 if relu else 0,
-                   self._down_variant(ksplit), ksplit, P(ws) if ksplit > 1 else None, _capi.stream())
+        ``ident``: identity scale / shift for (this convolution, the down-sample) -- see op."""
+        _capi.issue_enc_op(self.op(xp, ipad, out, opad, None, relu, self._scratch(xp, ipad, ws, down), ident[0], down, out_down, ident[1]))
         return out, out_down
-
-    def enc_op_with_down(self, xp, ipad, out, opad, down, out_down, ws=None):
-        """The hps_enc_op of ``padded_with_down(...)`` for hps_encoder_run."""
-        B, Hp, Wp, C = xp.shape
-        H, W = Hp - 2 * ipad, Wp - 2 * ipad
-        assert self.folds_down(down, H, W, ipad) and C == self.cin_p
-        Ho, Wo = self.out_hw(H, W)
-        assert tuple(out.shape) == tuple(out_down.shape) == (B, Ho + 2 * opad, Wo + 2 * opad, self.cout)
-        ksplit = self.ksplit if self.ksplit > 0 else self._auto_ksplit(Ho * Wo)
-        assert ksplit == 1 or ws is not None
-        return _capi.EncOp(kind=_capi.ENC_CONV_DOWN, x=xp.data_ptr(), w=self.wn.data_ptr(), scale=self.scale.data_ptr(),
-                           shift=self.shift.data_ptr(), residual=None, y=out.data_ptr(), splitk_ws=ws.data_ptr() if ksplit > 1 else None,
-                           B=B, H=H, W=W, ipad=ipad, Cin=C, Cout=self.cout, KH=self.kh, KW=self.kw, stride=self.stride, pad=self.pad,
-                           opad=opad, relu=1, row_mode=0, variant=self._down_variant(ksplit), ksplit=ksplit, w_down=down.wn.data_ptr(),
-                           scale_down=down.scale.data_ptr(), shift_down=down.shift.data_ptr(), y_down=out_down.data_ptr())
-
-    def enc_op(self, xp, ipad, out, opad, residual=None, relu=True, ws=None):
-        """The hps_enc_op of ``padded(...)`` for hps_encoder_run (same arguments, nothing is launched)."""
-        B, Hp, Wp, C = xp.shape
-        H, W = Hp - 2 * ipad, Wp - 2 * ipad
-        dp = lambda t: t.data_ptr() if t is not None else None
-        if self.winograd_ok(H, W, ipad):
-            assert tuple(out.shape) == (B, H + 2 * opad, W + 2 * opad, self.cout) and C == self.cin_p
-            need = self.wino_workspace_bytes(B, H, W, ipad)
-            assert need == 0 or (ws is not None and ws.numel() * 4 >= need)
-            return _capi.EncOp(kind=_capi.ENC_CONV_WINOGRAD, x=dp(xp), w=dp(self.wino_u), scale=dp(self.scale), shift=dp(self.shift),
-                               residual=dp(residual), y=dp(out), splitk_ws=dp(ws) if need else None, B=B, H=H, W=W, ipad=ipad,
-                               Cin=C, Cout=self.cout, KH=3, KW=3, stride=1, pad=1, opad=opad, relu=1 if relu else 0, ksplit=1)
-        row_mode = self.wn is None
-        Ho, Wo = self.out_hw(H, W)
-        assert tuple(out.shape) == (B, Ho + 2 * opad, Wo + 2 * opad, self.cout) and C == (self.row_c if row_mode else self.cin_p)
-        ksplit = 1 if row_mode else (self.ksplit if self.ksplit > 0 else self._auto_ksplit(Ho * Wo))
-        assert ksplit == 1 or ws is not None
-        return _capi.EncOp(kind=_capi.ENC_CONV, x=dp(xp), w=dp(self.wrow if row_mode else self.wn), scale=dp(self.scale),
-                           shift=dp(self.shift), residual=dp(residual), y=dp(out), splitk_ws=dp(ws) if ksplit > 1 else None,
-                           B=B, H=H, W=W, ipad=ipad, Cin=C, Cout=self.cout, KH=self.kh, KW=self.kw, stride=self.stride,
-                           pad=self.pad, opad=opad, relu=1 if relu else 0, row_mode=1 if row_mode else 0,
-                           variant=self._tile_variant(ksplit), ksplit=ksplit)
 
     def out_hw(self, H, W):
         return (H + 2 * self.pad - self.kh) // self.stride + 1, (W + 2 * self.pad - self.kw) // self.stride + 1
@@ -282,6 +257,11 @@ def _stem_winograd_filters(w):
     hi = u[:, 16:].reshape(81, 2, 2, 32).permute(0, 2, 1, 3).reshape(81, 2, 64)          # p, half, [c - 16][co % 32]
     packed = torch.cat([lo, hi], 2).reshape(-1)
     return torch.cat([packed, torch.zeros(256, dtype=torch.float64)]).float()
+
+
+# A training-mode BatchNorm behind its layer's convolution (ResNet._plan): the raw frame -> batch statistics -> fold -> out = act(raw
+# scale + shift [+ residual]) on (h, w) maps inside a ``pad`` halo (csrc/bn_train.hip)
+_BNStep = collections.namedtuple("_BNStep", "name channels raw out residual relu h w pad")
 
 
 class FilledStemFrames:
@@ -347,7 +327,7 @@ class _EncoderFunction(torch.autograd.Function):
 
 
 class BasicBlock(nn.Module):
-    """models/resnet.py:40-78 (parameter container; executed by ResNet._run_block)."""
+    """models/resnet.py:40-78 (parameter container; executed as the steps of ResNet._plan)."""
     expansion = 1
 
     def __init__(self, inplanes, planes, stride=1, downsample=None):
@@ -481,7 +461,8 @@ class ResNet(DeviceStateModule):
         stem_wino = stem.stem_winograd_ok(C, H, W)
         fused_pool = bool(stem_wino and self.fused_pool)
         from_nchw = bool(fused_pool and self.stem_reads_nchw and not frames)
-        key = (B, C, H, W, _capi.stream().value, from_nchw)          # (switches and layer modes: one device state each)
+        # (switches and layer modes: one device state each; layer fields edited by hand on a prepared layer: a frame set of their own)
+        key = (B, C, H, W, _capi.stream().value, from_nchw, self._variant_state(prep))
         return self._derived("frames", key, lambda: self._new_frame_set(prep, B, C, H, W, device, stem_wino, fused_pool, from_nchw),
                              limit=6)                # a handful of batch shapes / streams at most
 
@@ -507,7 +488,6 @@ class ResNet(DeviceStateModule):
             fs["side"] = torch.empty(int(_capi.load(dev=_capi._use_dev).hps_stem_pool_side_bytes(B, H, W)) // 4, device=device, dtype=torch.float32)
         else:
             fs["stem"] = torch.empty(B, h, w, stem.cout, device=device, dtype=torch.float32)
-        h_stem, w_stem = h, w
         h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
         fs["pool"] = z(B, h + 2, w + 2, stem.cout)
         fs["blocks"] = []
@@ -516,51 +496,75 @@ class ResNet(DeviceStateModule):
             h, w = c1.out_hw(h, w)
             ent = {"c1": z(B, h + 2, w + 2, c1.cout), "c2": z(B, h + 2, w + 2, c2.cout),
                    "down": z(B, h + 2, w + 2, down.cout) if down is not None else None}
-            ks = max(c._auto_ksplit(h * w) if c.ksplit == 0 else c.ksplit for c in (c1, c2))
-            ws_bytes = max(_capi.query_workspace(_capi.WS_CONV_SPLITK, ks, B * h * w, c1.cout),
-                           c1.wino_workspace_bytes(B, hin, win), c2.wino_workspace_bytes(B, h, w))
+            folded = self.fold_downsample and c1.folds_down(down, hin, win, 1)
+            ws_bytes = max(c1.workspace_bytes(B, hin, win, 1, down if folded else None), c2.workspace_bytes(B, h, w),
+                           down.workspace_bytes(B, hin, win) if down is not None else 0)
             ent["ws"] = torch.empty(ws_bytes // 4, device=device, dtype=torch.float32) if ws_bytes else None
             fs["blocks"].append(ent)
         fs["hw"] = (h, w)
         # the launch list of hps_encoder_run: every pointer but the input image and the feature output is fixed
-        if from_nchw:
-            first = [_capi.EncOp(kind=_capi.ENC_STEM_WINOGRAD_POOLED_NCHW, x=None, w=stem.stem_u.data_ptr(), scale=stem.scale.data_ptr(),
-                                 shift=stem.shift.data_ptr(), y=fs["pool"].data_ptr(), splitk_ws=fs["side"].data_ptr(), B=B, H=H, W=W, Cin=C,
-                                 Cout=stem.cout, KH=7, KW=7, stride=2, pad=3, opad=1, relu=1)]
-        elif fused_pool:
-            first = [_capi.EncOp(kind=_capi.ENC_STEM_SPLIT, x=None, y=fs["in"].data_ptr(), B=B, Cin=C, H=H, W=W),
-                     _capi.EncOp(kind=_capi.ENC_STEM_WINOGRAD_POOLED, x=fs["in"].data_ptr(), w=stem.stem_u.data_ptr(), scale=stem.scale.data_ptr(),
-                                 shift=stem.shift.data_ptr(), y=fs["pool"].data_ptr(), splitk_ws=fs["side"].data_ptr(), B=B, H=H, W=W, Cin=C,
-                                 Cout=stem.cout, KH=7, KW=7, stride=2, pad=3, opad=1, relu=1)]
-        elif stem_wino:
-            first = [_capi.EncOp(kind=_capi.ENC_STEM_SPLIT, x=None, y=fs["in"].data_ptr(), B=B, Cin=C, H=H, W=W),
-                     _capi.EncOp(kind=_capi.ENC_STEM_WINOGRAD, x=fs["in"].data_ptr(), w=stem.stem_u.data_ptr(), scale=stem.scale.data_ptr(),
-                                 shift=stem.shift.data_ptr(), y=fs["stem"].data_ptr(), B=B, H=H, W=W, Cin=C, Cout=stem.cout, KH=7, KW=7,
-                                 stride=2, pad=3, opad=0, relu=1)]
-        else:
-            relayout = (_capi.EncOp(kind=_capi.ENC_RELAYOUT_GENERIC, x=None, y=fs["in"].data_ptr(), B=B, Cin=C, Cout=cf, H=H, W=W, KW=wf, opad=3)
-                        if generic else _capi.EncOp(kind=_capi.ENC_RELAYOUT, x=None, y=fs["in"].data_ptr(), B=B, Cin=C, H=H, W=W, opad=3))
-            first = [relayout, stem.enc_op(fs["in"], 3, fs["stem"], 0, relu=True)]
-        ops = first if fused_pool else first + [
-               _capi.EncOp(kind=_capi.ENC_MAXPOOL, x=fs["stem"].data_ptr(), y=fs["pool"].data_ptr(), B=B, H=h_stem, W=w_stem, Cin=stem.cout, opad=1)]
-        y = fs["pool"]
-        for (c1, c2, down), ent in zip(prep["blocks"], fs["blocks"]):      # BasicBlock.forward :62-78
-            identity = y
-            hin, win = y.shape[1] - 2, y.shape[2] - 2
-            if down is not None and self.fold_downsample and c1.folds_down(down, hin, win, 1):
-                ops.append(c1.enc_op_with_down(y, 1, ent["c1"], 1, down, ent["down"], ws=ent["ws"]))
-                identity = ent["down"]
-            else:
-                if down is not None:
-                    ops.append(down.enc_op(y, 1, ent["down"], 1, relu=False))
-                    identity = ent["down"]
-                ops.append(c1.enc_op(y, 1, ent["c1"], 1, relu=True, ws=ent["ws"]))
-            ops.append(c2.enc_op(ent["c1"], 1, ent["c2"], 1, residual=identity, relu=True, ws=ent["ws"]))
-            y = ent["c2"]
-        ops.append(_capi.EncOp(kind=_capi.ENC_AVGPOOL, x=y.data_ptr(), y=None, B=B, H=h, W=w, Cin=y.shape[3], ipad=1))
+        ops = self._plan(prep, fs, (B, C, H, W))
         fs["ops"] = (_capi.EncOp * len(ops))(*ops)
-        fs["variants"] = self._variant_state(prep)
         return fs
+
+    def _plan(self, prep, fs, shape, flags=None):
+        """The forward on the frame set ``fs`` as the ordered list of its steps -- THE walk over the network (models/resnet.py:202-217,
+        BasicBlock.forward :62-78): stem, max pool, blocks, average pool.  A step is one launch (a _capi.EncOp; the first one's input and
+        the last one's output pointer are the caller's, set per forward) or, with ``flags`` (_train_flags()) naming a layer's BatchNorm as
+        training, the _BNStep behind that layer's convolution, which then writes the raw frame: identity scale / shift, no ReLU, no
+        residual.  Order within a block: the down-sample (its own launch or riding in c1's), c1, the BatchNorm of .down, of .c1, then
+        c2 and its BatchNorm (with the residual and the block's ReLU)."""
+        B, C, H, W = shape
+        E, P = _capi.EncOp, _capi.ptr
+        stem, steps = prep["stem"], []
+        train = lambda name: flags is not None and flags[name]
+        assert flags is None or not fs["fused_pool"]              # the statistics are needed between the convolution and the pool
+        target = lambda name, frame: fs["raw"][name] if train(name) else frame       # where a layer's convolution writes
+
+        def bn(name, cb, out, pad, residual, relu):
+            if train(name):
+                steps.append(_BNStep(name, cb.cout, fs["raw"][name], out, residual, relu, out.shape[1] - 2 * pad, out.shape[2] - 2 * pad, pad))
+
+        ts = train("stem")
+        if fs["stem_wino"]:
+            fused = fs["fused_pool"]
+            kind = _capi.ENC_STEM_WINOGRAD_POOLED_NCHW if fs["from_nchw"] else _capi.ENC_STEM_WINOGRAD_POOLED if fused else _capi.ENC_STEM_WINOGRAD
+            if not fs["from_nchw"]:
+                steps.append(E(kind=_capi.ENC_STEM_SPLIT, x=None, y=P(fs["in"]), B=B, Cin=C, H=H, W=W))
+            scale, shift = stem.ident if ts else (stem.scale, stem.shift)
+            steps.append(E(kind=kind, x=P(fs["in"]), w=P(stem.stem_u), scale=P(scale), shift=P(shift),
+                           y=P(fs["pool"] if fused else target("stem", fs["stem"])), splitk_ws=P(fs["side"]) if fused else None, B=B, H=H, W=W,
+                           Cin=C, Cout=stem.cout, KH=7, KW=7, stride=2, pad=3, opad=1 if fused else 0, relu=0 if ts else 1))
+        else:
+            if fs["generic_in"] is not None:
+                _, cf, _, wf = fs["generic_in"]
+                steps.append(E(kind=_capi.ENC_RELAYOUT_GENERIC, x=None, y=P(fs["in"]), B=B, Cin=C, Cout=cf, H=H, W=W, KW=wf, opad=3))
+            else:
+                steps.append(E(kind=_capi.ENC_RELAYOUT, x=None, y=P(fs["in"]), B=B, Cin=C, H=H, W=W, opad=3))
+            steps.append(stem.op(fs["in"], 3, target("stem", fs["stem"]), 0, relu=not ts, ident=ts))         # conv1 + bn1 + relu
+        if not fs["fused_pool"]:
+            y = fs["stem"]
+            bn("stem", stem, y, 0, None, True)
+            steps.append(E(kind=_capi.ENC_MAXPOOL, x=P(y), y=P(fs["pool"]), B=B, H=y.shape[1], W=y.shape[2], Cin=stem.cout, opad=1))
+        y = fs["pool"]
+        for name, (c1, c2, down), ent in zip(self._block_names(), prep["blocks"], fs["blocks"]):
+            n1, n2, nd = name + ".c1", name + ".c2", name + ".down"
+            t1, t2, td = train(n1), train(n2), down is not None and train(nd)
+            identity = y if down is None else ent["down"]
+            folded = self.fold_downsample and c1.folds_down(down, y.shape[1] - 2, y.shape[2] - 2, 1)
+            if down is not None and not folded:
+                steps.append(down.op(y, 1, target(nd, ent["down"]), 1, relu=False, ws=ent["ws"], ident=td))
+            steps.append(c1.op(y, 1, target(n1, ent["c1"]), 1, relu=not t1, ws=ent["ws"], ident=t1,
+                               down=down if folded else None, out_down=target(nd, ent["down"]) if folded else None, ident_down=td))
+            if down is not None:
+                bn(nd, down, ent["down"], 1, None, False)
+            bn(n1, c1, ent["c1"], 1, None, True)
+            steps.append(c2.op(ent["c1"], 1, target(n2, ent["c2"]), 1, residual=None if t2 else identity, relu=not t2, ws=ent["ws"], ident=t2))
+            bn(n2, c2, ent["c2"], 1, identity, True)
+            y = ent["c2"]
+        h, w = fs["hw"]
+        steps.append(E(kind=_capi.ENC_AVGPOOL, x=P(y), y=None, B=B, H=h, W=w, Cin=y.shape[3], ipad=1))
+        return steps
 
     @staticmethod
     def _variant_state(prep):
@@ -586,8 +590,6 @@ class ResNet(DeviceStateModule):
         convolutions wait).  ``fs``: run on this frame set instead of the module's own for the shape (the backward's recompute)."""
         filled = isinstance(x, FilledStemFrames)
         B, C, H, W = x.shape
-        s = _capi.stream()
-        P = _capi.ptr
         if fs is None:
             fs = self._frame_set(prep, B, C, H, W, x.device, frames=filled)
         if filled and (not fs["stem_wino"] or fs["in"].data_ptr() != x.frames.data_ptr()):
@@ -600,74 +602,25 @@ class ResNet(DeviceStateModule):
             fs["generation"] += 1                        # consumed: a second forward with the same object would read whatever the frames hold then
         elif fs.get("in") is not None and fs["stem_wino"]:
             fs["generation"] = fs.get("generation", 0) + 1      # the phase split below overwrites the frames
-        if self.composite and fs["variants"] == self._variant_state(prep):
-            # one call across the C ABI for the whole encoder (csrc/composite.hip); two when the list is gated
-            feats = torch.empty(B, fs["blocks"][-1]["c2"].shape[3], device=x.device, dtype=torch.float32)
-            ops = fs["ops"]
-            ops[len(ops) - 1].y = feats.data_ptr()
-            if filled:                                   # the caller fills the phase frames: the list starts at the stem convolution
-                import ctypes
-                if gate is not None:
-                    gate()
-                x.run_fill()
-                rest = ctypes.cast(ctypes.byref(ops, ctypes.sizeof(_capi.EncOp)), ctypes.POINTER(_capi.EncOp))
-                _capi.call("hps_encoder_run", rest, len(ops) - 1, s)
-                return feats
-            ops[0].x = x.data_ptr()
-            if fs["from_nchw"] and gate is not None:     # no relayout in front of the first convolution: the whole list waits
-                gate()
-                gate = None
-            if gate is None:
-                _capi.call("hps_encoder_run", ops, len(ops), s)
-            else:
-                import ctypes
-                _capi.call("hps_encoder_run", ops, 1, s)
-                gate()
-                rest = ctypes.cast(ctypes.byref(ops, ctypes.sizeof(_capi.EncOp)), ctypes.POINTER(_capi.EncOp))
-                _capi.call("hps_encoder_run", rest, len(ops) - 1, s)
-            return feats
-        stem = prep["stem"]
-        if fs["from_nchw"]:
-            if gate is not None:
-                gate()
-            y = None
-            _capi.call("hps_stem_winograd_pooled_nchw", P(x), P(stem.stem_u), P(stem.scale), P(stem.shift), P(fs["pool"]), P(fs["side"]),
-                       B, H, W, 1, 1, s)
-        elif fs["stem_wino"]:
-            if not filled:
-                _capi.call("hps_stem_phase_split", P(x), P(fs["in"]), B, C, H, W, s)
-            if gate is not None:
-                gate()
-            if filled:
-                x.run_fill()
-            y = fs["stem"]
-            if fs["fused_pool"]:
-                _capi.call("hps_stem_winograd_pooled", P(fs["in"]), P(stem.stem_u), P(stem.scale), P(stem.shift), P(fs["pool"]), P(fs["side"]),
-                           B, H, W, 1, 1, s)
-            else:
-                _capi.call("hps_stem_winograd", P(fs["in"]), P(stem.stem_u), P(stem.scale), P(stem.shift), P(y), B, H, W, 0, 1, s)
+        # the frame set's launch list (_plan): one call across the C ABI for the whole encoder (csrc/composite.hip), two when it is
+        # gated; ``composite`` False: the same list launch by launch through the public entry points (the cross-check of the tests)
+        feats = torch.empty(B, fs["blocks"][-1]["c2"].shape[3], device=x.device, dtype=torch.float32)
+        ops = fs["ops"]
+        n = len(ops)
+        ops[n - 1].y = feats.data_ptr()
+        if filled:                                       # the caller fills the phase frames: the list starts at the stem convolution
+            first = 1
         else:
-            if fs["generic_in"] is not None:
-                _, cf, _, wf = fs["generic_in"]
-                _capi.call("hps_nchw_to_padded_nhwc_generic", P(x), P(fs["in"]), B, C, cf, H, W, wf, 3, s)
-            else:
-                _capi.call("hps_nchw_to_padded_nhwc", P(x), P(fs["in"]), B, C, H, W, 3, s)
-            if gate is not None:
-                gate()
-            y = stem.padded(fs["in"], 3, fs["stem"], 0, relu=True)         # conv1 + bn1 + relu
-        if not fs["fused_pool"]:
-            _capi.call("hps_maxpool3x3s2_pad", P(y), P(fs["pool"]), B, y.shape[1], y.shape[2], y.shape[3], 1, s)
-        y = fs["pool"]
-        for (c1, c2, down), ent in zip(prep["blocks"], fs["blocks"]):      # BasicBlock.forward :62-78
-            if down is not None and self.fold_downsample and c1.folds_down(down, y.shape[1] - 2, y.shape[2] - 2, 1):
-                out, identity = c1.padded_with_down(y, 1, ent["c1"], 1, down, ent["down"], ws=ent["ws"])
-            else:
-                identity = down.padded(y, 1, ent["down"], 1, relu=False) if down is not None else y
-                out = c1.padded(y, 1, ent["c1"], 1, relu=True, ws=ent["ws"])
-            y = c2.padded(out, 1, ent["c2"], 1, residual=identity, relu=True, ws=ent["ws"])
-        h, w = fs["hw"]
-        feats = torch.empty(B, y.shape[3], device=x.device, dtype=torch.float32)
-        _capi.call("hps_global_avgpool_pad", P(y), P(feats), B, h, w, y.shape[3], 1, s)
+            ops[0].x = x.data_ptr()
+            # op 0 is the input relayout / phase split in front of the gate -- unless the stem reads the NCHW input itself: the whole list waits
+            first = 0 if gate is None or fs["from_nchw"] else 1
+            if first:
+                _capi.run_enc_ops(ops, 0, 1, self.composite)
+        if gate is not None:
+            gate()
+        if filled:
+            x.run_fill()
+        _capi.run_enc_ops(ops, first, n - first, self.composite)
         return feats
 
     def forward(self, x, _gate=None):
@@ -759,34 +712,36 @@ class ResNet(DeviceStateModule):
     def _train_frames(self, prep, B, C, H, W, device, flags):
         """The training forward's frame set for a batch shape on the current stream: as the backward's activation set (unfused stem
         and pool: the statistics are needed between the convolution and the pool) plus one raw frame per training layer."""
-        key = (B, C, H, W, _capi.stream().value, tuple(flags.values()))
+        key = (B, C, H, W, _capi.stream().value, tuple(flags.values()), self._variant_state(prep))
         return self._derived("train_frames", key, lambda: self._add_raw_frames(
-            self._new_frame_set(prep, B, C, H, W, device, prep["stem"].stem_winograd_ok(C, H, W), False, False), flags), limit=4)
+            prep, self._new_frame_set(prep, B, C, H, W, device, prep["stem"].stem_winograd_ok(C, H, W), False, False), (B, C, H, W), flags), limit=4)
 
-    def _add_raw_frames(self, fs, flags):
+    def _add_raw_frames(self, prep, fs, shape, flags):
+        """... and with them the training forward's steps, ``fs["plan"]`` (_plan with ``flags``: every pointer in it is fixed)."""
         raw = {"stem": torch.empty_like(fs["stem"]) if flags["stem"] else None}
         for name, ent in zip(self._block_names(), fs["blocks"]):
             for k in ("c1", "c2", "down"):
                 raw[name + "." + k] = torch.empty_like(ent[k]) if ent[k] is not None and flags[name + "." + k] else None
         fs["raw"] = raw
+        fs["plan"] = self._plan(prep, fs, shape, flags)
         return fs
 
     def _forward_train(self, prep, x, fs, flags, saved=None, update=False):
-        """The forward with batch statistics in the layers ``flags`` names, launch by launch on the frame set ``fs`` (it has raw
-        frames: _add_raw_frames): (features, {name: (mean, biased var or None, invstd, n)}).  The convolution kernels and the rules
-        that pick them are those of the eval forward.  ``saved`` {name: (mean, invstd)}: apply these statistics instead of reducing
+        """The forward with batch statistics in the layers ``flags`` names, step by step over ``fs["plan"]`` (_add_raw_frames), one
+        call across the C ABI per launch: (features, {name: (mean, biased var or None, invstd, n)}).  The convolution kernels and the
+        rules that pick them are those of the eval forward.  ``saved`` {name: (mean, invstd)}: apply these statistics instead of reducing
         them (the backward's recompute).  ``update``: the fold launch also updates the layer's running buffers and counter."""
-        B, C, H, W = x.shape
+        B = x.shape[0]
         s, P = _capi.stream(), _capi.ptr
         D = lambda t: _capi.ptr(t, torch.float64)
         lib = _capi.load(dev=_capi._use_dev)
         dev, f64 = x.device, torch.float64
         bns = {name: bn for name, _, bn in self._enc_layers()}
-        raw, stats = fs["raw"], {}
+        stats = {}
 
-        def normalise(name, cb, h, w, pad, out, residual, relu):
-            """raw frame of ``name`` -> statistics -> fold -> out = act(raw scale + shift [+ residual])"""
-            bn, c, z = bns[name], cb.cout, raw[name]
+        def normalise(name, c, z, out, residual, relu, h, w, pad):
+            """raw frame ``z`` of ``name`` -> statistics -> fold -> out = act(raw scale + shift [+ residual])"""
+            bn = bns[name]
             scale, shift = torch.empty(c, device=dev), torch.empty(c, device=dev)
             gamma, beta = _capi.f32c(bn.weight.detach()), _capi.f32c(bn.bias.detach())
             n = B * h * w
@@ -809,51 +764,14 @@ class ResNet(DeviceStateModule):
                        pad, pad, 1 if relu else 0, s)
             stats[name] = (mean, var, invstd, n)
 
-        stem = prep["stem"]
-        ts = flags["stem"]
-        y = raw["stem"] if ts else fs["stem"]
-        if fs["stem_wino"]:
-            _capi.call("hps_stem_phase_split", P(x), P(fs["in"]), B, C, H, W, s)
-            sc, sh = stem.ident if ts else (stem.scale, stem.shift)
-            _capi.call("hps_stem_winograd", P(fs["in"]), P(stem.stem_u), P(sc), P(sh), P(y), B, H, W, 0, 0 if ts else 1, s)
-        else:
-            if fs["generic_in"] is not None:
-                _, cf, _, wf = fs["generic_in"]
-                _capi.call("hps_nchw_to_padded_nhwc_generic", P(x), P(fs["in"]), B, C, cf, H, W, wf, 3, s)
+        plan = fs["plan"]
+        feats = torch.empty(B, fs["blocks"][-1]["c2"].shape[3], device=dev, dtype=torch.float32)
+        plan[0].x, plan[-1].y = x.data_ptr(), feats.data_ptr()
+        for step in plan:
+            if isinstance(step, _BNStep):
+                normalise(*step)
             else:
-                _capi.call("hps_nchw_to_padded_nhwc", P(x), P(fs["in"]), B, C, H, W, 3, s)
-            stem.padded(fs["in"], 3, y, 0, relu=not ts, ident=ts)
-        y = fs["stem"]
-        if ts:
-            normalise("stem", stem, y.shape[1], y.shape[2], 0, y, None, True)
-        _capi.call("hps_maxpool3x3s2_pad", P(y), P(fs["pool"]), B, y.shape[1], y.shape[2], y.shape[3], 1, s)
-        y = fs["pool"]
-        for name, (c1, c2, down), ent in zip(self._block_names(), prep["blocks"], fs["blocks"]):      # BasicBlock.forward :62-78
-            t1, t2, td = flags[name + ".c1"], flags[name + ".c2"], down is not None and flags[name + ".down"]
-            hin, win = y.shape[1] - 2, y.shape[2] - 2
-            h, w = c1.out_hw(hin, win)
-            o1 = raw[name + ".c1"] if t1 else ent["c1"]
-            od = raw[name + ".down"] if td else ent["down"]
-            if down is not None and self.fold_downsample and c1.folds_down(down, hin, win, 1):
-                c1.padded_with_down(y, 1, o1, 1, down, od, ws=ent["ws"], relu=not t1, ident=(t1, td))
-            else:
-                if down is not None:
-                    down.padded(y, 1, od, 1, relu=False, ident=td)
-                c1.padded(y, 1, o1, 1, relu=not t1, ws=ent["ws"], ident=t1)
-            if td:
-                normalise(name + ".down", down, h, w, 1, ent["down"], None, False)
-            if t1:
-                normalise(name + ".c1", c1, h, w, 1, ent["c1"], None, True)
-            identity = ent["down"] if down is not None else y
-            if t2:
-                c2.padded(ent["c1"], 1, raw[name + ".c2"], 1, relu=False, ws=ent["ws"], ident=True)
-                normalise(name + ".c2", c2, h, w, 1, ent["c2"], identity, True)
-            else:
-                c2.padded(ent["c1"], 1, ent["c2"], 1, residual=identity, relu=True, ws=ent["ws"])
-            y = ent["c2"]
-        h, w = fs["hw"]
-        feats = torch.empty(B, y.shape[3], device=dev, dtype=torch.float32)
-        _capi.call("hps_global_avgpool_pad", P(y), P(feats), B, h, w, y.shape[3], 1, s)
+                _capi.issue_enc_op(step)
         if update:
             prep.setdefault("stale_bn", set()).update(stats)      # their eval-mode folds no longer match the running statistics
         return feats, stats
@@ -888,7 +806,7 @@ class ResNet(DeviceStateModule):
         written out, max pool as a launch of its own; phase split + frame-fed kernel where the forward took the Winograd stem -- the
         same values as the fused launches) and one cotangent frame per activation frame, halos zeroed once."""
         # the launch list points at ``prep``'s filters: a backward that outlives a kernel-mode switch keeps its own set
-        key = (B, C, H, W, _capi.stream().value, id(prep), tuple(flags.values()) if flags else None)
+        key = (B, C, H, W, _capi.stream().value, id(prep), tuple(flags.values()) if flags else None, self._variant_state(prep))
 
         def build():
             stem = prep["stem"]
@@ -901,7 +819,7 @@ class ResNet(DeviceStateModule):
                                     "tmp": torch.zeros_like(y) if down is not None else None})
                 y = ent["c2"]
             if flags:        # raw maps of the training layers; their dz frames (out of place: the gated cotangent has other readers)
-                self._add_raw_frames(fs, flags)
+                self._add_raw_frames(prep, fs, (B, C, H, W), flags)
                 g["dz_stem"] = torch.empty_like(fs["stem"]) if flags["stem"] else None
                 for name, ent, ge in zip(self._block_names(), fs["blocks"], g["blocks"]):
                     ge["dz"] = torch.zeros_like(ent["c2"]) if flags[name + ".c1"] or flags[name + ".c2"] else None

@@ -292,3 +292,29 @@ def test_frame_cache_keeps_transposed_shapes_apart(dev, encoder):
     for n in (0, 2):
         assert torch.equal(enc(xs[n].to(dev)), first[n]), CACHE_SHAPES[n]
     assert len(enc._frames) == 3
+
+
+def test_hand_edited_layer_gets_a_frame_set_of_its_own(dev, encoder):
+    """Fields edited by hand on a prepared layer (layer1.0's first convolution: Winograd off, two K slices over its 18 chunks) select a
+    frame set of their own, with the op list and the split-K scratch of the edited state: the bits of a fresh encoder that was edited
+    before its first forward, within the Winograd-versus-direct figure of the default ones, and the default bits again once restored."""
+    enc = encoder[0]
+    enc.invalidate()
+    x = torch.rand(1, 18, 32, 32, generator=torch.Generator().manual_seed(41)).to(dev)
+    fresh = copy.deepcopy(enc)
+    with torch.no_grad():
+        default = enc(x).clone()
+        n_sets = len(enc._frames)
+        cb, cb_fresh = enc._prepared["blocks"][0][0], fresh.prepare()["blocks"][0][0]
+        assert cb.winograd_ok(8, 8, 1) and cb.kh * cb.kw * cb.cin_p // 32 == 18
+        try:
+            cb.use_winograd, cb.ksplit = False, 2
+            cb_fresh.use_winograd, cb_fresh.ksplit = False, 2
+            edited = enc(x).clone()
+            assert len(enc._frames) == n_sets + 1
+            assert torch.equal(edited, fresh(x))
+            assert maxerr(edited, default) <= 2e-5 * float(default.abs().max())
+        finally:
+            cb.use_winograd, cb.ksplit = True, 0
+        assert torch.equal(enc(x), default)
+        assert len(enc._frames) == n_sets + 1
