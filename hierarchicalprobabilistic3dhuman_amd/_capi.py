@@ -117,6 +117,10 @@ _PROTOTYPES = {
     "hps_seg_bbox_affine": [_P, _c.c_int64, _P, _I, _I, _I, _I, _c.c_float, _P, _P, _P, _P, _P, _P],
     "hps_train_crop_augment": [_P, _c.c_int64, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "hps_train_joints2d": [_P, _P, _P, _P, _P, _I, _I, _c.c_float, _I, _I, _P, _P, _P, _P, _P],
+    "hps_sizeof_adam_entry": [],
+    "hps_adam_step": [_P, _I, _P, _I, _P],
+    "hps_sizeof_refresh_op": [],
+    "hps_weights_refresh": [_P, _I, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -149,6 +153,21 @@ class MfLossArgs(_c.Structure):
                           "g_verts", "g_joints3d")]
 
 
+class AdamEntry(_c.Structure):
+    """include/hps.h: hps_adam_entry."""
+    _fields_ = [("param", _P), ("grad", _P), ("exp_avg", _P), ("exp_avg_sq", _P), ("numel", _c.c_int64)] + [
+        (n, _c.c_double) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "bias_correction1", "bias_correction2_sqrt")] + [
+        ("decoupled", _I), ("reserved", _I)]
+
+
+class RefreshOp(_c.Structure):
+    """include/hps.h: hps_refresh_op."""
+    _fields_ = [("kind", _I), ("scale_dim", _I), ("src", _P), ("dst", _P), ("dst2", _P), ("aux0", _P), ("aux1", _P), ("aux2", _P),
+                ("eps", _c.c_double), ("n", _I * 4), ("sstride", _I * 4), ("dstride", _I * 4)]
+
+
+ADAM_CHUNK = 4096
+REFRESH_PERMUTE, REFRESH_FOLD, REFRESH_WINO_U, REFRESH_STEM_U = 0, 1, 2, 3
 MF_REDUCTION_MEAN, MF_REDUCTION_SUM = 0, 1
 ENC_RELAYOUT, ENC_CONV, ENC_MAXPOOL, ENC_AVGPOOL, ENC_CONV_WINOGRAD, ENC_STEM_SPLIT, ENC_STEM_WINOGRAD, ENC_RELAYOUT_GENERIC = 0, 1, 2, 3, 4, 5, 6, 7
 ENC_STEM_WINOGRAD_POOLED, ENC_STEM_WINOGRAD_POOLED_NCHW, ENC_CONV_DOWN = 8, 9, 10

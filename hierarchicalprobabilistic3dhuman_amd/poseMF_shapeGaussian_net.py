@@ -47,6 +47,7 @@ from torch import nn
 from torch.distributions import Normal
 
 from . import _capi
+from .device_optim import RefreshList, plain
 from .device_state import DeviceStateModule
 from .resnet import resnet18
 from .rigid_transform_utils import rotmat_to_rot6d
@@ -261,6 +262,57 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
 
     def _head_versions(self):
         return tuple(w._version for w in self._head_params())
+
+    # ---- after an optimiser step that says so (device_optim.DeviceAdam): the derived weights again, in place ----
+    def _refresh_list(self, p, token):
+        """One hps_refresh_op per tensor prepare() / _prepare_backward derive from a parameter by more than an alias: the transposed
+        copies, the fused fc_shape | fc_glob | fc_cam layer; the copies nn.Linear's own layout needs only where the parameter is not
+        what the kernels read already (RefreshList.copy: nothing for an alias)."""
+        ref = RefreshList(token)
+        q = p.get("bwd")
+        ref.transpose(self.fc1.weight, p["fc1_wt"])
+        ref.copy(self.fc1.bias, p["fc1_b"])
+        nt, row = p["sgc_b"].numel(), 0
+        for m in (self.fc_shape, self.fc_glob, self.fc_cam):
+            ref.transpose(m.weight, p["sgc_wt"], offset=row, ld=nt)
+            ref.copy(m.bias, p["sgc_b"], offset=row)
+            if q is not None:
+                ref.copy(m.weight, q["sgc_w"], offset=row * m.weight.shape[1])
+            row += m.weight.shape[0]
+        ref.transpose(self.fc_embed.weight, p["embed_wt"])
+        ref.copy(self.fc_embed.bias, p["embed_b"])
+        if q is not None:
+            ref.copy(self.fc1.weight, q["fc1_w"])
+            ref.copy(self.fc_embed.weight, q["embed_w"])
+        w1t, b1, w2, b2 = p["keep"]
+        for j, m in enumerate(self.fc_pose):
+            ref.transpose(m[0].weight, w1t[j])
+            ref.copy(m[0].bias, b1[j])
+            ref.copy(m[2].weight, w2[j])
+            ref.copy(m[2].bias, b2[j])
+        return ref
+
+    def refresh_weights(self):
+        """The encoder's refresh (ResNet.refresh_weights), then the head's: every kernel-side copy of a head parameter written again
+        in place (hps_weights_refresh) and the version counters recorded, so that the next forward keeps the prepared state with its
+        pointer tables.  Without a prepared state: nothing to do."""
+        self.image_encoder.refresh_weights()
+        p = self._prepared
+        if p is None:
+            return
+        params = self._head_params()
+        if not all(w.is_cuda and plain(w) for w in params):
+            self.invalidate()
+            return
+        token = (tuple(w.data_ptr() for w in params), "bwd" in p)
+        ref = self._device_state.get("refresh")
+        if ref is not None and ref.token[0] != token[0]:
+            self.invalidate()
+            return
+        if ref is None or ref.token != token:
+            ref = self._device_state["refresh"] = self._refresh_list(p, token)
+        ref.run()
+        p["versions"] = self._head_versions()
 
     def _prepare_backward(self, p):
         """What only the backward needs, built at the first backward of a prepared state: the weights in nn.Linear's own layout (the

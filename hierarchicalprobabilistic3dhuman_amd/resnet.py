@@ -38,6 +38,7 @@ import torch
 from torch import nn
 
 from . import _capi
+from .device_optim import RefreshList, plain
 from .device_state import DeviceStateModule
 
 
@@ -708,6 +709,63 @@ class ResNet(DeviceStateModule):
                         prep.get("bwd", {}).pop(name, None)       # the data gradient's scaled filter
             stale.clear()
         return prep
+
+    # ---- after an optimiser step that says so (device_optim.DeviceAdam): the derived weights again, in place ----
+    def _refresh_token(self, prep):
+        tensors = [t for _, conv, bn in self._enc_layers() for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        if not all(t.is_cuda and plain(t) for t in tensors):
+            return None
+        return tuple(t.data_ptr() for t in tensors), frozenset(prep.get("bwd", {}))
+
+    def _refresh_list(self, prep, token):
+        """One hps_refresh_op per tensor _ConvBN.__init__ / _dgrad_filter derive from a parameter, in their layouts; the folds first
+        (the scaled data-gradient filters read them)."""
+        ref = RefreshList(token)
+        bwd = prep.get("bwd", {})
+        convs = [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]
+        layers = list(zip(self._enc_layers(), convs))
+        for (_, _, bn), cb in layers:
+            ref.fold(bn, cb.scale, cb.shift)
+        for (name, conv, _), cb in layers:
+            w = conv.weight
+            cout, cin, kh, kw = w.shape
+            s_o, s_c, s_i, s_j = cin * kh * kw, kh * kw, kw, 1
+            ref.permute(w, cb.wk, (kh, kw, cin, cout), (s_i, s_j, s_c, s_o), (kw * cb.cin_p * cout, cb.cin_p * cout, cout, 1))
+            if cb.wn is not None:
+                ref.permute(w, cb.wn, (cout, kh, kw, cin), (s_o, s_i, s_j, s_c), (kh * kw * cb.cin_p, kw * cb.cin_p, cb.cin_p, 1))
+            if cb.wrow is not None:
+                ck = cb.wrow.shape[1] // kh
+                ref.permute(w, cb.wrow, (cout, kh, kw, cin), (s_o, s_i, s_j, s_c), (kh * ck, ck, cb.row_c, 1))
+            if cb.wino_u is not None:
+                ref.winograd(w, cb.wino_u)
+            if cb.stem_u is not None:
+                ref.winograd(w, cb.stem_u, stem=True)
+            for key, scale in ((name + ".raw", None), (name, cb.scale)):
+                if key in bwd:
+                    ref.permute(w, bwd[key], (kh, kw, cout, cin), (s_i, s_j, s_o, s_c), (kw * cout * cin, cout * cin, cin, 1),
+                                scale=scale, scale_dim=2)
+        return ref
+
+    def refresh_weights(self):
+        """Write every kernel-side tensor of the prepared state again, in place, from the parameters and running statistics as they
+        are now (hps_weights_refresh), and record the parameters' version counters: the next forward keeps the state -- frames,
+        launch lists, captured graphs -- where the version check would have dropped it.  The eval-mode folds of the layers a training
+        forward marked stale are redone by this very pass (the same float64 arithmetic, the same bits as _ConvBN.refold).  Without a
+        prepared state: nothing to do.  Parameters the kernels cannot read in place (another dtype, a replaced storage): the state
+        is dropped instead, as after any other edit."""
+        prep = self._prepared
+        if prep is None:
+            return
+        token = self._refresh_token(prep)
+        ref = self._device_state.get("refresh")
+        if token is None or (ref is not None and ref.token[0] != token[0]):
+            self.invalidate()
+            return
+        if ref is None or ref.token != token:
+            ref = self._device_state["refresh"] = self._refresh_list(prep, token)
+        ref.run()
+        prep.get("stale_bn", set()).clear()
+        prep["versions"] = self._enc_versions()
 
     def _train_frames(self, prep, B, C, H, W, device, flags):
         """The training forward's frame set for a batch shape on the current stream: as the backward's activation set (unfused stem

@@ -1011,6 +1011,69 @@ typedef struct hps_mf_loss_args {
 int hps_mf_loss_forward(const hps_mf_loss_args* args, void* workspace, float* total, hps_stream_t stream);
 int hps_mf_loss_backward(const hps_mf_loss_args* args, const void* workspace, const float* grad_total, hps_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The optimiser step  (run_train.py:97 optim.Adam(pose_shape_model.parameters(), lr=1e-4);
+ * train/train_poseMF_shapeGaussian_net.py:346-349 optimiser.zero_grad / loss.backward / optimiser.step; csrc/optim.hip)
+ * ---------------------------------------------------------------------------------------- */
+
+/* One tensor of a step: torch/optim/adam.py _single_tensor_adam with this tensor's own hyper-parameters.  bias_correction1 =
+ * 1 - beta1^t and bias_correction2_sqrt = sqrt(1 - beta2^t) are computed on the host, in double, as torch computes them.
+ * decoupled: weight_decay multiplies the parameter by 1 - lr weight_decay (AdamW) instead of adding weight_decay p to the gradient.
+ * All four arrays contiguous fp32 of numel elements; 16-byte aligned arrays take 16-byte accesses, any other alignment 4-byte ones. */
+typedef struct hps_adam_entry {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    int64_t numel;
+    double lr, beta1, beta2, eps, weight_decay;
+    double bias_correction1, bias_correction2_sqrt;
+    int decoupled;
+    int reserved;
+} hps_adam_entry;
+#define HPS_ADAM_CHUNK 4096 /* elements of one workgroup */
+int hps_sizeof_adam_entry(void);
+
+/* ONE launch for all tensors of a step.  table: n_tensors entries in DEVICE memory; block_map: n_blocks pairs (tensor, chunk) of
+ * int32 in device memory, workgroup i updates elements [chunk HPS_ADAM_CHUNK, (chunk + 1) HPS_ADAM_CHUNK) of its tensor -- every
+ * element of every tensor belongs to exactly one pair.  Per element, in float64 from the fp32 values, each of p, m, v rounded once:
+ *   g += weight_decay p (L2)  |  p *= 1 - lr weight_decay (decoupled);   m += (1 - beta1)(g - m);   v = beta2 v + (1 - beta2) g^2;
+ *   p -= (lr / bias_correction1) m / (sqrt(v) / bias_correction2_sqrt + eps).
+ * No atomics, bitwise repeatable, a tensor's result does not depend on the other tensors of the launch.  n_tensors == 0 or
+ * n_blocks == 0: nothing is launched. */
+int hps_adam_step(const hps_adam_entry* table, int n_tensors, const int32_t* block_map, int n_blocks, hps_stream_t stream);
+
+/* One derived tensor of a prepared state written again, in place, from its parameter (resnet.py _ConvBN, ResNet._dgrad_filter;
+ * poseMF_shapeGaussian_net.py prepare / _prepare_backward).  Elements of dst the op does not name (padding) are not touched.
+ *   HPS_REFRESH_PERMUTE  dst[sum_k i_k dstride[k]] = src[sum_k i_k sstride[k]] for i_k < n[k]: the k-major, n-major and row-mode
+ *                        filters, the data-gradient filter, the head's transposed copies and concatenations.  aux0 != NULL:
+ *                        times aux0[i_scale_dim] in float64, rounded once (the data-gradient filter with the fold's scale).
+ *   HPS_REFRESH_FOLD     eval-mode BatchNorm over n[0] channels: src = weight, aux0 = bias, aux1 = running_mean, aux2 = running_var;
+ *                        dst = scale = weight / sqrt(var + eps), dst2 = shift = bias - mean scale; float64, rounded once.
+ *   HPS_REFRESH_WINO_U   src (n[0] = Cout, n[1] = Cin, 3, 3) -> G g G^T in hps_conv3x3_winograd's layout; float64, rounded once.
+ *   HPS_REFRESH_STEM_U   src (64, 18, 7, 7) -> the 81 positions of hps_stem_winograd; float64, rounded once. */
+enum { HPS_REFRESH_PERMUTE = 0, HPS_REFRESH_FOLD = 1, HPS_REFRESH_WINO_U = 2, HPS_REFRESH_STEM_U = 3 };
+typedef struct hps_refresh_op {
+    int kind;
+    int scale_dim;
+    const float* src;
+    float* dst;
+    float* dst2;
+    const float* aux0;
+    const float* aux1;
+    const float* aux2;
+    double eps;
+    int n[4], sstride[4], dstride[4];
+} hps_refresh_op;
+int hps_sizeof_refresh_op(void);
+
+/* Issues ops[0..n_ops) in order on `stream`; the list (HOST memory) is built once per prepared state and run after every optimiser
+ * step.  Up to 16 consecutive ops share a launch and run in no order within it; an op whose src / aux pointer EQUALS the dst / dst2
+ * pointer of an earlier op of the same launch starts a new launch (stream order).  That is the only dependence the library sees: the
+ * caller keeps overlapping ranges, destinations reached at an offset and write-after-read out of one run of 16, or orders the list
+ * so that they cannot meet.  Null pointers, unknown kinds and impossible extents are refused before any launch. */
+int hps_weights_refresh(const hps_refresh_op* ops, int n_ops, hps_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
