@@ -121,6 +121,8 @@ _PROTOTYPES = {
     "hps_adam_step": [_P, _I, _P, _I, _P],
     "hps_sizeof_refresh_op": [],
     "hps_weights_refresh": [_P, _I, _P],
+    "hps_sizeof_render_args": [],
+    "hps_render": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -166,6 +168,16 @@ class RefreshOp(_c.Structure):
                 ("eps", _c.c_double), ("n", _I * 4), ("sstride", _I * 4), ("dstride", _I * 4)]
 
 
+class RenderArgs(_c.Structure):
+    """include/hps.h: hps_render_args (struct_bytes = ctypes.sizeof(RenderArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "H", "W", "num_verts", "num_dp_verts", "num_faces", "projection", "tex_h", "tex_w",
+                                  "cam_t_stride", "scale_stride")] + [("light_stride", _I * 4)] + [
+        (n, _P) for n in ("vertices", "verts_map", "faces", "vf_offsets", "vf_faces", "verts_iuv", "verts_uv", "cam_t", "scale",
+                          "light_location", "ambient", "diffuse", "specular", "texture", "verts_features", "workspace", "iuv", "rgb",
+                          "depth", "pix_to_face", "bary", "iuv_train")]
+
+
+RENDER_PERSPECTIVE, RENDER_ORTHOGRAPHIC = 0, 1
 ADAM_CHUNK = 4096
 REFRESH_PERMUTE, REFRESH_FOLD, REFRESH_WINO_U, REFRESH_STEM_U = 0, 1, 2, 3
 MF_REDUCTION_MEAN, MF_REDUCTION_SUM = 0, 1
@@ -368,6 +380,7 @@ WS_MF_LOSS = 8
 WS_SMPL_LBS_BWD, WS_SMPL_BLEND_BWD = 9, 10
 WS_HEAD_LEVELS_BWD, WS_HEAD_TRUNK_BWD = 11, 12
 WS_SEG_BBOX = 13
+WS_RENDER = 14
 
 
 def query_workspace(what, d0=0, d1=0, d2=0):

@@ -36,10 +36,14 @@ def _synth_data():
         REMOVE_APPENDAGE_JOINTS_PROB=0.5, REMOVE_JOINTS_INDICES=[7, 8, 9, 10, 13, 14, 15, 16], REMOVE_JOINTS_PROB=0.1,
         DELTA_J2D_DEV_RANGE=[-6, 6], JOINTS_TO_SWAP=[[5, 6], [11, 12]], JOINTS_SWAP_PROB=0.1, OCCLUDE_BOX_DIM=48,
         OCCLUDE_BOX_PROB=0.1, OCCLUDE_BOTTOM_PROB=0.02, OCCLUDE_TOP_PROB=0.005, OCCLUDE_VERTICAL_PROB=0.05, EXTREME_CROP_PROB=0.1)
-    rgb = SimpleNamespace(OCCLUDE_BOTTOM_PROB=0.02, OCCLUDE_TOP_PROB=0.005, OCCLUDE_VERTICAL_PROB=0.05, PIXEL_CHANNEL_NOISE=0.2)
+    rgb = SimpleNamespace(OCCLUDE_BOTTOM_PROB=0.02, OCCLUDE_TOP_PROB=0.005, OCCLUDE_VERTICAL_PROB=0.05, PIXEL_CHANNEL_NOISE=0.2,
+                          LIGHT_LOC_RANGE=[0.05, 3.0], LIGHT_AMBIENT_RANGE=[0.4, 0.8], LIGHT_DIFFUSE_RANGE=[0.4, 0.8],
+                          LIGHT_SPECULAR_RANGE=[0.0, 0.5])                           # :73-76, textured_renderer.augment_light
     bbox = SimpleNamespace(DELTA_SCALE_RANGE=[-0.3, 0.2], DELTA_CENTRE_RANGE=[-5, 5])
     return SimpleNamespace(FOCAL_LENGTH=300.0, MEAN_CAM_T=[0.0, -0.2, 2.5],
-                           AUGMENT=SimpleNamespace(BBOX=bbox, PROXY_REP=proxy_rep, RGB=rgb))
+                           AUGMENT=SimpleNamespace(BBOX=bbox, PROXY_REP=proxy_rep, RGB=rgb,
+                                                   SMPL=SimpleNamespace(SHAPE_STD=1.25),                          # :45
+                                                   CAM=SimpleNamespace(XY_STD=0.05, DELTA_Z_RANGE=[-0.5, 0.5])))  # :48-49
 
 
 def get_cfg_defaults():

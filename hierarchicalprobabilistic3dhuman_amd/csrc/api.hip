@@ -37,6 +37,7 @@ extern "C" int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t
 #ifdef HPS_DEV_BUILD
         case HPS_DEV_WS_HEAD_SYNC: return ((d0 + 3) / 4) * (HPS_HEAD_MAX_LEVELS + 1) * (int64_t)sizeof(int32_t);
 #endif
+        case HPS_WS_RENDER: return hps::render_ws_bytes(d0, d1, d2);
         default: hps::set_error("hps_query_workspace: unknown item %d", what); return -1;
     }
 }

@@ -24,6 +24,8 @@ int64_t blend_backward_ws_bytes(int64_t M, int64_t kp, int64_t np);
 // bytes of the hps_head_pose_levels_backward / hps_head_trunk_backward workspaces (csrc/head_backward.hip; HPS_WS_HEAD_LEVELS_BWD / _TRUNK_BWD)
 int64_t head_levels_backward_ws_bytes(int64_t B, int64_t total_in, int64_t NJ);
 int64_t head_trunk_backward_ws_bytes(int64_t B, int64_t wide, int64_t nt);
+// bytes of the hps_render workspace (csrc/render.hip; HPS_WS_RENDER)
+int64_t render_ws_bytes(int64_t B, int64_t Nd, int64_t F);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -103,10 +103,11 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_HEAD_TRUNK_BWD  (d0 = B, d1 = num_feats + hidden + embed_dim, d2 = 2 num_shape + num_glob + num_cam)
  *                                                               workspace of hps_head_trunk_backward
  *   HPS_WS_SEG_BBOX    (d0 = B)                                 ws of hps_seg_bbox_affine (per-chunk integer box corners)
+ *   HPS_WS_RENDER      (d0 = B, d1 = DensePose vertices, d2 = faces)  workspace of hps_render
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
        HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
-       HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13 };
+       HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13, HPS_WS_RENDER = 14 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -1073,6 +1074,66 @@ int hps_sizeof_refresh_op(void);
  * caller keeps overlapping ranges, destinations reached at an offset and write-after-read out of one run of 16, or orders the list
  * so that they cannot meet.  Null pointers, unknown kinds and impossible extents are refused before any launch. */
 int hps_weights_refresh(const hps_refresh_op* ops, int n_ops, hps_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * The training renderer  (train/train_poseMF_shapeGaussian_net.py:186-196; renderers/pytorch3d_textured_renderer.py:223-290
+ * with run_train.py:86-91's defaults: blur_radius 0, one face per pixel, no perspective correction, no culling, no clipping,
+ * HardPhongShader, under no_grad; csrc/render.hip)
+ * ---------------------------------------------------------------------------------------- */
+
+/* A hard nearest-face rasteriser with Phong shading, forward only.  pytorch3d is restated here, not linked:
+ *   vertices   v = vertices[:, verts_map] (:264).  X = -(x + tx), Y = -(y + ty), Z = z + tz (the camera's diag(-1,-1,1) and the
+ *              translation's sign flip, :155-163, :254).  Perspective: x_ndc = (s_x X) / Z, y_ndc = (s_y Y) / Z with s = 2 f / W;
+ *              orthographic: x_ndc = s_x X, y_ndc = s_y Y with s = orthographic_scale.  z = Z in both.  Square images only.
+ *   pixels     row r, column c samples (1 - (2 c + 1) / W, 1 - (2 r + 1) / W): a vertex lands in the pixel
+ *              cam_utils.perspective_project_torch gives it (u = c + 0.5).
+ *   coverage   E(p, a, b) = (p.x - a.x)(b.y - a.y) - (p.y - a.y)(b.x - a.x); area = E(v2, v0, v1); a face with |area| <= 1e-8 or
+ *              with its largest z < 1e-8 is skipped; w0 = E(p, v1, v2) / (area + 1e-8), w1 = E(p, v2, v0) / (area + 1e-8),
+ *              w2 = E(p, v0, v1) / (area + 1e-8); covered only if all three are > 0 (a centre on an edge belongs to no face);
+ *              pz = w0 z0 + w1 z1 + w2 z2, skipped at that pixel if pz < 0.
+ *   depth      the smallest pz wins, on equal pz the lower face index; empty pixels: pix_to_face = -1, depth = -1, bary = -1.
+ *   IUV        sum of w verts_iuv (Nd,3), shared by the batch (:266-267, lights (1,1,1), (0,0,0), (0,0,0): the texel itself).
+ *   texel      texture (B,Ht,Wt,3): (u, v) = sum of w verts_uv (Nd,2), x = u (Wt - 1), y = (1 - v)(Ht - 1), both clamped to the map,
+ *              bilinear with a + t (b - a) along x twice, then along y (TexturesUV, align_corners = True, border) -- or, when
+ *              verts_features (B,V,3) is given, sum of w verts_features[:, verts_map] (TexturesVertex, :269-271).
+ *   Phong      vertex normal = sum over the vertex's faces, in the order of the table (vf_offsets (Nd+1), vf_faces: compressed sparse
+ *              rows, built once on the host), of cross(v1 - v0, v2 - v0), divided by max(|n|, 1e-6).  n = normalise(sum of w n_v),
+ *              P = sum of w v, L = normalise(light_location - P), view = normalise((-tx, -ty, -tz) - P), each by max(|.|, 1e-6);
+ *              diffuse = diffuse_color relu(n.L); reflect = -L + 2 (n.L) n; specular = specular_color (relu(view.reflect) [n.L > 0])^64
+ *              (six squarings); rgb = min(1, (ambient_color + diffuse) texel + specular) (:285); background (0,0,0).
+ * Outputs, each NULL = not wanted, planar: iuv, rgb, bary (B,3,W,W), depth (B,W,W), pix_to_face (B,W,W) int32 (the face's index in
+ * `faces`), iuv_train (B,3,W,W) = iuv with U and V times 255, all three rounded half to even (:193-195).
+ * cam_t, scale and the four light arrays are per image (stride 3, scale 2) or shared (stride 0).  verts_map (< num_verts), faces
+ * (< num_dp_verts) and vf_faces (< num_faces) are read as they are: the caller checks them once, where it builds them.
+ * Three launches (project; face boxes and vertex normals; rasterise and shade), no atomics, bitwise repeatable, nothing allocated:
+ * workspace is hps_query_workspace(HPS_WS_RENDER, B, num_dp_verts, num_faces) bytes, 16-byte aligned.  B <= 65535, W <= 4096,
+ * num_faces <= 2^24, texture sides <= 32768; HPS_E_BADARG otherwise.  struct_bytes = sizeof(hps_render_args) as the caller compiled it. */
+#define HPS_RENDER_PERSPECTIVE 0
+#define HPS_RENDER_ORTHOGRAPHIC 1
+typedef struct hps_render_args {
+    int struct_bytes;
+    int B, H, W;
+    int num_verts, num_dp_verts, num_faces;
+    int projection;                                            /* HPS_RENDER_* */
+    int tex_h, tex_w;
+    int cam_t_stride, scale_stride;                            /* floats between images: 3 / 2, or 0 = shared */
+    int light_stride[4];                                       /* location, ambient, diffuse, specular: 3 or 0 */
+    const float* vertices;                                     /* (B, num_verts, 3) */
+    const int32_t* verts_map;                                  /* (num_dp_verts) */
+    const int32_t* faces;                                      /* (num_faces, 3) */
+    const int32_t *vf_offsets, *vf_faces;                      /* (num_dp_verts + 1), (vf_offsets[num_dp_verts]) */
+    const float *verts_iuv, *verts_uv;                         /* (num_dp_verts, 3), (num_dp_verts, 2) */
+    const float *cam_t, *scale;
+    const float *light_location, *ambient, *diffuse, *specular;
+    const float* texture;                                      /* (B, tex_h, tex_w, 3) */
+    const float* verts_features;                               /* (B, num_verts, 3) */
+    void* workspace;
+    float *iuv, *rgb, *depth;
+    int32_t* pix_to_face;
+    float *bary, *iuv_train;
+} hps_render_args;
+int hps_sizeof_render_args(void);
+int hps_render(const hps_render_args* args, hps_stream_t stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
