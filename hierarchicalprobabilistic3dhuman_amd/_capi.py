@@ -123,6 +123,8 @@ _PROTOTYPES = {
     "hps_weights_refresh": [_P, _I, _P],
     "hps_sizeof_render_args": [],
     "hps_render": [_P, _P],
+    "hps_sizeof_silhouette_args": [],
+    "hps_silhouette_iou": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -175,6 +177,13 @@ class RenderArgs(_c.Structure):
         (n, _P) for n in ("vertices", "verts_map", "faces", "vf_offsets", "vf_faces", "verts_iuv", "verts_uv", "cam_t", "scale",
                           "light_location", "ambient", "diffuse", "specular", "texture", "verts_features", "workspace", "iuv", "rgb",
                           "depth", "pix_to_face", "bary", "iuv_train")]
+
+
+class SilhouetteArgs(_c.Structure):
+    """include/hps.h: hps_silhouette_args (struct_bytes = ctypes.sizeof(SilhouetteArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "M", "W", "group", "num_verts", "num_dp_verts", "num_faces", "projection", "flip_x_pi",
+                                  "cam_t_stride", "scale_stride")] + [
+        (n, _P) for n in ("vertices", "verts_map", "faces", "verts_iuv", "cam_t", "scale", "target", "workspace", "counts", "mask_out")]
 
 
 RENDER_PERSPECTIVE, RENDER_ORTHOGRAPHIC = 0, 1
@@ -381,6 +390,12 @@ WS_SMPL_LBS_BWD, WS_SMPL_BLEND_BWD = 9, 10
 WS_HEAD_LEVELS_BWD, WS_HEAD_TRUNK_BWD = 11, 12
 WS_SEG_BBOX = 13
 WS_RENDER = 14
+WS_SILHOUETTE = 15
+
+
+def silhouette_d2(num_faces, W):
+    """include/hps.h: HPS_WS_SILHOUETTE_D2 -- the face count and the image side in hps_query_workspace's third dimension."""
+    return int(num_faces) + (int(W) << 32)
 
 
 def query_workspace(what, d0=0, d1=0, d2=0):

@@ -38,6 +38,11 @@ extern "C" int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t
         case HPS_DEV_WS_HEAD_SYNC: return ((d0 + 3) / 4) * (HPS_HEAD_MAX_LEVELS + 1) * (int64_t)sizeof(int32_t);
 #endif
         case HPS_WS_RENDER: return hps::render_ws_bytes(d0, d1, d2);
+        case HPS_WS_SILHOUETTE: {                                                  // d2 = HPS_WS_SILHOUETTE_D2(faces, W)
+            const int64_t faces = d2 & 0xffffffffll, W = d2 >> 32;
+            if (faces > (1 << 24) || W < 1 || W > 4096) { hps::set_error("hps_query_workspace: HPS_WS_SILHOUETTE takes d2 = faces + W * 2^32 with faces <= 2^24, W in [1, 4096]"); return -1; }
+            return hps::silhouette_ws_bytes(d0, d1, faces, W);
+        }
         default: hps::set_error("hps_query_workspace: unknown item %d", what); return -1;
     }
 }

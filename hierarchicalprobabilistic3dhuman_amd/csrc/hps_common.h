@@ -26,6 +26,8 @@ int64_t head_levels_backward_ws_bytes(int64_t B, int64_t total_in, int64_t NJ);
 int64_t head_trunk_backward_ws_bytes(int64_t B, int64_t wide, int64_t nt);
 // bytes of the hps_render workspace (csrc/render.hip; HPS_WS_RENDER)
 int64_t render_ws_bytes(int64_t B, int64_t Nd, int64_t F);
+// bytes of the hps_silhouette_iou workspace (csrc/render.hip; HPS_WS_SILHOUETTE)
+int64_t silhouette_ws_bytes(int64_t M, int64_t Nd, int64_t F, int64_t W);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

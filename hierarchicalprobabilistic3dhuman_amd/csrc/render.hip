@@ -21,6 +21,9 @@
 //
 // Compiled with -ffp-contract=off (build.py): coverage is a sign decision on the edge functions, and the restatement the kernels are
 // held to (numpy, which never contracts) rounds every product; the operation ORDER below is the restatement's, line by line.
+//
+// The evaluation's silhouette counts (hps_silhouette_iou, second half of this file) run launch 2's face blocks and launch 3's loop
+// over the same helpers and end in pixel counts instead of images.
 #include "hps_common.h"
 
 namespace hps {
@@ -361,7 +364,217 @@ __global__ __launch_bounds__(64) void render_raster_kernel(const RasterParams P)
     }
 }
 
+// ---- silhouette counts (hps_silhouette_iou) ---------------------------------------------------------------------------------------
+// The evaluation's silhouette metrics (evaluate/evaluate_poseMF_shapeGaussian_net.py:143-155, 192-203 with
+// metrics/eval_metrics_tracker.py:294-328) need one bit per pixel of every mesh, compared with a target bit and counted.  Four
+// launches over the same face boxes, records and walk as above:
+//
+//   1  silhouette_project_kernel   as launch 1, with the rotation by pi about x folded in, a camera per GROUP of meshes, NDC only
+//   2  render_setup_kernel         its face blocks only: no normals are needed, none are computed
+//   3  silhouette_raster_kernel    launch 3's chunk / record / walk loop (the loop is repeated here, render_raster_kernel is left
+//                                  as it is); then the winner's rounded part label against the target byte, four ballots, and one
+//                                  16-byte store of the tile's [tp, fp, tn, fn]
+//   4  silhouette_reduce_kernel    a mesh's tile counts added up: integers, so any order gives the same sums
+int64_t silhouette_ws_bytes(int64_t M, int64_t Nd, int64_t F, int64_t W) {
+    const int64_t chunks = (F + RD_CHUNK - 1) / RD_CHUNK, tiles = (W + RD_TILE - 1) / RD_TILE;
+    // ndc: float4 per (mesh, vertex); tile counts: int4 per (mesh, tile); face boxes and chunk boxes: two words each
+    return M * Nd * 16 + M * tiles * tiles * 16 + M * F * 8 + M * chunks * 8;
+}
+
+struct SilhouetteWs {
+    float4* ndc;
+    int4* tile_counts;
+    int2* face_box;
+    int2* chunk_box;
+};
+
+static SilhouetteWs carve_silhouette(void* ws, int64_t M, int64_t Nd, int64_t F, int64_t W) {
+    const int64_t tiles = (W + RD_TILE - 1) / RD_TILE;
+    SilhouetteWs r;
+    char* p = static_cast<char*>(ws);
+    r.ndc = reinterpret_cast<float4*>(p); p += M * Nd * 16;
+    r.tile_counts = reinterpret_cast<int4*>(p); p += M * tiles * tiles * 16;
+    r.face_box = reinterpret_cast<int2*>(p); p += M * F * 8;
+    r.chunk_box = reinterpret_cast<int2*>(p);
+    return r;
+}
+
+// Mesh m is seen by camera m / group.  flip: the vertex rotated by pi about x, (x, -y, -z) -- a negation is exact, so the result is
+// the one render_project_kernel gives for vertices flipped beforehand.
+__global__ __launch_bounds__(256) void silhouette_project_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ verts_map,
+                                                                 const float* __restrict__ cam_t, int cam_stride,
+                                                                 const float* __restrict__ scale, int scale_stride, int perspective,
+                                                                 int flip, int group, int V, int Nd, float4* __restrict__ ndc) {
+    const int i = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y;
+    if (i >= Nd) return;
+    const float* v = vertices + ((size_t)m * V + verts_map[i]) * 3;
+    const float x = v[0], y = flip ? -v[1] : v[1], z = flip ? -v[2] : v[2];
+    const float* t = cam_t + (size_t)(m / group) * cam_stride;
+    const float* s = scale + (size_t)(m / group) * scale_stride;
+    const float X = -(x + t[0]), Y = -(y + t[1]), Z = z + t[2];
+    float xn = s[0] * X, yn = s[1] * Y;
+    if (perspective) { xn = xn / Z; yn = yn / Z; }
+    ndc[(size_t)m * Nd + i] = make_float4(xn, yn, Z, 0.0f);
+}
+
+struct SilhouetteParams {
+    const int32_t* faces;
+    const float4* ndc;
+    const int2* face_box;
+    const int2* chunk_box;
+    const float* verts_iuv;
+    const uint8_t* target;
+    int Nd, F, chunks, W, group;
+    int4* tile_counts;
+    uint8_t* mask_out;
+};
+
+__global__ __launch_bounds__(64) void silhouette_raster_kernel(const SilhouetteParams P) {
+    __shared__ __attribute__((aligned(16))) float rec[RD_CHUNK * RD_REC];
+    const int b = blockIdx.z, lane = threadIdx.x;
+    const unsigned long long lane_lt = (1ull << lane) - 1ull;
+    const int W = P.W, Nd = P.Nd, F = P.F;
+    const int tc0 = blockIdx.x * RD_TILE, tr0 = blockIdx.y * RD_TILE;
+    const int tc1 = min(tc0 + RD_TILE, W) - 1, tr1 = min(tr0 + RD_TILE, W) - 1;
+    const int c = tc0 + (lane & (RD_TILE - 1)), r = tr0 + (lane >> 3);
+    const bool inside = c < W && r < W;
+    const float px = 1.0f - (float)(2 * c + 1) / (float)W;
+    const float py = 1.0f - (float)(2 * r + 1) / (float)W;
+    const float4* ndc = P.ndc + (size_t)b * Nd;
+    const int2* face_box = P.face_box + (size_t)b * F;
+
+    // the target byte of image m / group; NULL: no target, every pixel counts as background
+    const size_t plane = (size_t)W * W, pix = (size_t)r * W + c;
+    bool tgt = false;
+    if (inside && P.target) tgt = P.target[(size_t)(b / P.group) * plane + pix] != 0;
+
+    Winner best = {__builtin_inff(), 0.0f, 0.0f, 0.0f, -1};
+    int count = 0;                                         // records in LDS that have not been walked yet (wave-uniform)
+
+    // render_raster_kernel's loop; every condition around a barrier is wave-uniform (a ballot or a kernel argument), and a tile that
+    // meets no chunk falls through to the count below like any other
+    for (int c0 = 0; c0 < P.chunks; c0 += 64) {
+        bool chit = false;
+        if (c0 + lane < P.chunks) chit = meets(P.chunk_box[(size_t)b * P.chunks + c0 + lane], tc0, tc1, tr0, tr1);
+        unsigned long long cm = __ballot(chit);
+        while (cm) {
+            int f[RD_GROUP], i0[RD_GROUP], i1[RD_GROUP], i2[RD_GROUP];
+            int2 fb[RD_GROUP];
+#pragma unroll
+            for (int g = 0; g < RD_GROUP; ++g) {
+                f[g] = F;
+                if (cm) {
+                    f[g] = (c0 + __builtin_ctzll(cm)) * RD_CHUNK + lane;
+                    cm &= cm - 1;
+                }
+                const int fc = min(f[g], F - 1);
+                fb[g] = face_box[fc];
+                i0[g] = P.faces[3 * fc]; i1[g] = P.faces[3 * fc + 1]; i2[g] = P.faces[3 * fc + 2];
+            }
+#pragma unroll
+            for (int g = 0; g < RD_GROUP; ++g) {
+                const bool hit = f[g] < F && meets(fb[g], tc0, tc1, tr0, tr1);
+                const unsigned long long m = __ballot(hit);
+                const int nh = __popcll(m);
+                if (nh == 0) continue;
+                if (count + nh > RD_CHUNK) {               // the list would overflow: walk it first
+                    __syncthreads();
+                    walk(rec, count, px, py, best);
+                    count = 0;
+                    __syncthreads();
+                }
+                if (hit) put_record(rec, count + __popcll(m & lane_lt), f[g], ndc[i0[g]], ndc[i1[g]], ndc[i2[g]]);
+                count += nh;
+            }
+        }
+    }
+    __syncthreads();
+    walk(rec, count, px, py, best);
+
+    // the part label as the shade forms iu[0], rounded half to even: convert_multiclass_to_binary_labels(iuv[..., 0].round()).  The
+    // nearest face decides even where its label rounds to 0 (a sliver whose area is just above 1e-8), as in hps_render's own image.
+    bool set = false;
+    if (inside && best.f >= 0) {
+        const int i0 = P.faces[3 * best.f], i1 = P.faces[3 * best.f + 1], i2 = P.faces[3 * best.f + 2];
+        const float part = best.w0 * P.verts_iuv[3 * (size_t)i0] + best.w1 * P.verts_iuv[3 * (size_t)i1] + best.w2 * P.verts_iuv[3 * (size_t)i2];
+        set = rintf(part) != 0.0f;
+    }
+    if (inside && P.mask_out) P.mask_out[(size_t)b * plane + pix] = set ? 1 : 0;
+    const int tp = __popcll(__ballot(inside && set && tgt)), fp = __popcll(__ballot(inside && set && !tgt));
+    const int tn = __popcll(__ballot(inside && !set && !tgt)), fn = __popcll(__ballot(inside && !set && tgt));
+    if (lane == 0) P.tile_counts[((size_t)b * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = make_int4(tp, fp, tn, fn);
+}
+
+// one workgroup per mesh; W <= 4096: no sum exceeds 2^24
+__global__ __launch_bounds__(256) void silhouette_reduce_kernel(const int4* __restrict__ tile_counts, int tiles2, int32_t* __restrict__ counts) {
+    __shared__ int4 part[256];
+    const int4* t = tile_counts + (size_t)blockIdx.x * tiles2;
+    int4 s = make_int4(0, 0, 0, 0);
+    for (int i = threadIdx.x; i < tiles2; i += 256) {
+        const int4 v = t[i];
+        s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+    }
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if ((int)threadIdx.x < off) {
+            const int4 v = part[threadIdx.x + off];
+            s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+            part[threadIdx.x] = s;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) reinterpret_cast<int4*>(counts)[blockIdx.x] = s;
+}
+
 }  // namespace hps
+
+extern "C" int hps_sizeof_silhouette_args(void) { return (int)sizeof(hps_silhouette_args); }
+
+extern "C" int hps_silhouette_iou(const hps_silhouette_args* a, hps_stream_t stream) {
+    using namespace hps;
+    if (!a) return bad_arg("hps_silhouette_iou: null pointer (args)");
+    if (a->struct_bytes != (int)sizeof(hps_silhouette_args))
+        return bad_arg("hps_silhouette_iou: struct_bytes is not sizeof(hps_silhouette_args)");
+    if (!a->vertices || !a->verts_map || !a->faces || !a->verts_iuv || !a->cam_t || !a->scale || !a->workspace)
+        return bad_arg("hps_silhouette_iou: null pointer (vertices, verts_map, faces, verts_iuv, cam_t, scale, workspace)");
+    if (!a->counts && !a->mask_out) return bad_arg("hps_silhouette_iou: no output wanted (counts and mask_out are both null)");
+    if (a->M < 1 || a->M > 65535 || a->W < 1 || a->W > 4096) return bad_arg("hps_silhouette_iou: M in [1, 65535], W in [1, 4096]");
+    if (a->group < 1 || a->M % a->group != 0) return bad_arg("hps_silhouette_iou: group >= 1 must divide M");
+    if (a->num_verts < 1 || a->num_dp_verts < 1 || a->num_faces < 1 || a->num_faces > (1 << 24))
+        return bad_arg("hps_silhouette_iou: num_verts, num_dp_verts >= 1, num_faces in [1, 2^24]");
+    if (a->projection != HPS_RENDER_PERSPECTIVE && a->projection != HPS_RENDER_ORTHOGRAPHIC)
+        return bad_arg("hps_silhouette_iou: unknown projection");
+    if ((a->cam_t_stride != 0 && a->cam_t_stride != 3) || (a->scale_stride != 0 && a->scale_stride != 2))
+        return bad_arg("hps_silhouette_iou: cam_t_stride is 0 or 3, scale_stride 0 or 2");
+    if ((reinterpret_cast<uintptr_t>(a->workspace) & 15) || (reinterpret_cast<uintptr_t>(a->counts) & 15))
+        return bad_arg("hps_silhouette_iou: workspace and counts must be 16-byte aligned");
+    const int M = a->M, W = a->W, Nd = a->num_dp_verts, F = a->num_faces;
+    const int chunks = ceil_div(F, RD_CHUNK), face_blocks = ceil_div(F, 256), vblocks = ceil_div(Nd, 256), tiles = ceil_div(W, RD_TILE);
+    const SilhouetteWs ws = carve_silhouette(a->workspace, M, Nd, F, W);
+    hipStream_t st = (hipStream_t)stream;
+
+    hipLaunchKernelGGL(silhouette_project_kernel, dim3(vblocks, M), dim3(256), 0, st, a->vertices, a->verts_map, a->cam_t,
+                       a->cam_t_stride, a->scale, a->scale_stride, a->projection == HPS_RENDER_PERSPECTIVE ? 1 : 0,
+                       a->flip_x_pi != 0 ? 1 : 0, a->group, a->num_verts, Nd, ws.ndc);
+    int rc = check_launch("hps_silhouette_iou (project)");
+    if (rc) return rc;
+    // gridDim.x == face_blocks: every workgroup takes the face branch, the vertex-normal half and its pointers are never touched
+    hipLaunchKernelGGL(render_setup_kernel, dim3(face_blocks, M), dim3(256), 0, st, a->faces, (const int32_t*)nullptr,
+                       (const int32_t*)nullptr, (const float4*)nullptr, ws.ndc, Nd, F, face_blocks, chunks, W, (float4*)nullptr,
+                       ws.face_box, ws.chunk_box);
+    rc = check_launch("hps_silhouette_iou (set-up)");
+    if (rc) return rc;
+    SilhouetteParams P;
+    P.faces = a->faces; P.ndc = ws.ndc; P.face_box = ws.face_box; P.chunk_box = ws.chunk_box; P.verts_iuv = a->verts_iuv;
+    P.target = a->target; P.Nd = Nd; P.F = F; P.chunks = chunks; P.W = W; P.group = a->group;
+    P.tile_counts = ws.tile_counts; P.mask_out = a->mask_out;
+    hipLaunchKernelGGL(silhouette_raster_kernel, dim3(tiles, tiles, M), dim3(64), 0, st, P);
+    rc = check_launch("hps_silhouette_iou (rasterise and count)");
+    if (rc || !a->counts) return rc;
+    hipLaunchKernelGGL(silhouette_reduce_kernel, dim3(M), dim3(256), 0, st, ws.tile_counts, tiles * tiles, a->counts);
+    return check_launch("hps_silhouette_iou (reduce)");
+}
 
 extern "C" int hps_sizeof_render_args(void) { return (int)sizeof(hps_render_args); }
 

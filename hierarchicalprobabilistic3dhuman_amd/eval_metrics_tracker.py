@@ -1,10 +1,18 @@
 """``EvalMetricsTracker`` with the interface of the reference's metrics/eval_metrics_tracker.py for the 3D metrics
 (PVE / PVE-SC / PVE-PA / PVE-T / PVE-T-SC / MPJPE / MPJPE-SC / MPJPE-PA and their ``*_samples_min`` forms) and
-joints2D-L2E, computed on the device (hps_pointset_errors) from device tensors.  Sums stay on the device as float64
-scalars; nothing is synchronised with the host until ``compute_final_metrics``.  ``reduce_across_ranks`` is the one
-collective of a multi-GPU evaluation.
+joints2D-L2E / joints2Dsamples-L2E, computed on the device (hps_pointset_errors) from device tensors, and for silhouette-IOU /
+silhouettesamples-IOU (:50-59, 294-330, 336-347).  Sums stay on the device as float64 scalars; nothing is synchronised with the
+host until ``compute_final_metrics``.  ``reduce_across_ranks`` is the one collective of a multi-GPU evaluation (SURVEY.md
+section 8(e)).
 
-Not implemented (out of scope, they need the pytorch3d renderer): silhouette-IOU, silhouettesamples-IOU.
+The silhouette metrics are tracked only by a tracker that was given a ``silhouette_renderer`` (a TexturedIUVRenderer: the package
+ships no DensePose asset, so without one nobody can make silhouettes, and the metric is refused with NotImplementedError).  Their
+predictions come in either form: the reference's masks, pred_dict['silhouettes'] (B,W,W) / ['silhouettessamples'] (B,N,W,W) with
+target_dict['silhouettes'] (B,W,W), counted here with tensor operations on the device; or the counts the renderer's
+``silhouette_counts`` has already made, pred_dict['silhouette_counts'] (B,4) / ['silhouettesamples_counts'] (B N,4), rows of
+[tp, fp, tn, fn].  The sums carry the reference's names, num_true_positives ... num_samples_false_negatives; they are whole numbers
+in float64, so they are exact and the same in any order.  The 2D-joint sums are added frame by frame in frame order, which makes
+them the same for any batch size.
 """
 import os
 
@@ -21,13 +29,30 @@ for _sfx, _mode in _MODES.items():
     _POINT_METRICS["MPJPE" + _sfx] = ("joints3D", "joints3D", _mode)
 _POINT_METRICS["PVE-T"] = ("reposed_verts", "reposed_verts", eval_utils.MODE_RAW)
 _POINT_METRICS["PVE-T-SC"] = ("reposed_verts", "reposed_verts", eval_utils.MODE_SC)
+# metric name -> its four sums, in the order of a counts row [tp, fp, tn, fn]
+_SILHOUETTE_SUMS = {"silhouette-IOU": tuple("num_%s" % k for k in ("true_positives", "false_positives", "true_negatives", "false_negatives")),
+                    "silhouettesamples-IOU": tuple("num_samples_%s" % k for k in ("true_positives", "false_positives", "true_negatives",
+                                                                                 "false_negatives"))}
+
+
+def silhouette_counts_from_masks(pred, target):
+    """:297-304 / :316-324 on the device: pred (B,W,W) or (B,N,W,W) masks against target (B,W,W), nonzero = foreground ->
+    (B,4) or (B N,4) int64 rows of [tp, fp, tn, fn]."""
+    pred = pred != 0
+    target = (target.to(pred.device) != 0)
+    if pred.dim() == 4:
+        target = target[:, None].expand_as(pred)
+    pairs = ((pred, target), (pred, ~target), (~pred, ~target), (~pred, target))
+    return torch.stack([(p & t).sum(dim=(-2, -1)) for p, t in pairs], dim=-1).reshape(-1, 4)
 
 
 class EvalMetricsTracker:
-    def __init__(self, metrics_to_track, img_wh=None, save_path=None, save_per_frame_metrics=False):
+    def __init__(self, metrics_to_track, img_wh=None, save_path=None, save_per_frame_metrics=False, silhouette_renderer=None):
         for m in metrics_to_track:
-            if "silhouette" in m:
-                raise NotImplementedError("%s needs the pytorch3d renderer, which is outside the hot path" % m)
+            if "silhouette" in m and silhouette_renderer is None:
+                raise NotImplementedError("%s needs a silhouette_renderer (textured_renderer.TexturedIUVRenderer, orthographic, built "
+                                          "from the DensePose UV asset this package does not ship)" % m)
+        self.silhouette_renderer = silhouette_renderer
         self.metrics_to_track = list(metrics_to_track)
         self.img_wh = img_wh
         self.metric_sums = None
@@ -40,7 +65,11 @@ class EvalMetricsTracker:
         for m in self.metrics_to_track:
             if m == "joints2Dsamples-L2E":
                 self.metric_sums["num_vis_joints2Dsamples"] = 0.0
-            self.metric_sums[m] = 0.0
+            if m in _SILHOUETTE_SUMS:                                               # :50-59: the IOU is formed from these at the end
+                for key in _SILHOUETTE_SUMS[m]:
+                    self.metric_sums[key] = 0.0
+            else:
+                self.metric_sums[m] = 0.0
 
     def initialise_per_frame_metric_lists(self):
         self.per_frame_metrics = {m: [] for m in self.metrics_to_track}
@@ -78,7 +107,7 @@ class EvalMetricsTracker:
                 self.per_frame_metrics[m].append((best / samples.shape[1]).reshape(1))
             elif m == "joints2D-L2E":
                 d = torch.linalg.norm(pred_dict["joints2D"].double() - target_dict["joints2D"].to(pred_dict["joints2D"].device).double(), dim=-1)
-                self.metric_sums[m] = self.metric_sums[m] + d.sum()
+                self._add_frame_by_frame(m, d.sum(dim=-1))
                 self.per_frame_metrics[m].append(d.mean(dim=-1))
                 if return_per_frame_metrics:
                     per_frame[m] = d.mean(dim=-1)
@@ -88,14 +117,35 @@ class EvalMetricsTracker:
                 d = torch.linalg.norm(pred - tgt, dim=-1)                       # (B,N,17)
                 if "joints2D_vis" in target_dict:
                     vis = target_dict["joints2D_vis"].to(pred.device)[:, None].expand(d.shape)
-                    self.metric_sums[m] = self.metric_sums[m] + (d * vis).sum()
+                    self._add_frame_by_frame(m, (d * vis).sum(dim=(1, 2)))
                     self.metric_sums["num_vis_joints2Dsamples"] = self.metric_sums["num_vis_joints2Dsamples"] + vis.sum()
                 else:
-                    self.metric_sums[m] = self.metric_sums[m] + d.sum()
+                    self._add_frame_by_frame(m, d.sum(dim=(1, 2)))
                     self.metric_sums["num_vis_joints2Dsamples"] = self.metric_sums["num_vis_joints2Dsamples"] + d.numel()
+            elif m in _SILHOUETTE_SUMS:
+                fused, masks = ("silhouette_counts", "silhouettes") if m == "silhouette-IOU" else ("silhouettesamples_counts",
+                                                                                                   "silhouettessamples")
+                if fused in pred_dict:
+                    counts = pred_dict[fused].reshape(-1, 4)
+                else:
+                    counts = silhouette_counts_from_masks(pred_dict[masks], target_dict["silhouettes"])
+                counts = counts.double()                                           # whole numbers below 2^53: every sum is exact
+                for k, key in enumerate(_SILHOUETTE_SUMS[m]):
+                    self.metric_sums[key] = self.metric_sums[key] + counts[:, k].sum()
+                if m == "silhouette-IOU":                                           # :309-312; 0 / 0 is NaN, as numpy gives the reference
+                    iou = counts[:, 0] / (counts[:, 0] + counts[:, 1] + counts[:, 3])
+                    self.per_frame_metrics[m].append(iou)
+                    if return_per_frame_metrics:
+                        per_frame[m] = iou
             else:
                 raise KeyError("unknown metric %r" % m)
         return transformed, per_frame
+
+    def _add_frame_by_frame(self, key, per_frame):
+        """Adds a (B,) float64 vector to a sum one frame after the other, in frame order: a float64 sum depends on the order of its
+        terms, and this order is the same whatever the batch size."""
+        for v in per_frame.unbind(0):
+            self.metric_sums[key] = self.metric_sums[key] + v
 
     # ------------------------------------------------------------------------------------------
     def reduce_across_ranks(self):
@@ -122,6 +172,9 @@ class EvalMetricsTracker:
             mult = 1.0
             if m == "joints2Dsamples-L2E":
                 final[m] = float(self.metric_sums[m]) / float(self.metric_sums["num_vis_joints2Dsamples"])
+            elif m in _SILHOUETTE_SUMS:                                             # :336-347: tp / (tp + fn + fp)
+                tp, fp, _, fn = (float(self.metric_sums[key]) for key in _SILHOUETTE_SUMS[m])
+                final[m] = tp / (tp + fn + fp) if tp + fn + fp else float("nan")
             else:
                 if "PVE" in m:
                     num_per_sample, mult = 6890, 1000.0

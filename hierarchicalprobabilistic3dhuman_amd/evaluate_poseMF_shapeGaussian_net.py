@@ -1,5 +1,6 @@
 """Dataset evaluation harness with the signature of the reference's
-evaluate/evaluate_poseMF_shapeGaussian_net.py:19-33, for the 3D metrics (BASELINE configs[3]: 3DPW with gendered SMPL).
+evaluate/evaluate_poseMF_shapeGaussian_net.py:19-33, for the 3D metrics (BASELINE configs[3]: 3DPW with gendered SMPL) and the
+silhouette / 2D-joint metrics of its shape benchmark (SSP-3D, run_evaluate.py:67-68).
 
 Per batch: Canny + heat-maps -> net -> SMPL(mode) -> SMPL(T-pose, mean shape) -> [N pose samples, N shape samples,
 SMPL(samples), SMPL(T-pose samples)] -> metrics on the device.  Differences from the reference, none of which change
@@ -14,19 +15,26 @@ for any world size and batch size.
 ``svd_mode`` selects the head's 3x3 SVD for this evaluation ("host": MKL sgesdd on the host, the reference's very routine;
 "device": the in-kernel restatement of sgesdd, bit-identical to this host's MKL in U, S and V once its rounding flavour is
 calibrated, _capi.svd_flavor).  Default: the model's own ``svd_mode`` -- except that the reference's seed-reproducible route
-(``sample_on_cpu``, run_evaluate.py:83-94) falls back to "host" on a machine whose LAPACK neither flavour reproduces.  The silhouette / 2D-joint metrics need the pytorch3d renderer and the detector
-outputs and are out of scope.
+(``sample_on_cpu``, run_evaluate.py:83-94) falls back to "host" on a machine whose LAPACK neither flavour reproduces.
 
-The 3DPW frames and the licensed SMPL_{MALE,FEMALE}.pkl files are external assets; any ``eval_dataset`` yielding the
-item dict of data/pw3d_eval_dataset.py:72-77 works (tests use a synthetic one).
+silhouette-IOU, silhouettesamples-IOU, joints2D-L2E and joints2Dsamples-L2E (:78-81, 112-115, 136-155, 181-204, 214-228) need
+``batch['keypoints']`` (B,17,2) and ``batch['silhouette']`` (B,W,W), W = DATA.PROXY_REP_SIZE.  The reference builds its silhouette
+renderer from configs.paths (:49-55); here the caller hands one in, ``silhouette_renderer``: an orthographic TexturedIUVRenderer with
+img_wh = DATA.PROXY_REP_SIZE (the DensePose UV asset is not shipped).  A frame's mode mesh and its N samples are never rendered to
+images: TexturedIUVRenderer.silhouette_counts rasterises, compares with the target and counts in one call per batch (B meshes) and
+one per batch of samples (B N meshes in groups of N), and the tracker adds the counts up.
+
+The 3DPW / SSP-3D frames and the licensed SMPL_{MALE,FEMALE}.pkl files are external assets; any ``eval_dataset`` yielding the
+item dict of data/pw3d_eval_dataset.py:72-77 (data/ssp3d_eval_dataset.py:87-94 for the 2D metrics) works (tests use synthetic ones).
 """
 import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from . import _capi, sharding
+from . import _capi, cam_utils, sharding
 from .eval_metrics_tracker import EvalMetricsTracker
-from .label_conversions import ALL_JOINTS_TO_H36M_MAP, H36M_TO_J14
+from .joints2d_utils import undo_keypoint_normalisation
+from .label_conversions import ALL_JOINTS_TO_COCO_MAP, ALL_JOINTS_TO_H36M_MAP, H36M_TO_J14
 from .rigid_transform_utils import batch_rodrigues, rot6d_to_rotmat
 from .sampling_utils import pose_matrix_fisher_sampling_torch, check_sampling, _philox_seed
 
@@ -83,7 +91,8 @@ class _StagedCollate:
 def evaluate_pose_MF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male, smpl_model_female,
                                        edge_detect_model, device, eval_dataset, metrics, save_path, num_workers=4,
                                        pin_memory=True, save_per_frame_metrics=True, num_samples_for_metrics=10,
-                                       sample_on_cpu=False, batch_size=1, reduce_across_ranks=True, svd_mode=None, seed=None):
+                                       sample_on_cpu=False, batch_size=1, reduce_across_ranks=True, svd_mode=None, seed=None,
+                                       silhouette_renderer=None):
     device = torch.device(device)
     if device.type == "cuda":
         torch.cuda.set_device(device)              # libhps launches on the current device's current stream
@@ -105,7 +114,11 @@ def evaluate_pose_MF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mo
     staged = _StagedCollate(pinned=device.type == "cuda") if num_workers == 0 else None
     loader = DataLoader(eval_dataset, batch_size=batch_size, shuffle=False, drop_last=False, num_workers=num_workers,
                         pin_memory=pin_memory and staged is None, collate_fn=staged)
-    tracker = EvalMetricsTracker(metrics, save_path=save_path, save_per_frame_metrics=save_per_frame_metrics)
+    tracker = EvalMetricsTracker(metrics, save_path=save_path, save_per_frame_metrics=save_per_frame_metrics,
+                                 silhouette_renderer=silhouette_renderer)
+    if silhouette_renderer is not None and any("silhouette" in m for m in metrics):
+        if silhouette_renderer.projection_type != "orthographic" or silhouette_renderer.img_wh != pose_shape_cfg.DATA.PROXY_REP_SIZE:
+            raise ValueError("silhouette_renderer must be orthographic with img_wh = DATA.PROXY_REP_SIZE (:50-55)")
     tracker.initialise_metric_sums()
     tracker.initialise_per_frame_metric_lists()
     want_samples = any("samples" in m for m in metrics)
@@ -138,8 +151,17 @@ def flipped_target_rotmats(target_pose, flip=None):
 
 def _evaluate_loop(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male, smpl_model_female, edge_detect_model, device,
                    loader, staged, tracker, metrics, want_samples, N, flip, fnames, poses, shapes, cams, sample_on_cpu, run_seed, frame0,
-                   reduce_across_ranks, save_per_frame_metrics, save_path, **_unused):
+                   reduce_across_ranks, save_per_frame_metrics, save_path, silhouette_renderer, **_unused):
     frame = frame0
+    want_joints2d, want_silhouettes = any("joints2D" in m for m in metrics), any("silhouette" in m for m in metrics)
+    wh = pose_shape_cfg.DATA.PROXY_REP_SIZE
+
+    def project_coco(joints, cam):
+        """:129, 137-142 / :182-190: all joints (M,J,3) -> COCO joints in pixels (M,17,2).  The predicted body is upside down where the
+        flipped targets are the right way up, so it is rotated by pi about x before the weak-perspective camera."""
+        coco = cam_utils.flip_about_x(joints[:, ALL_JOINTS_TO_COCO_MAP, :])
+        return undo_keypoint_normalisation(cam_utils.orthographic_project_torch(coco, cam), wh)
+
     for batch in loader:
         with torch.no_grad():
             image = batch["image"].to(device, non_blocking=True)
@@ -180,8 +202,21 @@ def _evaluate_loop(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male
             out_rest = smpl_model(betas=shape_dist.loc, body_pose=zeros69, global_orient=zeros3)
             pred = {"verts": out_mode.vertices, "reposed_verts": out_rest.vertices, "joints3D": _h36mlsp(out_mode.joints)}
             target = {"verts": target_vertices, "reposed_verts": target_reposed, "joints3D": target_joints}
+            if want_joints2d:                                                                             # :78-79, 214-216
+                target["joints2D"] = batch["keypoints"].to(device, non_blocking=True).float()
+            if "joints2D-L2E" in metrics:
+                pred["joints2D"] = project_coco(out_mode.joints, cam)
+            if want_silhouettes:                                                                          # :80-81, 112-115
+                target_silhouette = batch["silhouette"].to(device, non_blocking=True)
+                if target_silhouette.dtype not in (torch.bool, torch.uint8):
+                    target_silhouette = target_silhouette != 0
+                scale, cam_t = cam[:, [0, 0]].contiguous(), torch.cat([cam[:, 1:], torch.full_like(cam[:, :1], 2.5)], dim=-1)
+            if "silhouette-IOU" in metrics:                                                               # :143-155, 217-219
+                pred["silhouette_counts"] = silhouette_renderer.silhouette_counts(
+                    out_mode.vertices, target_silhouette, cam_t=cam_t, orthographic_scale=scale, flip=True)
             base_metrics = [m for m in metrics if "samples" not in m]
-            sample_metrics = [m for m in metrics if "samples" in m]
+            sample_metrics = [m for m in metrics if m.endswith("_samples_min")]                           # per frame
+            batch_sample_metrics = [m for m in metrics if "samples" in m and not m.endswith("_samples_min")]
             tracker.metrics_to_track = base_metrics
             tracker.update_per_batch(pred, target, B)
 
@@ -212,6 +247,20 @@ def _evaluate_loop(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male
                                               "joints3D_samples": joints_s[i]},
                                              {k: v[i:i + 1] for k, v in target.items()}, 1)
                 tracker.total_samples -= B                                       # already counted by the base update
+                pred_s = {}
+                if "joints2Dsamples-L2E" in metrics:                                                      # :181-190, 225-226
+                    # from the sample joints as SMPL gave them: the reference overwrites sample 0 of the VERTICES (:172) and of the
+                    # h36m joints (:174), never of pred_smpl_output_samples.joints, which :182 reads
+                    pred_s["joints2Dsamples"] = project_coco(out_s.joints, cam.repeat_interleave(N, dim=0)).view(B, N, 17, 2)
+                if "silhouettesamples-IOU" in metrics:                                                    # :192-204, 227-228
+                    # on the sample vertices WITH sample 0 replaced by the mode mesh: :172's pred_vertices_samples[0] =
+                    # pred_vertices_mode[0] writes into pred_smpl_output_samples.vertices itself (:171 takes no copy), and :195
+                    # reads that tensor.  verts_s is (B,N,V,3) contiguous: B N meshes in groups of N, one camera and target each
+                    pred_s["silhouettesamples_counts"] = silhouette_renderer.silhouette_counts(
+                        verts_s.view(B * N, -1, 3), target_silhouette, cam_t=cam_t, orthographic_scale=scale, group=N, flip=True)
+                if batch_sample_metrics:
+                    tracker.metrics_to_track = batch_sample_metrics
+                    tracker.update_per_batch(pred_s, target, 0)
             tracker.metrics_to_track = list(metrics)
             if save_per_frame_metrics:
                 fnames.extend(list(batch["fname"]))

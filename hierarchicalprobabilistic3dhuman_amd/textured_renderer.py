@@ -9,6 +9,9 @@ no_grad).  Any other setting raises NotImplementedError; there is no pytorch3d b
 
 The images are stored planar, (B,3,H,W), and returned as (B,H,W,3) views of that storage, so the training loop's
 ``.permute(0, 3, 1, 2).contiguous()`` copies nothing.  Output buffers are owned per batch size and overwritten by the next call.
+
+``silhouette_counts`` is the evaluation's use of the same rasteriser (evaluate/evaluate_poseMF_shapeGaussian_net.py:143-155, 192-203;
+include/hps.h: hps_silhouette_iou): the silhouette of every mesh compared with a target and counted, without an image in between.
 """
 import numpy as np
 import torch
@@ -118,6 +121,7 @@ class TexturedIUVRenderer(torch.nn.Module):
         self._lights = [f32(np.asarray(c, dtype=np.float32).reshape(-1, 3)) for c in
                         (light_t, light_ambient_color, light_diffuse_color, light_specular_color)]
         self._bufs = {}
+        self._silhouette_bufs = {}
 
     def to(self, device):
         if torch.device(device) != self.device:
@@ -234,6 +238,79 @@ class TexturedIUVRenderer(torch.nn.Module):
             raise _capi.HpsError("render_train_inputs needs a renderer built with render_rgb=True")
         bufs = self._render(vertices, textures, cam_t, orthographic_scale, lights_rgb_settings, verts_features, False, True)
         return bufs["iuv_train"], bufs["rgb"]
+
+    def _silhouette(self, vertices, target_silhouettes, cam_t, orthographic_scale, group, flip, want_counts, want_masks):
+        """hps_silhouette_iou into the buffers owned per (M, group): (counts or None, masks or None)."""
+        _capi.require_device(vertices, "vertices")
+        vertices = _capi.f32c(vertices)
+        if vertices.dim() != 3 or vertices.shape[2] != 3:
+            raise _capi.HpsError("vertices must be (M,N,3)")
+        M, V, W, group = vertices.shape[0], vertices.shape[1], self.img_wh, int(group)
+        if self._map_max >= V:
+            raise _capi.HpsError("verts_map names vertex %d, the meshes have %d" % (self._map_max, V))
+        if group < 1 or M % group != 0:
+            raise _capi.HpsError("group (%d) must divide the number of meshes (%d)" % (group, M))
+        bufs = self._silhouette_bufs.get((M, group))
+        if bufs is None:
+            nbytes = _capi.query_workspace(_capi.WS_SILHOUETTE, M, self._Nd, _capi.silhouette_d2(self._F, W))
+            bufs = dict(ws=torch.empty(nbytes // 4, device=self.device, dtype=torch.float32),
+                        counts=torch.empty(M, 4, device=self.device, dtype=torch.int32), masks=None)
+            self._silhouette_bufs[(M, group)] = bufs
+        if want_masks and bufs["masks"] is None:
+            bufs["masks"] = torch.empty(M, W, W, device=self.device, dtype=torch.uint8)
+        a = _capi.SilhouetteArgs()
+        a.struct_bytes = _capi._c.sizeof(_capi.SilhouetteArgs)
+        a.M, a.W, a.group, a.num_verts, a.num_dp_verts, a.num_faces = M, W, group, V, self._Nd, self._F
+        a.projection = _capi.RENDER_PERSPECTIVE if self.projection_type == "perspective" else _capi.RENDER_ORTHOGRAPHIC
+        a.flip_x_pi = 1 if flip else 0
+        P = _capi.ptr
+        keep = [vertices]                                  # what the argument block points to stays alive until the launches are issued
+
+        def per_group(t, width, what):
+            t = self._per_image(t, width, what)
+            if t.shape[0] not in (1, M // group):
+                raise _capi.HpsError("%s has %d rows, there are %d groups of meshes" % (what, t.shape[0], M // group))
+            keep.append(t)
+            return P(t), (0 if t.shape[0] == 1 else width)
+
+        a.cam_t, a.cam_t_stride = per_group(self._cam_t if cam_t is None else cam_t, 3, "cam_t")
+        scale = self._scale
+        if orthographic_scale is not None and self.projection_type == "orthographic":
+            scale = orthographic_scale
+        a.scale, a.scale_stride = per_group(scale, 2, "orthographic_scale")
+        a.vertices, a.verts_map, a.faces, a.verts_iuv = P(vertices), _capi.iptr(self._map), _capi.iptr(self._faces), P(self._iuv)
+        if target_silhouettes is not None:
+            _capi.require_device(target_silhouettes, "target_silhouettes")
+            t = target_silhouettes
+            if t.dtype not in (torch.bool, torch.uint8):
+                raise _capi.HpsError("target_silhouettes must be bool or uint8, got %s" % t.dtype)
+            if tuple(t.shape) != (M // group, W, W):
+                raise _capi.HpsError("target_silhouettes must be (%d,%d,%d)" % (M // group, W, W))
+            t = t.contiguous()
+            t = t.view(torch.uint8) if t.dtype == torch.bool else t                 # True is stored as the byte 1
+            keep.append(t)
+            a.target = P(t, torch.uint8, "target_silhouettes")
+        a.workspace = P(bufs["ws"])
+        if want_counts:
+            a.counts = _capi.iptr(bufs["counts"])
+        if want_masks:
+            a.mask_out = P(bufs["masks"], torch.uint8)
+        _capi.call("hps_silhouette_iou", _capi._c.addressof(a), _capi.stream())
+        return (bufs["counts"] if want_counts else None), (bufs["masks"] if want_masks else None)
+
+    def silhouette_counts(self, vertices, target_silhouettes=None, cam_t=None, orthographic_scale=None, group=1, flip=False,
+                          return_silhouettes=False):
+        """The silhouette metrics' pixel counts (evaluate/evaluate_poseMF_shapeGaussian_net.py:143-155, 192-203 with
+        metrics/eval_metrics_tracker.py:294-304) in one call of hps_silhouette_iou, whatever ``render_rgb`` the renderer was built
+        with: ``vertices`` (M,N,3) in groups of ``group`` consecutive meshes (a frame's samples); group g is seen by row g of
+        ``cam_t`` / ``orthographic_scale`` (or their one shared row) and scored against ``target_silhouettes[g]`` ((M/group,W,W) bool
+        or uint8, nonzero = foreground; None: every pixel counts as background).  ``flip``: the meshes are rotated by pi about x
+        first, as the reference does before it renders.  A pixel is set where round(iuv_images[..., 0]) != 0 in forward()'s image,
+        bit for bit.  Returns counts (M,4) int32 = [tp, fp, tn, fn] on the device -- with ``return_silhouettes`` (counts, masks
+        (M,W,W) uint8 of 0 / 1).  The buffers are owned per (M, group) and overwritten by the next call."""
+        counts, masks = self._silhouette(vertices, target_silhouettes, cam_t, orthographic_scale, group, flip, True,
+                                         bool(return_silhouettes))
+        return (counts, masks) if return_silhouettes else counts
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -104,10 +104,12 @@ int hps_stream_destroy(hps_stream_t stream);
  *                                                               workspace of hps_head_trunk_backward
  *   HPS_WS_SEG_BBOX    (d0 = B)                                 ws of hps_seg_bbox_affine (per-chunk integer box corners)
  *   HPS_WS_RENDER      (d0 = B, d1 = DensePose vertices, d2 = faces)  workspace of hps_render
+ *   HPS_WS_SILHOUETTE  (d0 = M, d1 = DensePose vertices, d2 = HPS_WS_SILHOUETTE_D2(faces, W))  workspace of hps_silhouette_iou
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
        HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
-       HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13, HPS_WS_RENDER = 14 };
+       HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13, HPS_WS_RENDER = 14,
+       HPS_WS_SILHOUETTE = 15 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -1134,6 +1136,49 @@ typedef struct hps_render_args {
 } hps_render_args;
 int hps_sizeof_render_args(void);
 int hps_render(const hps_render_args* args, hps_stream_t stream);
+
+/* Silhouette counts for the SSP-3D metrics  (evaluate/evaluate_poseMF_shapeGaussian_net.py:143-155, 192-203;
+ * metrics/eval_metrics_tracker.py:294-328; csrc/render.hip).  M meshes in groups of `group` consecutive ones (a frame's mode mesh,
+ * group 1, or its N samples, group N): mesh m is seen by camera row m / group of cam_t / scale (stride 3 / 2, or 0 = shared) and
+ * scored against target image m / group.  With flip_x_pi != 0 a vertex is taken as (x, -y, -z) before the camera -- the reference's
+ * rotation by pi about x (:144-147, :195-198); a negation is exact, so this is hps_render on vertices flipped beforehand.
+ *   mask     pixel (r, c) of mesh m is set iff hps_render's rasteriser finds a face there (every coverage, area, z, pz and depth rule
+ *            above; the nearest face wins, on equal depth the lower index) AND round_half_even(w0 I0 + w1 I1 + w2 I2) != 0, the sum
+ *            formed as hps_render forms its I plane: convert_multiclass_to_binary_labels(iuv_images[..., 0].round()) (:153-155), bit
+ *            for bit the mask hps_render's own iuv gives.  Only the I column of verts_iuv (num_dp_verts, 3) is read.
+ *   target   (M / group, W, W) uint8, nonzero = foreground; NULL = no target (every pixel counts as background: fp = the set
+ *            pixels, tn = the rest, tp = fn = 0).
+ *   counts   (M, 4) int32 = [tp, fp, tn, fn] of each mesh against its target, tp + fp + tn + fn = W^2; 16-byte aligned.
+ *   mask_out (M, W, W) uint8 holding 0 / 1.  counts and mask_out may each be NULL, not both.
+ * Four launches (project; face and chunk boxes -- hps_render's set-up without its vertex normals; rasterise and count, one 16-byte
+ * store per 8 x 8 tile; add a mesh's tile counts), three without counts; no atomics, no image is written but mask_out, bitwise
+ * repeatable, nothing allocated.
+ * workspace is hps_query_workspace(HPS_WS_SILHOUETTE, M, num_dp_verts, HPS_WS_SILHOUETTE_D2(num_faces, W)) bytes, 16-byte aligned.
+ * The tile counts are 16 bytes per tile: sized for the largest image (512 x 512 tiles) they would be 4 MiB per mesh, more than
+ * everything else in the workspace by two orders of magnitude, so the query takes W -- packed into d2 above the face count, which
+ * is at most 2^24: d2 = num_faces + W * 2^32.
+ * M in [1, 65535], group >= 1 dividing M, W in [1, 4096], num_faces <= 2^24; HPS_E_BADARG otherwise, before any launch.
+ * struct_bytes = sizeof(hps_silhouette_args) as the caller compiled it. */
+#define HPS_WS_SILHOUETTE_D2(num_faces, W) ((int64_t)(num_faces) + ((int64_t)(W) << 32))
+typedef struct hps_silhouette_args {
+    int struct_bytes;
+    int M, W, group;
+    int num_verts, num_dp_verts, num_faces;
+    int projection;                                            /* HPS_RENDER_* */
+    int flip_x_pi;
+    int cam_t_stride, scale_stride;                            /* floats between GROUPS: 3 / 2, or 0 = shared */
+    const float* vertices;                                     /* (M, num_verts, 3) */
+    const int32_t* verts_map;                                  /* (num_dp_verts) */
+    const int32_t* faces;                                      /* (num_faces, 3) */
+    const float* verts_iuv;                                    /* (num_dp_verts, 3) */
+    const float *cam_t, *scale;
+    const uint8_t* target;                                     /* (M / group, W, W) or NULL */
+    void* workspace;
+    int32_t* counts;                                           /* (M, 4) or NULL */
+    uint8_t* mask_out;                                         /* (M, W, W) or NULL */
+} hps_silhouette_args;
+int hps_sizeof_silhouette_args(void);
+int hps_silhouette_iou(const hps_silhouette_args* args, hps_stream_t stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
