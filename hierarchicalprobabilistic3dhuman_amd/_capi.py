@@ -125,6 +125,8 @@ _PROTOTYPES = {
     "hps_render": [_P, _P],
     "hps_sizeof_silhouette_args": [],
     "hps_silhouette_iou": [_P, _P],
+    "hps_sizeof_train_metrics_args": [],
+    "hps_train_metrics_update": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -186,6 +188,15 @@ class SilhouetteArgs(_c.Structure):
         (n, _P) for n in ("vertices", "verts_map", "faces", "verts_iuv", "cam_t", "scale", "target", "workspace", "counts", "mask_out")]
 
 
+class TrainMetricsArgs(_c.Structure):
+    """include/hps.h: hps_train_metrics_args (struct_bytes = ctypes.sizeof(TrainMetricsArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "P", "J", "K", "N", "batch_size", "mask", "split", "num_status")] + [
+        ("img_wh", _c.c_float)] + [
+        (n, _P) for n in ("pred_verts", "target_verts", "pred_reposed", "target_reposed", "pred_joints3d", "target_joints3d",
+                          "pred_joints2d", "target_joints2d", "pred_joints2d_samples", "vis", "loss", "status", "workspace", "sums")]
+
+
+TRAIN_METRICS_NSLOT = 14
 RENDER_PERSPECTIVE, RENDER_ORTHOGRAPHIC = 0, 1
 ADAM_CHUNK = 4096
 REFRESH_PERMUTE, REFRESH_FOLD, REFRESH_WINO_U, REFRESH_STEM_U = 0, 1, 2, 3
@@ -391,6 +402,7 @@ WS_HEAD_LEVELS_BWD, WS_HEAD_TRUNK_BWD = 11, 12
 WS_SEG_BBOX = 13
 WS_RENDER = 14
 WS_SILHOUETTE = 15
+WS_TRAIN_METRICS = 16
 
 
 def silhouette_d2(num_faces, W):

@@ -20,8 +20,8 @@ SMPLX_EXTRA_VERTEX_IDS = [332, 6260, 2800, 4071, 583,
                           6191, 5782, 5905, 6016, 6133]
 
 
-def _loss_stage(overreg, pose, shape, joints2d, glob_rotmats, verts3d, joints3d):
-    return SimpleNamespace(REDUCTION="mean", MF_OVERREG=overreg,
+def _loss_stage(overreg, pose, shape, joints2d, glob_rotmats, verts3d, joints3d, j2d_loss_on):
+    return SimpleNamespace(REDUCTION="mean", MF_OVERREG=overreg, J2D_LOSS_ON=j2d_loss_on,
                            WEIGHTS=SimpleNamespace(POSE=pose, SHAPE=shape, JOINTS2D=joints2d, GLOB_ROTMATS=glob_rotmats,
                                                    VERTS3D=verts3d, JOINTS3D=joints3d))
 
@@ -49,14 +49,17 @@ def _synth_data():
 def get_cfg_defaults():
     """Values of configs/poseMF_shapeGaussian_net_config.py:8-24 that the inference path reads, of :83-110 that
     matrix_fisher_loss.PoseMFShapeGaussianLoss reads (LOSS.STAGE1 / STAGE2: REDUCTION, MF_OVERREG, WEIGHTS), and of :29, :36-80 that
-    the synthetic-data training front end reads (TRAIN.BATCH_SIZE, TRAIN.SYNTH_DATA)."""
+    the synthetic-data training front end reads (TRAIN.BATCH_SIZE, TRAIN.SYNTH_DATA), and of :28-33, :84-86, :91, :103 that the
+    training loop reads (TRAIN.NUM_EPOCHS ... NUM_WORKERS, LOSS.SAMPLE_ON_CPU / NUM_SAMPLES / STAGE_CHANGE_EPOCH, J2D_LOSS_ON)."""
     return SimpleNamespace(
         MODEL=SimpleNamespace(NUM_IN_CHANNELS=18, NUM_RESNET_LAYERS=18, EMBED_DIM=256,
                               DELTA_I=True, DELTA_I_WEIGHT=1.0, NUM_SMPL_BETAS=10),
         DATA=SimpleNamespace(PROXY_REP_SIZE=256, HEATMAP_GAUSSIAN_STD=4.0, EDGE_NMS=True,
                              EDGE_THRESHOLD=0.0, EDGE_GAUSSIAN_STD=1.0, EDGE_GAUSSIAN_SIZE=5,
                              BBOX_THRESHOLD=0.95, BBOX_SCALE_FACTOR=1.2),
-        LOSS=SimpleNamespace(STAGE1=_loss_stage(1.005, 80.0, 50.0, 5000.0, 5000.0, 0.0, 0.0),
-                             STAGE2=_loss_stage(1.005, 10.0, 80.0, 30000.0, 5000.0, 5000.0, 5000.0)),
-        TRAIN=SimpleNamespace(BATCH_SIZE=72, SYNTH_DATA=_synth_data()),
+        LOSS=SimpleNamespace(SAMPLE_ON_CPU=True, NUM_SAMPLES=8, STAGE_CHANGE_EPOCH=66,
+                             STAGE1=_loss_stage(1.005, 80.0, 50.0, 5000.0, 5000.0, 0.0, 0.0, "means"),
+                             STAGE2=_loss_stage(1.005, 10.0, 80.0, 30000.0, 5000.0, 5000.0, 5000.0, "means+samples")),
+        TRAIN=SimpleNamespace(NUM_EPOCHS=300, BATCH_SIZE=72, LR=0.0001, EPOCHS_PER_SAVE=5, PIN_MEMORY=True, NUM_WORKERS=2,
+                              SYNTH_DATA=_synth_data()),
     )

@@ -43,6 +43,7 @@ extern "C" int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t
             if (faces > (1 << 24) || W < 1 || W > 4096) { hps::set_error("hps_query_workspace: HPS_WS_SILHOUETTE takes d2 = faces + W * 2^32 with faces <= 2^24, W in [1, 4096]"); return -1; }
             return hps::silhouette_ws_bytes(d0, d1, faces, W);
         }
+        case HPS_WS_TRAIN_METRICS: return hps::train_metrics_ws_bytes(d0);
         default: hps::set_error("hps_query_workspace: unknown item %d", what); return -1;
     }
 }

@@ -28,6 +28,8 @@ int64_t head_trunk_backward_ws_bytes(int64_t B, int64_t wide, int64_t nt);
 int64_t render_ws_bytes(int64_t B, int64_t Nd, int64_t F);
 // bytes of the hps_silhouette_iou workspace (csrc/render.hip; HPS_WS_SILHOUETTE)
 int64_t silhouette_ws_bytes(int64_t M, int64_t Nd, int64_t F, int64_t W);
+// bytes of the hps_train_metrics_update workspace (csrc/metrics.hip; HPS_WS_TRAIN_METRICS)
+int64_t train_metrics_ws_bytes(int64_t B);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -105,11 +105,12 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_SEG_BBOX    (d0 = B)                                 ws of hps_seg_bbox_affine (per-chunk integer box corners)
  *   HPS_WS_RENDER      (d0 = B, d1 = DensePose vertices, d2 = faces)  workspace of hps_render
  *   HPS_WS_SILHOUETTE  (d0 = M, d1 = DensePose vertices, d2 = HPS_WS_SILHOUETTE_D2(faces, W))  workspace of hps_silhouette_iou
+ *   HPS_WS_TRAIN_METRICS (d0 = B)                               workspace of hps_train_metrics_update
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
        HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
        HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13, HPS_WS_RENDER = 14,
-       HPS_WS_SILHOUETTE = 15 };
+       HPS_WS_SILHOUETTE = 15, HPS_WS_TRAIN_METRICS = 16 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -1179,6 +1180,60 @@ typedef struct hps_silhouette_args {
 } hps_silhouette_args;
 int hps_sizeof_silhouette_args(void);
 int hps_silhouette_iou(const hps_silhouette_args* args, hps_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Training loss-and-metrics tracker  (metrics/train_loss_and_metrics_tracker.py)
+ * ---------------------------------------------------------------------------------------- */
+
+/* One training or validation step of TrainingLossesAndMetricsTracker.update_per_batch (:113-196): every tracked metric of the batch is
+ * formed on the device and added into running float64 sums that stay there until the epoch ends (the reference copies four (B,6890,3)
+ * tensors to the host, calls loss.item() and runs numpy Procrustes every step, and keeps float32 sums).
+ *   mask     HPS_TRAIN_METRIC_* bits, in the order of the reference's all_metrics_types.  Inputs that no set bit needs may be NULL.
+ *   point sets  pred_verts / target_verts (B,P,3) for PVE, PVE-SC, PVE-PA (:118-138); pred_reposed / target_reposed (B,P,3) for PVE-T,
+ *            PVE-T-SC (:141-150); pred_joints3d / target_joints3d (B,J,3) for MPJPE, MPJPE-SC, MPJPE-PA (:152-174).  B counts sets
+ *            after the reference's reshape(-1, P, 3).  The arithmetic is hps_pointset_errors' (float64 statistics, the transform as 12
+ *            floats, sqrtf per point, float64 sums in the same lane and tree order): a set's sum in a mode has the bits
+ *            hps_pointset_errors gives for that set.  One statistics pass per family serves SC and PA; one workgroup forms the raw,
+ *            SC and PA sums of a set, so the set comes from HBM once (three walks of hps_pointset_errors' own error loop -- the one
+ *            body of machine code that has its bits -- of which the second and third find the set in the cache).
+ *   2-D      pred_joints2d (B,K,2) normalised to [-1, 1], target_joints2d (B,K,2) in pixels: joints2D-L2E adds, over all B K joints,
+ *            || (x + 1) img_wh / 2 - target || (:176-181).  pred_joints2d_samples (B,N,K,2), vis (B,K) bytes: joints2Dsamples-L2E adds
+ *            the same over the visible joints of every sample, and their number B-wise sum(vis) N to its own slot (:183-196).
+ *   loss     one device float; slot 0 receives (double)loss * batch_size (:114), slot 1 batch_size (:115).
+ *   status   optional (num_status,) int32 (the synthetic front end's empty-box words): the number of non-zero words is added to the
+ *            last slot.  NULL with num_status = 0: the slot is not touched.
+ *   sums     (2, HPS_TRAIN_METRICS_NSLOT) double, row `split` (0 train, 1 val) is updated: slot 0 loss * batch_size, 1 samples,
+ *            2 + b the metric of mask bit b, 12 visible joint samples, 13 non-zero status words.  Only the slots named by the call
+ *            are written; the other row is not touched.  The caller zeroes sums at the start of an epoch.
+ *   workspace  hps_query_workspace(HPS_WS_TRAIN_METRICS, B) bytes, 8-byte aligned.  After the call it holds the per-set values that
+ *            were summed: double stats[3][B][17], double part[3][B][3] (family, set, mode), double j2d[B][3] (L2E, samples L2E,
+ *            visible count), float xf[3][B][3][12]; entries of untracked metrics are not written.
+ * Four launches whatever the mask (statistics; transforms; errors with the 2-D joints as a fourth grid row; one workgroup that adds the
+ * per-set values in set order and then does sums[split][slot] += value, one lane per slot).  No atomics, bitwise repeatable, nothing
+ * allocated, no host round trip.  HPS_E_BADARG before any launch: struct_bytes, B < 1, batch_size < 1, split outside {0, 1}, a mask bit
+ * outside the ten, NULL for an input a set bit needs, P / J / K / N < 1 where used, img_wh <= 0 with a 2-D bit. */
+enum { HPS_TRAIN_METRIC_PVE = 1, HPS_TRAIN_METRIC_PVE_SC = 2, HPS_TRAIN_METRIC_PVE_PA = 4, HPS_TRAIN_METRIC_PVE_T = 8,
+       HPS_TRAIN_METRIC_PVE_T_SC = 16, HPS_TRAIN_METRIC_MPJPE = 32, HPS_TRAIN_METRIC_MPJPE_SC = 64, HPS_TRAIN_METRIC_MPJPE_PA = 128,
+       HPS_TRAIN_METRIC_J2D = 256, HPS_TRAIN_METRIC_J2D_SAMPLES = 512, HPS_TRAIN_METRIC_ALL = 1023 };
+#define HPS_TRAIN_METRICS_NSLOT 14
+typedef struct hps_train_metrics_args {
+    int struct_bytes;
+    int B, P, J, K, N;
+    int batch_size, mask, split, num_status;
+    float img_wh;
+    const float *pred_verts, *target_verts;                    /* (B, P, 3) */
+    const float *pred_reposed, *target_reposed;                /* (B, P, 3) */
+    const float *pred_joints3d, *target_joints3d;              /* (B, J, 3) */
+    const float *pred_joints2d, *target_joints2d;              /* (B, K, 2) */
+    const float* pred_joints2d_samples;                        /* (B, N, K, 2) */
+    const uint8_t* vis;                                        /* (B, K) */
+    const float* loss;
+    const int32_t* status;                                     /* (num_status) or NULL */
+    void* workspace;
+    double* sums;                                              /* (2, HPS_TRAIN_METRICS_NSLOT) */
+} hps_train_metrics_args;
+int hps_sizeof_train_metrics_args(void);
+int hps_train_metrics_update(const hps_train_metrics_args* args, hps_stream_t stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
