@@ -127,6 +127,12 @@ _PROTOTYPES = {
     "hps_silhouette_iou": [_P, _P],
     "hps_sizeof_train_metrics_args": [],
     "hps_train_metrics_update": [_P, _P],
+    "hps_sizeof_vis_views_args": [],
+    "hps_vis_views": [_P, _P],
+    "hps_sizeof_vis_compose_args": [],
+    "hps_vis_compose": [_P, _P],
+    "hps_sizeof_vis_uncrop_args": [],
+    "hps_vis_uncrop": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -196,6 +202,37 @@ class TrainMetricsArgs(_c.Structure):
                           "pred_joints2d", "target_joints2d", "pred_joints2d_samples", "vis", "loss", "status", "workspace", "sums")]
 
 
+class VisView(_c.Structure):
+    """include/hps.h: hps_vis_view."""
+    _fields_ = [("vertices", _P), ("var", _P), ("yaw", _I), ("camera", _I)]
+
+
+class VisViewsArgs(_c.Structure):
+    """include/hps.h: hps_vis_views_args (struct_bytes = ctypes.sizeof(VisViewsArgs); the library rejects any other value)."""
+    _fields_ = [("struct_bytes", _I), ("num_views", _I), ("num_verts", _I), ("constant", _c.c_float), ("fixed_cam_t", _c.c_float * 3),
+                ("fixed_scale", _c.c_float), ("cam_z", _c.c_float), ("views", _c.POINTER(VisView))] + [
+        (n, _P) for n in ("lut", "cam", "out_vertices", "out_colours", "out_cam_t", "out_scale")]
+
+
+class VisPanel(_c.Structure):
+    """include/hps.h: hps_vis_panel."""
+    _fields_ = [(n, _I) for n in ("kind", "row", "col", "render")]
+
+
+class VisComposeArgs(_c.Structure):
+    """include/hps.h: hps_vis_compose_args (struct_bytes = ctypes.sizeof(VisComposeArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "rows", "cols", "wh", "num_panels", "num_renders", "D", "proxy_channels", "num_joints")] + [
+        ("panels", _c.POINTER(VisPanel))] + [(n, _P) for n in ("rgb", "iuv", "crop", "proxy", "joints", "out")]
+
+
+class VisUncropArgs(_c.Structure):
+    """include/hps.h: hps_vis_uncrop_args (struct_bytes = ctypes.sizeof(VisUncropArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "H", "W", "wh")] + [
+        (n, _P) for n in ("rgb", "iplane", "image", "bbox_centre", "bbox_wh", "out")]
+
+
+VIS_MAX_VIEWS, VIS_MAX_CELLS = 32, 32
+VIS_PANEL_RENDER, VIS_PANEL_RENDER_OVER_CROP, VIS_PANEL_CROP, VIS_PANEL_PROXY = 0, 1, 2, 3
 TRAIN_METRICS_NSLOT = 14
 RENDER_PERSPECTIVE, RENDER_ORTHOGRAPHIC = 0, 1
 ADAM_CHUNK = 4096

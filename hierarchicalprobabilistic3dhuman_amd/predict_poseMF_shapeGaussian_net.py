@@ -5,8 +5,10 @@ with the reference's signature (:19-32) that feeds it.
 Everything between the proxy representation and the sampled meshes runs on the device through
 libhps.so.  The front end before it (:61-100) is assembled from the injected ``hrnet_model`` / ``object_detect_model``
 (the detectors themselves are out of scope), the crop glue of image_utils / predict_hrnet
-and the Canny / heat-map kernels of SURVEY 8(f)1; ``proxy_rep_fn`` may replace it.  What comes after (rendering, PNG
-writing; :167-333) is out of scope (rows 14, 20): results go to ``result_fn`` or to .pt files.
+and the Canny / heat-map kernels of SURVEY 8(f)1; ``proxy_rep_fn`` may replace it.  Results go to ``result_fn`` or to .pt files;
+with ``vis_renderer=`` the reference's three pictures per image (:149-333: the eight-panel figure, the body over the original
+photograph, the sample sheet) are written beside them as PNG files by visualise.PredictVisualiser (DESIGN.md section 8 row (f)16;
+section 9 for what stays out: the text labels of the proxy panel, JPEG output).
 """
 import os
 import weakref
@@ -644,8 +646,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                                      edge_detect_model, device, image_dir, save_dir, object_detect_model=None,
                                      joints2Dvisib_threshold=0.75, visualise_wh=512, visualise_uncropped=True,
                                      visualise_samples=False, proxy_rep_fn=None, num_samples=50, batch_size=1,
-                                     result_fn=None):
-    """Signature of predict/predict_poseMF_shapeGaussian_net.py:19-32 plus three keyword extensions.
+                                     result_fn=None, vis_renderer=None):
+    """Signature of predict/predict_poseMF_shapeGaussian_net.py:19-32 plus keyword extensions.
 
     Called exactly like the reference (run_predict.py:77-89) it runs the reference's front end (:61-100) on the injected
     ``hrnet_model`` / ``object_detect_model`` (any callables with the reference's interfaces) and ``edge_detect_model``
@@ -653,6 +655,16 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     optionally replaces that whole front end.  result_fn(image_name, result_dict) receives the
     outputs instead of the reference's pytorch3d renderer; by default vertices / joints / uncertainties are
     saved as <save_dir>/<image>.pt.
+
+    ``vis_renderer``: a textured_renderer.TexturedIUVRenderer built with projection_type='orthographic', render_rgb=True and
+    img_wh=visualise_wh (the DensePose asset is not shipped, so the caller brings the renderer, as the evaluation's
+    ``silhouette_renderer=``).  With it the reference's pictures (:149-333) are written for every image, beside the .pt / result_fn
+    delivery, which does not change: <save_dir>/<stem>.png (the eight-panel figure), <stem>_uncrop.png if ``visualise_uncropped``
+    and <stem>_samples.png if ``visualise_samples``.  Always PNG: the reference reuses the input's file name, which makes a lossy
+    JPEG of a .jpg input.  Without it ``visualise_wh`` / ``visualise_uncropped`` / ``visualise_samples`` have no effect.
+    A custom ``proxy_rep_fn`` may return a dict with ``proxy_rep`` and, for the pictures, ``cropped_rgb`` (1,3,D,D), ``joints2D``
+    (1,K,2) in crop pixels, ``image`` (3,H,W) float in [0,1], ``bbox_centre`` (2,) and ``bbox_wh`` (max(h, w) BBOX_SCALE_FACTOR),
+    all on the device; a bare tensor gives black crop panels, no joint discs and no uncropped picture (one warning).
     """
     device = torch.device(device)
     if device.type == "cuda":
@@ -663,6 +675,42 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         proxy_rep_fn = _reference_front_end(pose_shape_cfg, hrnet_model, hrnet_cfg, edge_detect_model,
                                             object_detect_model, joints2Dvisib_threshold, device)
     os.makedirs(save_dir, exist_ok=True)
+    vis = writer = None
+    extras = {}                                          # image name -> what the front end kept for the pictures
+    if vis_renderer is not None:
+        from .visualise import PngWriter, predict_visualiser
+        vis, writer = predict_visualiser(vis_renderer, pose_shape_cfg, visualise_wh), PngWriter()
+    warned = []
+
+    def get_proxy(name):
+        """proxy_rep_fn's tensor for one image; a dict's other entries are kept for the pictures until the image is delivered."""
+        fn = getattr(proxy_rep_fn, "with_extras", proxy_rep_fn) if vis is not None else proxy_rep_fn
+        out = fn(os.path.join(image_dir, name))
+        if isinstance(out, dict):
+            if vis is not None:
+                extras[name] = out
+            return out["proxy_rep"]
+        if vis is not None:
+            extras[name] = {"proxy_rep": out}
+        return out
+
+    def visualise(name, item):
+        ex = extras.pop(name)
+        stem = os.path.join(save_dir, os.path.splitext(name)[0])
+        proxy = ex["proxy_rep"]
+        if not proxy.is_cuda:
+            proxy = proxy.to(device, non_blocking=True)
+        crop, joints = ex.get("cropped_rgb"), ex.get("joints2D")
+        writer.write(vis.figure(item, crop, proxy.float(), joints), stem + ".png")
+        if visualise_uncropped:
+            if all(ex.get(k) is not None for k in ("image", "bbox_centre", "bbox_wh")):
+                writer.write(vis.uncropped(ex["image"], ex["bbox_centre"], ex["bbox_wh"]), stem + "_uncrop.png")
+            elif not warned:
+                import warnings
+                warned.append(True)
+                warnings.warn("predict: proxy_rep_fn gave no image / bbox_centre / bbox_wh; the uncropped pictures are skipped")
+        if visualise_samples:
+            writer.write(vis.samples_figure(item, crop, proxy.float()), stem + "_samples.png")
     # The loop is software-pipelined (InferencePipeline): while batch k's head, sampling and meshes run, batch k+1's proxy
     # representations are already staged (page-locked host tensors go up by non-blocking copies on a copy stream, StagedUpload)
     # and its encoder is enqueued.  Same results as infer() per batch.
@@ -680,6 +728,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                 keep = ("verts_mode", "joints_mode", "verts_tpose", "unc", "cam", "glob_rotmats")
                 torch.save({key: item[key].cpu() for key in keep},
                            os.path.join(save_dir, os.path.splitext(n)[0] + ".pt"))
+            if vis is not None:
+                visualise(n, item)
 
     if batch_size <= 2 and device.type == "cuda":
         # The reference's own operating point -- one image per call (:58-59) -- is latency-bound: ~50 launches of a few microseconds
@@ -703,8 +753,10 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                 res_p = {key: (val.clone() if torch.is_tensor(val) else val) for key, val in res_p.items()}
             deliver(names_p, res_p)
         for gi, names in enumerate(groups):
-            items = [proxy_rep_fn(os.path.join(image_dir, n)).float() for n in names]
+            items = [get_proxy(n).float() for n in names]
             if len(items) == batch_size and tuple(items[0].shape[1:]) == graphed.input_shape:
+                if writer is not None and graphed._slots[graphed._k % len(graphed._slots)] is None:
+                    writer.drain()                       # a capture is coming: no other thread may call the runtime during it
                 nxt = (names,) + graphed(items, wait=False)
             else:                                        # a last, smaller group / another image size: the eager path
                 x = torch.cat([t.to(device) for t in items], dim=0)
@@ -717,6 +769,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         finish_pending(pending)
         graphed.check_sampling()
         check_sampling()
+        if writer is not None:
+            writer.close()
         return
     # the pipeline (its streams, the encoder's frame buffers bound to them, the upload slots) is kept between calls, per model (weakly
     # referenced side table: nothing is attached to the module, so copies / pickles of it are unaffected)
@@ -731,7 +785,7 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     _, pipe, stager = cached
 
     def stage(names):
-        items = [proxy_rep_fn(os.path.join(image_dir, n)) for n in names]
+        items = [get_proxy(n) for n in names]
         if all(t.is_cuda for t in items):                # built on the device (the reference front end): ordered by submit()'s default event
             return pipe.submit(torch.cat([t.float() for t in items], dim=0) if len(items) > 1 else items[0].float())
         proxy, ready = stager.upload_rows([t.float() for t in items])
@@ -750,6 +804,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
             deliver(names, res)
         check_sampling()
     torch.cuda.current_stream().wait_stream(pipe.caller_stream(batch_size))
+    if writer is not None:
+        writer.close()
 
 
 def load_rgb_image(path):
@@ -798,7 +854,7 @@ def _reference_front_end(pose_shape_cfg, hrnet_model, hrnet_cfg, edge_detect_mod
         return d.view(chw.shape)
 
     @torch.no_grad()
-    def front_end(image_path):
+    def run(image_path, extras):
         rgb_u8 = load_rgb_image(image_path).transpose(2, 0, 1)
         if torch.device(device).type == "cuda":
             image = upload_u8(rgb_u8).float() / 255.0                                                               # :63-65
@@ -816,6 +872,16 @@ def _reference_front_end(pose_shape_cfg, hrnet_model, hrnet_cfg, edge_detect_mod
                                             bbox_widths=height.clone(), orig_scale_factor=1.0)                      # :82-91
         visib = hr["joints2Dconfs"] > joints2Dvisib_threshold                                                      # :98
         visib[[0, 1, 2, 3, 4, 5, 6, 11, 12]] = True                                                                # :99
-        return proxy_representation(cropped["rgb"], cropped["joints2D"], visib[None], edge_detect_model, pose_shape_cfg)
+        proxy = proxy_representation(cropped["rgb"], cropped["joints2D"], visib[None], edge_detect_model, pose_shape_cfg)
+        if not extras:
+            return proxy
+        # what the pictures need beside the network's input (:198-201, :248-250, :280-292)
+        side = torch.max(hr["bbox_height"], hr["bbox_width"]).reshape(1).float() * pose_shape_cfg.DATA.BBOX_SCALE_FACTOR
+        return {"proxy_rep": proxy, "cropped_rgb": cropped["rgb"], "joints2D": cropped["joints2D"], "image": image,
+                "bbox_centre": hr["bbox_centre"].reshape(2).float(), "bbox_wh": side}
 
+    def front_end(image_path):
+        return run(image_path, False)
+
+    front_end.with_extras = lambda image_path: run(image_path, True)      # predict_poseMF_shapeGaussian_net(vis_renderer=...) takes the dict
     return front_end

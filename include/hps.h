@@ -1235,6 +1235,115 @@ typedef struct hps_train_metrics_args {
 int hps_sizeof_train_metrics_args(void);
 int hps_train_metrics_update(const hps_train_metrics_args* args, hps_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The predict visualisations  (predict/predict_poseMF_shapeGaussian_net.py:149-333; csrc/visualise.hip)
+ * ---------------------------------------------------------------------------------------- */
+
+/* The layer between hps_render's planes and a PNG.  One launch each, no atomics, nothing allocated, bitwise repeatable, all on the
+ * caller's stream; bad arguments return HPS_E_BADARG before any launch.  The `views` and `panels` tables are HOST arrays, read during
+ * the call (they travel as kernel arguments); every other pointer is device memory.
+ *
+ * hps_vis_views  (:116-147, :174-190)  the vertex and colour buffers of every view of a figure, laid out as one hps_render batch:
+ * out_vertices, out_colours (num_views, num_verts, 3).  View i reads the mesh views[i].vertices (num_verts, 3):
+ *   position   first (x, y, z) -> (x, -y, -z), then yaw times (x, y, z) -> (-z, y, x): the reference's rotation by pi about x and by
+ *              -pi / 2 about y with the trigonometry exact.  A view is a signed permutation of the coordinates; yaw 0 is bit for bit
+ *              what hps_silhouette_iou's flip_x_pi sees.
+ *   colour     views[i].var == NULL: `constant` on all three channels (the reference's 0.7 plain texture; it renders those views
+ *              through a constant UV texture, here they take the per-vertex route so that all views share one render call -- the two
+ *              routes differ by rounding in the interpolation of a constant only).  Otherwise var (num_verts) is the per-vertex
+ *              variance and the colour is plt.cm.jet(plt.Normalize(0, 0.2, clip=True)(var))[:, :3] (:188-190): float64 arithmetic on
+ *              the float32 value -- clip to [0, 0.2], / 0.2, * 256, truncate, 256 -> 255 -- and a look-up in lut (256, 3) float32
+ *              (the colour map's table, built by the caller).  NaN gives (0, 0, 0).
+ *   camera     out_cam_t (num_views, 3) and out_scale (num_views, 2) are hps_render's per-image cam_t and scale: a view with camera 1
+ *              gets the predicted weak-perspective camera cam = [s, tx, ty] as [tx, ty, cam_z] and [s, s] (:151-154), a view with
+ *              camera 0 gets fixed_cam_t and [fixed_scale, fixed_scale] (:51-52).
+ * num_views in [1, HPS_VIS_MAX_VIEWS], yaw in [0, 3], num_verts in [1, 2^24]. */
+#define HPS_VIS_MAX_VIEWS 32
+typedef struct hps_vis_view {
+    const float* vertices;                                     /* (num_verts, 3) */
+    const float* var;                                          /* (num_verts) or NULL = the constant colour */
+    int yaw;
+    int camera;                                                /* 0 = the fixed camera, 1 = the predicted one */
+} hps_vis_view;
+typedef struct hps_vis_views_args {
+    int struct_bytes;
+    int num_views, num_verts;
+    float constant;
+    float fixed_cam_t[3], fixed_scale, cam_z;
+    const hps_vis_view* views;                                 /* HOST (num_views) */
+    const float* lut;                                          /* (256, 3) */
+    const float* cam;                                          /* (3) = [s, tx, ty], or NULL when no view uses it */
+    float *out_vertices, *out_colours;                         /* (num_views, num_verts, 3) */
+    float *out_cam_t, *out_scale;                              /* (num_views, 3), (num_views, 2); both NULL = not wanted */
+} hps_vis_views_args;
+int hps_sizeof_vis_views_args(void);
+int hps_vis_views(const hps_vis_views_args* args, hps_stream_t stream);
+
+/* hps_vis_compose  (:198-205, :236-274, :303-333)  a finished figure out (rows wh, cols wh, 3) uint8, RGB interleaved, from a list of
+ * panels; panel p fills grid cell (row, col), cells that no panel names are zero:
+ *   RENDER            the planar float rgb (num_renders, 3, wh, wh) of render `render`.
+ *   RENDER_OVER_CROP  that render where round_half_even(iuv[render][0]) != 0, elsewhere the CROP value (batch_add_rgb_background on
+ *                     iuv_images[..., 0].round(), :202-204); iuv is hps_render's (num_renders, 3, wh, wh).
+ *   CROP              crop (3, D, D) resized to wh as F.interpolate(mode='bilinear', align_corners=False) samples it (:198-201):
+ *                     output index i reads position max((i + 0.5) D / wh - 0.5, 0), the upper neighbour clamped to D - 1;
+ *                     h0 (w0 v00 + w1 v01) + h1 (w0 v10 + w1 v11) in float32.  crop == NULL: black.
+ *   PROXY             the sum over proxy's (proxy_channels, D, D) channels, resized with the same positions (cv2.resize's
+ *                     INTER_LINEAR, :245-247), grey on three channels; then a filled red disc, dx^2 + dy^2 <= 9, at
+ *                     (int(x wh / D), int(y wh / D)) (float64, as Python forms it) for each of joints (num_joints, 2) (:248-255;
+ *                     joints == NULL: none).  The joint numbers and confidences of :256-263 are NOT drawn.
+ * Every value v becomes clamp(rint(255 v), 0, 255), rint to even -- what cv2.imwrite does to a float image (a disc is (255, 0, 0)).
+ * A lane produces 16 consecutive bytes of the figure and stores one dwordx4; out is 16-byte aligned.  rows cols <= HPS_VIS_MAX_CELLS,
+ * wh in [1, 4096], the figure smaller than 2^31 bytes, D in [1, 8192]. */
+#define HPS_VIS_MAX_CELLS 32
+#define HPS_VIS_PANEL_RENDER 0
+#define HPS_VIS_PANEL_RENDER_OVER_CROP 1
+#define HPS_VIS_PANEL_CROP 2
+#define HPS_VIS_PANEL_PROXY 3
+typedef struct hps_vis_panel {
+    int kind;                                                  /* HPS_VIS_PANEL_* */
+    int row, col;
+    int render;                                                /* RENDER, RENDER_OVER_CROP: index into rgb / iuv */
+} hps_vis_panel;
+typedef struct hps_vis_compose_args {
+    int struct_bytes;
+    int rows, cols, wh;
+    int num_panels, num_renders;
+    int D, proxy_channels, num_joints;
+    const hps_vis_panel* panels;                               /* HOST (num_panels) */
+    const float *rgb, *iuv;                                    /* (num_renders, 3, wh, wh) */
+    const float* crop;                                         /* (3, D, D) or NULL */
+    const float* proxy;                                        /* (proxy_channels, D, D) */
+    const float* joints;                                       /* (num_joints, 2) or NULL */
+    uint8_t* out;                                              /* (rows wh, cols wh, 3) */
+} hps_vis_compose_args;
+int hps_sizeof_vis_compose_args(void);
+int hps_vis_compose(const hps_vis_compose_args* args, hps_stream_t stream);
+
+/* hps_vis_uncrop  (:278-300; utils/image_utils.py:195-229 with uncrop=True)  the render projected back onto the photograph:
+ * out (H, W, 3) uint8 from rgb (3, wh, wh), iplane (wh, wh) (plane 0 of hps_render's iuv), the float photograph image (3, H, W) in
+ * [0, 1], bbox_centre (2) = (vertical, horizontal) and bbox_wh (1) = max(h, w) BBOX_SCALE_FACTOR, both device floats.  For every pixel
+ * of the photograph the position in the render follows cv2.warpAffine's arithmetic as we understand it -- these rules have NOT been
+ * run against OpenCV itself:
+ *   matrix    float32, as the reference builds it: m00 = m11 = side / wh, t = centre[::-1] - (side / wh) (wh / 2); inverted in float64
+ *             the way warpAffine inverts (D = 1 / det, A11 = m11 D, ..., b = -A t).
+ *   position  per column rint(M x 1024), per row rint((M y + b) 1024), plus 512 for the nearest look-up or 16 for the linear one;
+ *             nearest index: >> 10; linear: >> 5, then the index is >> 5 and the fraction & 31 thirty-seconds; the four taps carry
+ *             float32 weights (1 - fy)(1 - fx), ...; anything outside the render reads 0.
+ * The part plane is looked up nearest, the colour linearly.  Where I == 0 the output is the photograph's own pixel, rint(255 image)
+ * (exact for an image that was uint8 / 255); elsewhere rint(255 rgb), saturated.  A lane produces 16 consecutive bytes; out is
+ * 16-byte aligned.  wh in [1, 4096], H and W in [1, 32767]. */
+typedef struct hps_vis_uncrop_args {
+    int struct_bytes;
+    int H, W, wh;
+    const float* rgb;                                          /* (3, wh, wh) */
+    const float* iplane;                                       /* (wh, wh) */
+    const float* image;                                        /* (3, H, W) */
+    const float *bbox_centre, *bbox_wh;                        /* (2), (1) */
+    uint8_t* out;                                              /* (H, W, 3) */
+} hps_vis_uncrop_args;
+int hps_sizeof_vis_uncrop_args(void);
+int hps_vis_uncrop(const hps_vis_uncrop_args* args, hps_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
