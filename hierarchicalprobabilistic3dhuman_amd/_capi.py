@@ -133,6 +133,14 @@ _PROTOTYPES = {
     "hps_vis_compose": [_P, _P],
     "hps_sizeof_vis_uncrop_args": [],
     "hps_vis_uncrop": [_P, _P],
+    "hps_sizeof_c16_problem": [],
+    "hps_conv2d_bn_act_c16": [_P, _I, _P],
+    "hps_hrnet_pack_input": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "hps_hrnet_unpack_output": [_P, _P, _I, _I, _I, _I, _I, _P],
+    "hps_sizeof_hrnet_fuse_args": [],
+    "hps_hrnet_fuse": [_P, _P],
+    "hps_sizeof_hrnet_op": [],
+    "hps_hrnet_run": [_P, _I, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -231,6 +239,26 @@ class VisUncropArgs(_c.Structure):
         (n, _P) for n in ("rgb", "iplane", "image", "bbox_centre", "bbox_wh", "out")]
 
 
+class C16Problem(_c.Structure):
+    """include/hps.h: hps_c16_problem."""
+    _fields_ = [(n, _P) for n in ("x", "w", "scale", "shift", "residual", "y")] + [
+        (n, _I) for n in ("B", "H", "W", "ipad", "Cin", "Cout", "K", "stride", "opad", "relu")]
+
+
+class HrnetFuseArgs(_c.Structure):
+    """include/hps.h: hps_hrnet_fuse_args."""
+    _fields_ = [("term", _P * 4), ("shift", _I * 4), ("pad", _I * 4), ("n_terms", _I), ("y", _P)] + [
+        (n, _I) for n in ("opad", "B", "H", "W", "C", "relu")]
+
+
+class HrnetOp(_c.Structure):
+    """include/hps.h: hps_hrnet_op."""
+    _fields_ = [("kind", _I), ("n_problems", _I), ("conv", C16Problem * 4), ("fuse", HrnetFuseArgs), ("x", _P), ("y", _P)] + [
+        (n, _I) for n in ("B", "H", "W", "C", "P")]
+
+
+C16_MAX_PROBLEMS, HRNET_MAX_TERMS = 4, 4
+HRNET_PACK, HRNET_CONV, HRNET_FUSE, HRNET_UNPACK = 0, 1, 2, 3
 VIS_MAX_VIEWS, VIS_MAX_CELLS = 32, 32
 VIS_PANEL_RENDER, VIS_PANEL_RENDER_OVER_CROP, VIS_PANEL_CROP, VIS_PANEL_PROXY = 0, 1, 2, 3
 TRAIN_METRICS_NSLOT = 14

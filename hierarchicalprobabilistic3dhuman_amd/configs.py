@@ -46,6 +46,39 @@ def _synth_data():
                                                    CAM=SimpleNamespace(XY_STD=0.05, DELTA_Z_RANGE=[-0.5, 0.5])))  # :48-49
 
 
+class _Bag(dict):
+    """A dict whose keys are also attributes, like a yacs CfgNode: models/pose2D_hrnet.py indexes its config (cfg['MODEL']['EXTRA']),
+    predict/predict_hrnet.py reads attributes (hrnet_config.MODEL.IMAGE_SIZE)."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name)
+
+    def __setattr__(self, name, value):
+        self[name] = value
+
+    def __deepcopy__(self, memo):
+        import copy
+        return _Bag((k, copy.deepcopy(v, memo)) for k, v in self.items())
+
+
+def get_pose2D_hrnet_cfg_defaults():
+    """The values of configs/pose2D_hrnet_config.py:17-55 (HRNet-W48 at 384 x 288), as an attribute / index bag; a fresh object per call."""
+    def stage(modules, branches, blocks, channels):
+        return _Bag(NUM_MODULES=modules, NUM_BRANCHES=branches, BLOCK="BASIC", NUM_BLOCKS=list(blocks), NUM_CHANNELS=list(channels),
+                    FUSE_METHOD="SUM")
+    extra = _Bag(PRETRAINED_LAYERS=["conv1", "bn1", "conv2", "bn2", "layer1", "transition1", "stage2", "transition2", "stage3",
+                                    "transition3", "stage4"],
+                 FINAL_CONV_KERNEL=1,
+                 STAGE2=stage(1, 2, [4, 4], [48, 96]),
+                 STAGE3=stage(4, 3, [4, 4, 4], [48, 96, 192]),
+                 STAGE4=stage(3, 4, [4, 4, 4, 4], [48, 96, 192, 384]))
+    return _Bag(MODEL=_Bag(NUM_JOINTS=17, IMAGE_SIZE=[288, 384], HEATMAP_SIZE=[72, 96], EXTRA=extra),     # width, height
+                TEST=_Bag(POST_PROCESS=False, OBJECT_DET_THRESH=0.95))
+
+
 def get_cfg_defaults():
     """Values of configs/poseMF_shapeGaussian_net_config.py:8-24 that the inference path reads, of :83-110 that
     matrix_fisher_loss.PoseMFShapeGaussianLoss reads (LOSS.STAGE1 / STAGE2: REDUCTION, MF_OVERREG, WEIGHTS), and of :29, :36-80 that

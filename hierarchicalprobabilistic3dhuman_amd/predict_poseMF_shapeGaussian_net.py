@@ -650,7 +650,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     """Signature of predict/predict_poseMF_shapeGaussian_net.py:19-32 plus keyword extensions.
 
     Called exactly like the reference (run_predict.py:77-89) it runs the reference's front end (:61-100) on the injected
-    ``hrnet_model`` / ``object_detect_model`` (any callables with the reference's interfaces) and ``edge_detect_model``
+    ``hrnet_model`` / ``object_detect_model`` (any callables with the reference's interfaces; the device implementation of the
+    former is pose2D_hrnet.PoseHighResolutionNet) and ``edge_detect_model``
     (canny_edge_detector.CannyEdgeDetector), image files read by cv2 or PIL.  proxy_rep_fn(image_path) -> (1,18,D,D) tensor
     optionally replaces that whole front end.  result_fn(image_name, result_dict) receives the
     outputs instead of the reference's pytorch3d renderer; by default vertices / joints / uncertainties are

@@ -1344,6 +1344,81 @@ typedef struct hps_vis_uncrop_args {
 int hps_sizeof_vis_uncrop_args(void);
 int hps_vis_uncrop(const hps_vis_uncrop_args* args, hps_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * HRNet 2D keypoint detector, inference forward  (models/pose2D_hrnet.py:426-461)
+ * ---------------------------------------------------------------------------------------- */
+
+/* Grouped convolution for 16-channel granularity (csrc/conv_c16.hip): the HRNet layers the encoder's kernels do not take (branch
+ * widths 48 and 96, maps of 96 x 72 ... 12 x 9 pixels, the 17-channel final 1x1).  One launch runs 1 to HPS_C16_MAX_PROBLEMS
+ * INDEPENDENT problems (the branches of a HighResolutionModule at the same block depth, :252-253); workgroups find their problem
+ * from the block index in a descriptor table passed by value (no device allocation).  Per problem
+ *     y = act(conv(x, w) * scale + shift [+ residual])
+ * on the halo-padded NHWC frames of hps_conv2d_bn_act_pad: x (B, H + 2 ipad, W + 2 ipad, Cin) with a ZERO halo, ipad >= pad = K / 2;
+ * y and residual (B, Ho + 2 opad, Wo + 2 opad, Cout), only y's interior is written, opad arbitrary.  K (= KH = KW) 1 or 3, stride 1
+ * or 2, Cin % 16 == 0, any Cout >= 1, any H, W >= 1, B >= 0 (0: skipped).  w: (K * K, ceil16(Cout), Cin) -- tap-major in the order
+ * (kh, kw), then output channel, input channel fastest; rows Cout .. ceil16(Cout) - 1 are zero (the host pads, the kernel masks the
+ * tail).  scale / shift: (Cout), the folded BatchNorm, or scale = 1 and shift = bias for a convolution with a bias and no
+ * BatchNorm (the final layer, :324-330).  x and w 16-byte aligned; with Cout % 4 == 0 also y, residual, scale, shift.
+ * fp32 operands, fp32 accumulation on v_mfma_f32_16x16x4_f32, no atomics: bitwise repeatable.
+ * SUMMATION ORDER of one output (the layer alone decides it -- never B, the tile an output lands in, or the other problems of the
+ * launch; an image has the same bits alone and in a batch, a problem the same bits alone and in a group): accumulator 0; the taps in
+ * the order (kh, kw); within a tap the 16-channel chunks c0 = 0, 16, ...; within a chunk four steps t = 0..3, each ONE matrix
+ * instruction that adds the products of channels c0 + t, c0 + 4 + t, c0 + 8 + t, c0 + 12 + t to the accumulator; then
+ * fma(acc, scale, shift), + residual, max(., 0).  Lane offsets are 32-bit: frames < 2^31 floats. */
+#define HPS_C16_MAX_PROBLEMS 4
+typedef struct hps_c16_problem {
+    const float* x;
+    const float* w;
+    const float* scale;
+    const float* shift;
+    const float* residual;                                     /* or NULL */
+    float* y;
+    int B, H, W, ipad, Cin, Cout, K, stride, opad, relu;
+} hps_c16_problem;
+int hps_sizeof_c16_problem(void);
+int hps_conv2d_bn_act_c16(const hps_c16_problem* problems /* HOST */, int n_problems, hps_stream_t stream);
+
+/* The network input (:427): x (B, 3, H, W) NCHW -> the interior of the stem's frame y (B, H + 2 P, W + 2 P, CP), channels 0..2 and a
+ * zero in channel 3 (one 16-byte store per pixel; CP % 4 == 0); the frame's other channels and its halo are the owner's zeros, part
+ * of the convolution's zero padding.  With CP = 16 the 3 -> 64 stem is a hps_conv2d_bn_act_c16 problem like any other. */
+int hps_hrnet_pack_input(const float* x, float* y, int B, int H, int W, int CP, int P, hps_stream_t stream);
+/* The heat maps (:459-461): the interior of the NHWC frame x (B, H + 2 P, W + 2 P, C) -> y (B, C, H, W) NCHW. */
+int hps_hrnet_unpack_output(const float* x, float* y, int B, int H, int W, int C, int P, hps_stream_t stream);
+
+/* The fuse step of a HighResolutionModule (:255-264): y = act(((term0 + term1) + term2) + term3) on y's (B, H + 2 opad, W + 2 opad, C)
+ * frame, interior only.  term k is a frame (B, (H >> shift_k) + 2 pad_k, (W >> shift_k) + 2 pad_k, C) read at (h >> shift_k,
+ * w >> shift_k): shift 0 is a map of y's own resolution (the branch itself, or the end of a 3x3 / 2 chain), shift s the 1x1 + BN
+ * output of a lower branch under nn.Upsample(scale_factor = 2^s, mode = 'nearest'), which is never materialised.  The additions run
+ * in TERM ORDER, the reference's j order.  1 to HPS_HRNET_MAX_TERMS terms, C % 4 == 0, 2^shift_k divides H and W. */
+#define HPS_HRNET_MAX_TERMS 4
+typedef struct hps_hrnet_fuse_args {
+    const float* term[HPS_HRNET_MAX_TERMS];
+    int shift[HPS_HRNET_MAX_TERMS];
+    int pad[HPS_HRNET_MAX_TERMS];
+    int n_terms;
+    float* y;
+    int opad, B, H, W, C, relu;
+} hps_hrnet_fuse_args;
+int hps_sizeof_hrnet_fuse_args(void);
+int hps_hrnet_fuse(const hps_hrnet_fuse_args* args /* HOST */, hps_stream_t stream);
+
+/* The forward as one call (as hps_encoder_run: issuing ~130 launches through a scripting-language FFI costs more host time than the
+ * GPU needs for them): ops[0..n_ops) in order on `stream`, the same launches as the individual entry points.  HPS_HRNET_PACK =
+ * hps_hrnet_pack_input (x, y, B, H, W, C = CP, P), HPS_HRNET_CONV = hps_conv2d_bn_act_c16 (conv, n_problems), HPS_HRNET_FUSE =
+ * hps_hrnet_fuse (fuse), HPS_HRNET_UNPACK = hps_hrnet_unpack_output (x, y, B, H, W, C, P). */
+enum { HPS_HRNET_PACK = 0, HPS_HRNET_CONV = 1, HPS_HRNET_FUSE = 2, HPS_HRNET_UNPACK = 3 };
+typedef struct hps_hrnet_op {
+    int kind;
+    int n_problems;
+    hps_c16_problem conv[HPS_C16_MAX_PROBLEMS];
+    hps_hrnet_fuse_args fuse;
+    const float* x;
+    float* y;
+    int B, H, W, C, P;
+} hps_hrnet_op;
+int hps_sizeof_hrnet_op(void);
+int hps_hrnet_run(const hps_hrnet_op* ops /* HOST */, int n_ops, hps_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
