@@ -141,6 +141,12 @@ _PROTOTYPES = {
     "hps_hrnet_fuse": [_P, _P],
     "hps_sizeof_hrnet_op": [],
     "hps_hrnet_run": [_P, _I, _P],
+    "hps_sizeof_predict_boxes_args": [],
+    "hps_predict_boxes": [_P, _P],
+    "hps_sizeof_crop_bilinear_args": [],
+    "hps_crop_bilinear": [_P, _P],
+    "hps_sizeof_hrnet_keypoints_args": [],
+    "hps_hrnet_keypoints": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -255,6 +261,39 @@ class HrnetOp(_c.Structure):
     """include/hps.h: hps_hrnet_op."""
     _fields_ = [("kind", _I), ("n_problems", _I), ("conv", C16Problem * 4), ("fuse", HrnetFuseArgs), ("x", _P), ("y", _P)] + [
         (n, _I) for n in ("B", "H", "W", "C", "P")]
+
+
+FRONTEND_MAX_IMAGES, FRONTEND_RECORD_FLOATS = 64, 12
+FRONTEND_SRC_HWC_U8, FRONTEND_SRC_CHW_F32 = 0, 1
+
+
+class BoxImage(_c.Structure):
+    """include/hps.h: hps_box_image."""
+    _fields_ = [("boxes", _P), ("labels", _P), ("scores", _P), ("n", _I), ("H", _I), ("W", _I), ("reserved", _I)]
+
+
+class PredictBoxesArgs(_c.Structure):
+    """include/hps.h: hps_predict_boxes_args (struct_bytes = ctypes.sizeof(PredictBoxesArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "out_w", "out_h", "hrnet_aspect_fix")] + [
+        ("threshold", _c.c_float), ("scale_factor", _c.c_float), ("records", _P), ("image", BoxImage * FRONTEND_MAX_IMAGES)]
+
+
+class CropImage(_c.Structure):
+    """include/hps.h: hps_crop_image."""
+    _fields_ = [("src", _P), ("H", _I), ("W", _I), ("kind", _I), ("reserved", _I)]
+
+
+class CropBilinearArgs(_c.Structure):
+    """include/hps.h: hps_crop_bilinear_args (struct_bytes = ctypes.sizeof(CropBilinearArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "out_w", "out_h")] + [("mean", _c.c_float * 3), ("std", _c.c_float * 3)] + [
+        (n, _P) for n in ("records", "raw", "normalised")] + [("image", CropImage * FRONTEND_MAX_IMAGES)]
+
+
+class HrnetKeypointsArgs(_c.Structure):
+    """include/hps.h: hps_hrnet_keypoints_args (struct_bytes = ctypes.sizeof(HrnetKeypointsArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "K", "h", "w")] + [("factor", _c.c_float), ("vis_threshold", _c.c_float),
+                                                                          ("always_visible", _c.c_uint32)] + [
+        (n, _P) for n in ("heatmaps", "records", "joints_hrnet", "confs", "joints_crop", "visib")]
 
 
 C16_MAX_PROBLEMS, HRNET_MAX_TERMS = 4, 4

@@ -1,8 +1,10 @@
 """Bounding-box cropping by an affine resample: the part of the reference's utils/image_utils.py the predict front end
 uses (batch_crop_pytorch_affine :234-372 with given boxes, convert_bbox_corners_to_centre_hw_torch :25-42).
 
-This is glue AROUND the hot path (it feeds the injected HRNet and the Canny / heat-map kernels); it runs on the device
-with torch's own affine_grid / grid_sample, like the reference -- PyTorch as plumbing, no libhps kernel involved.
+This is the PER-IMAGE form, with the reference's call surface: it runs on the device with torch's own affine_grid / grid_sample,
+like the reference -- PyTorch as plumbing, no libhps kernel involved.  The predict loop uses it only when the injected key-point
+detector is not the device HRNet; with the device HRNet the same box arithmetic and resample run for a whole batch of photographs
+as the kernels hps_predict_boxes / hps_crop_bilinear (predict_frontend.py, csrc/predict_frontend.hip).
 """
 import torch
 import torch.nn.functional as F

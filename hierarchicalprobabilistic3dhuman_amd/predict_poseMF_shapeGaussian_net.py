@@ -3,9 +3,11 @@ predict/predict_poseMF_shapeGaussian_net.py:103-165 (``infer``) and a ``predict_
 with the reference's signature (:19-32) that feeds it.
 
 Everything between the proxy representation and the sampled meshes runs on the device through
-libhps.so.  The front end before it (:61-100) is assembled from the injected ``hrnet_model`` / ``object_detect_model``
-(the detectors themselves are out of scope), the crop glue of image_utils / predict_hrnet
-and the Canny / heat-map kernels of SURVEY 8(f)1; ``proxy_rep_fn`` may replace it.  Results go to ``result_fn`` or to .pt files;
+libhps.so.  The front end before it (:61-100) runs on the device for a whole group of images when the key-point detector is the
+device HRNet (predict_frontend.DevicePredictFrontEnd: box, crops and key points are the kernels of csrc/predict_frontend.hip, one
+HRNet forward per group); with any other injected ``hrnet_model`` it is assembled per image from
+``hrnet_model`` / ``object_detect_model`` (the person detector itself is out of scope), the torch crop
+glue of image_utils / predict_hrnet and the Canny / heat-map kernels of SURVEY 8(f)1; ``proxy_rep_fn`` may replace it.  Results go to ``result_fn`` or to .pt files;
 with ``vis_renderer=`` the reference's three pictures per image (:149-333: the eight-panel figure, the body over the original
 photograph, the sample sheet) are written beside them as PNG files by visualise.PredictVisualiser (DESIGN.md section 8 row (f)16;
 section 9 for what stays out: the text labels of the proxy panel, JPEG output).
@@ -646,7 +648,7 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                                      edge_detect_model, device, image_dir, save_dir, object_detect_model=None,
                                      joints2Dvisib_threshold=0.75, visualise_wh=512, visualise_uncropped=True,
                                      visualise_samples=False, proxy_rep_fn=None, num_samples=50, batch_size=1,
-                                     result_fn=None, vis_renderer=None):
+                                     result_fn=None, vis_renderer=None, batched_front_end=None):
     """Signature of predict/predict_poseMF_shapeGaussian_net.py:19-32 plus keyword extensions.
 
     Called exactly like the reference (run_predict.py:77-89) it runs the reference's front end (:61-100) on the injected
@@ -666,13 +668,26 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     A custom ``proxy_rep_fn`` may return a dict with ``proxy_rep`` and, for the pictures, ``cropped_rgb`` (1,3,D,D), ``joints2D``
     (1,K,2) in crop pixels, ``image`` (3,H,W) float in [0,1], ``bbox_centre`` (2,) and ``bbox_wh`` (max(h, w) BBOX_SCALE_FACTOR),
     all on the device; a bare tensor gives black crop panels, no joint discs and no uncropped picture (one warning).
+
+    ``batched_front_end``: None runs the front end of a whole group of ``batch_size`` images on the device with ONE HRNet forward
+    (predict_frontend.DevicePredictFrontEnd: box, crops and key points are libhps kernels, no host synchronisation of its own) when it
+    can -- no ``proxy_rep_fn``, a GPU device, ``hrnet_model`` a pose2D_hrnet.PoseHighResolutionNet and an ``edge_detect_model`` with
+    ``edge_map_into`` -- and the per-image route of predict_hrnet / image_utils otherwise; True demands it (HpsError when it cannot be
+    used), False forbids it.
     """
     device = torch.device(device)
+    batched = None
+    if use_batched_front_end(batched_front_end, proxy_rep_fn, device, hrnet_model, edge_detect_model):
+        from .predict_frontend import DevicePredictFrontEnd
+        if device.type == "cuda":
+            torch.cuda.set_device(device)
+        batched = DevicePredictFrontEnd(pose_shape_cfg, hrnet_model, hrnet_cfg, edge_detect_model, object_detect_model,
+                                        joints2Dvisib_threshold, device)
     if device.type == "cuda":
         torch.cuda.set_device(device)              # libhps launches on the current device's current stream
     pose_shape_model.eval()
     image_fnames = sorted(f for f in os.listdir(image_dir) if f.lower().endswith((".png", ".jpg", ".jpeg", ".npy")))
-    if proxy_rep_fn is None:
+    if proxy_rep_fn is None and batched is None:
         proxy_rep_fn = _reference_front_end(pose_shape_cfg, hrnet_model, hrnet_cfg, edge_detect_model,
                                             object_detect_model, joints2Dvisib_threshold, device)
     os.makedirs(save_dir, exist_ok=True)
@@ -694,6 +709,16 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         if vis is not None:
             extras[name] = {"proxy_rep": out}
         return out
+
+    def front_batch(names):
+        """The batched front end on one group: its (B,18,D,D) proxy representations; per-image views for the pictures are kept."""
+        out = batched([load_rgb_image(os.path.join(image_dir, n)) for n in names], with_image=vis is not None and visualise_uncropped)
+        if vis is not None:
+            for b, n in enumerate(names):
+                extras[n] = {"proxy_rep": out["proxy_rep"][b:b + 1], "cropped_rgb": out["cropped_rgb"][b:b + 1],
+                             "joints2D": out["joints2D"][b:b + 1], "image": out["image"][b] if "image" in out else None,
+                             "bbox_centre": out["bbox_centre"][b], "bbox_wh": out["bbox_wh"][b:b + 1]}
+        return out["proxy_rep"]
 
     def visualise(name, item):
         ex = extras.pop(name)
@@ -754,13 +779,13 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                 res_p = {key: (val.clone() if torch.is_tensor(val) else val) for key, val in res_p.items()}
             deliver(names_p, res_p)
         for gi, names in enumerate(groups):
-            items = [get_proxy(n).float() for n in names]
-            if len(items) == batch_size and tuple(items[0].shape[1:]) == graphed.input_shape:
+            items = front_batch(names) if batched is not None else [get_proxy(n).float() for n in names]
+            if len(items) == batch_size and tuple(items[0].shape[-3:]) == graphed.input_shape:
                 if writer is not None and graphed._slots[graphed._k % len(graphed._slots)] is None:
                     writer.drain()                       # a capture is coming: no other thread may call the runtime during it
                 nxt = (names,) + graphed(items, wait=False)
             else:                                        # a last, smaller group / another image size: the eager path
-                x = torch.cat([t.to(device) for t in items], dim=0)
+                x = items if batched is not None else torch.cat([t.to(device) for t in items], dim=0)
                 nxt = (names, infer(pose_shape_model, smpl_model, x, num_samples=num_samples, use_mean_shape=True), None)
             if pending is not None:
                 finish_pending(pending)
@@ -786,6 +811,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     _, pipe, stager = cached
 
     def stage(names):
+        if batched is not None:                          # one front-end call per group, on the caller's stream: ordered by submit()'s default event
+            return pipe.submit(front_batch(names))
         items = [get_proxy(n) for n in names]
         if all(t.is_cuda for t in items):                # built on the device (the reference front end): ordered by submit()'s default event
             return pipe.submit(torch.cat([t.float() for t in items], dim=0) if len(items) > 1 else items[0].float())
@@ -807,6 +834,23 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     torch.cuda.current_stream().wait_stream(pipe.caller_stream(batch_size))
     if writer is not None:
         writer.close()
+
+
+def use_batched_front_end(batched_front_end, proxy_rep_fn, device, hrnet_model, edge_detect_model):
+    """predict_poseMF_shapeGaussian_net's ``batched_front_end`` rule: can the device front end of a whole group run, and is it wanted."""
+    from .pose2D_hrnet import PoseHighResolutionNet
+    why = None
+    if proxy_rep_fn is not None:
+        why = "a proxy_rep_fn replaces the whole front end"
+    elif torch.device(device).type != "cuda":
+        why = "the device is not a GPU"
+    elif not isinstance(hrnet_model, PoseHighResolutionNet):
+        why = "hrnet_model is not a pose2D_hrnet.PoseHighResolutionNet"
+    elif not hasattr(edge_detect_model, "edge_map_into"):
+        why = "edge_detect_model has no edge_map_into"
+    if batched_front_end and why is not None:
+        raise _capi.HpsError("batched_front_end=True, but %s" % why)
+    return why is None and batched_front_end is not False
 
 
 def load_rgb_image(path):

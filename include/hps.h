@@ -1419,6 +1419,98 @@ typedef struct hps_hrnet_op {
 int hps_sizeof_hrnet_op(void);
 int hps_hrnet_run(const hps_hrnet_op* ops /* HOST */, int n_ops, hps_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Predict front end for a batch of photographs of different sizes  (csrc/predict_frontend.hip;
+ * predict/predict_hrnet.py:34-117, predict/predict_poseMF_shapeGaussian_net.py:61-99, utils/image_utils.py:310-370)
+ * ---------------------------------------------------------------------------------------- */
+
+/* Per-image descriptors go BY VALUE in the argument structs (HOST memory, as hps_conv2d_bn_act_c16's problem table): no device
+ * allocation, no pointer-table upload.  At most HPS_FRONTEND_MAX_IMAGES images per launch; a caller with more splits the batch.  All
+ * three entry points validate on the host before any launch and only enqueue.  fp32 throughout, no fused multiply-adds, no atomics.
+ *
+ * The box RECORD, HPS_FRONTEND_RECORD_FLOATS floats per image, written by hps_predict_boxes and read by the other two:
+ *   [0] [1]  bbox_centre (vertical, horizontal)          what predict_hrnet returns (:109-114) -- height and width AFTER both aspect
+ *   [2] [3]  bbox_height, bbox_width                     fixes, because image_utils.py:311-312 assigns through the views it was given
+ *   [4] [5]  box height, box width times scale_factor    (image_utils.py:321-322)
+ *   [6] [7]  scale (horizontal, vertical) = out_wh / box_wh                       the forward affine of image_utils.py:329-334
+ *   [8] [9]  shift (horizontal, vertical) = out_wh / 2 - scale * centre(h, v)
+ *   [10]     index of the chosen detection, -1 for the whole image
+ *   [11]     max(bbox_height, bbox_width) * scale_factor */
+#define HPS_FRONTEND_MAX_IMAGES 64
+#define HPS_FRONTEND_RECORD_FLOATS 12
+#define HPS_FRONTEND_SRC_HWC_U8 0    /* (H, W, 3) uint8, a decoded photograph; value = float(u8) / 255.0f, a true division */
+#define HPS_FRONTEND_SRC_CHW_F32 1   /* (3, H, W) float32 */
+
+/* hps_predict_boxes  (predict_hrnet.py:48-87 and the aspect / scale / affine steps of image_utils.py:310-334)
+ * Per image: H, W in [1, 32767] and optionally a detector's output -- boxes (n, 4) float (x1, y1, x2, y2), labels (n) int64, scores (n)
+ * float, n >= 0; boxes == NULL: no detector.  Detections with label == 1 and score > threshold are kept; none: the whole image (centre
+ * (H/2, W/2), height H, width W); otherwise the one with the smallest (cy - H/2)^2 + (cx - W/2)^2, the first index between equals.
+ * hrnet_aspect_fix != 0 applies predict_hrnet's own aspect step (:83-87, if / elif, aspect = the float32 of the double out_h / out_w)
+ * first; then always the two sequential masked assignments of image_utils.py:310-312 (aspect = the float32 quotient), the scale factor
+ * and the affine.  Every value is one IEEE single operation of the reference, in its order: the record equals the reference's bit for bit. */
+typedef struct hps_box_image {
+    const float* boxes;
+    const int64_t* labels;
+    const float* scores;
+    int n, H, W, reserved;
+} hps_box_image;
+typedef struct hps_predict_boxes_args {
+    int struct_bytes;
+    int B;
+    int out_w, out_h;                                          /* the crop's size, out_wh of the reference */
+    int hrnet_aspect_fix;
+    float threshold, scale_factor;
+    float* records;                                            /* (B, HPS_FRONTEND_RECORD_FLOATS) */
+    hps_box_image image[HPS_FRONTEND_MAX_IMAGES];
+} hps_predict_boxes_args;
+int hps_sizeof_predict_boxes_args(void);
+int hps_predict_boxes(const hps_predict_boxes_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_crop_bilinear  (image_utils.py:348-370: grid_sample, mode 'bilinear', padding_mode 'zeros', align_corners False)
+ * raw (B, 3, out_h, out_w) and optionally normalised = (raw - mean[c]) / std[c] (a true division, transforms.Normalize) from one source
+ * per image and its record.  Output pixel (i, j) samples the source at
+ *     x = (j + 1/2) (box_w / out_w) + ((centre_h - box_w / 2) - 1/2),   y = (i + 1/2) (box_h / out_h) + ((centre_v - box_h / 2) - 1/2)
+ * -- the reference's normalised theta written in pixel space -- with four taps at floor and floor + 1, weights (1 - fy)(1 - fx), ...,
+ * summed in the order ((t00 + t01) + t10) + t11; a tap outside the image contributes zero INDIVIDUALLY.  A source row need not be
+ * 4-byte aligned.  An image's values depend on its own descriptor and record only: same bits alone and in a batch. */
+typedef struct hps_crop_image {
+    const void* src;
+    int H, W, kind, reserved;                                  /* kind: HPS_FRONTEND_SRC_* */
+} hps_crop_image;
+typedef struct hps_crop_bilinear_args {
+    int struct_bytes;
+    int B;
+    int out_w, out_h;
+    float mean[3], std[3];                                     /* read only with normalised != NULL */
+    const float* records;                                      /* (B, HPS_FRONTEND_RECORD_FLOATS) */
+    float* raw;                                                /* (B, 3, out_h, out_w) */
+    float* normalised;                                         /* (B, 3, out_h, out_w) or NULL */
+    hps_crop_image image[HPS_FRONTEND_MAX_IMAGES];
+} hps_crop_bilinear_args;
+int hps_sizeof_crop_bilinear_args(void);
+int hps_crop_bilinear(const hps_crop_bilinear_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_hrnet_keypoints  (predict_hrnet.py:7-31, :104-107; predict_poseMF_shapeGaussian_net.py:97-99; image_utils.py:359-363)
+ * heatmaps (B, K, h, w) NCHW; per (image, joint) the maximum and its FIRST index idx (one wave per map; a NaN is never the maximum):
+ * confs = max; key point (idx % w, floor(idx / float(w))), zeroed unless max > 0, both coordinates times `factor`
+ * (IMAGE_SIZE[0] / HEATMAP_SIZE[0]) -> joints_hrnet (B, K, 2); joints_crop (B, K, 2) = joints_hrnet * scale + shift of records (B, .)
+ * (both NULL: not written); visib (B, K) = 1.0 where max > vis_threshold or bit k of always_visible is set, else 0.0.
+ * K in [1, 32], h w < 2^24. */
+typedef struct hps_hrnet_keypoints_args {
+    int struct_bytes;
+    int B, K, h, w;
+    float factor, vis_threshold;
+    uint32_t always_visible;
+    const float* heatmaps;
+    const float* records;                                      /* the proxy crop's records, or NULL */
+    float* joints_hrnet;
+    float* confs;
+    float* joints_crop;                                        /* or NULL */
+    float* visib;
+} hps_hrnet_keypoints_args;
+int hps_sizeof_hrnet_keypoints_args(void);
+int hps_hrnet_keypoints(const hps_hrnet_keypoints_args* args /* HOST */, hps_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
