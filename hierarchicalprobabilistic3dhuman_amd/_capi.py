@@ -70,6 +70,7 @@ _PROTOTYPES = {
     "hps_sample_joints2d_error": [_P, _P, _I, _P, _P, _P, _c.c_float, _P, _I, _I, _P],
     "hps_conv2d_bn_act_pad": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "hps_conv2d_bn_act_pad_down": [_P] * 9 + [_I] * 14 + [_P, _P],
+    "hps_bottleneck_expand_down": [_P] * 9 + [_I] * 12 + [_P],
     "hps_conv3x3_winograd": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P],
     "hps_conv3x3_winograd_workspace": [_I, _I, _I, _I, _I],
     "hps_stem_phase_frames_bytes": [_I, _I, _I],
@@ -165,7 +166,7 @@ class EncOp(_c.Structure):
     _fields_ = [("kind", _I), ("x", _P), ("w", _P), ("scale", _P), ("shift", _P), ("residual", _P), ("y", _P),
                 ("splitk_ws", _P)] + [(n, _I) for n in ("B", "H", "W", "ipad", "Cin", "Cout", "KH", "KW", "stride", "pad", "opad",
                                                        "relu", "row_mode", "variant", "ksplit")] + [
-                    ("w_down", _P), ("scale_down", _P), ("shift_down", _P), ("y_down", _P)]
+                    ("w_down", _P), ("scale_down", _P), ("shift_down", _P), ("y_down", _P), ("x_down", _P), ("ipad_down", _I), ("Cin_down", _I)]
 
 
 class MfLossArgs(_c.Structure):
@@ -306,7 +307,7 @@ ADAM_CHUNK = 4096
 REFRESH_PERMUTE, REFRESH_FOLD, REFRESH_WINO_U, REFRESH_STEM_U = 0, 1, 2, 3
 MF_REDUCTION_MEAN, MF_REDUCTION_SUM = 0, 1
 ENC_RELAYOUT, ENC_CONV, ENC_MAXPOOL, ENC_AVGPOOL, ENC_CONV_WINOGRAD, ENC_STEM_SPLIT, ENC_STEM_WINOGRAD, ENC_RELAYOUT_GENERIC = 0, 1, 2, 3, 4, 5, 6, 7
-ENC_STEM_WINOGRAD_POOLED, ENC_STEM_WINOGRAD_POOLED_NCHW, ENC_CONV_DOWN = 8, 9, 10
+ENC_STEM_WINOGRAD_POOLED, ENC_STEM_WINOGRAD_POOLED_NCHW, ENC_CONV_DOWN, ENC_EXPAND_DOWN = 8, 9, 10, 11
 # op kind -> (entry point, the hps_enc_op fields that are its arguments in front of the stream): the switch of csrc/composite.hip
 ENC_ENTRY = {kind: (entry, tuple(fields.split())) for kind, entry, fields in (
     (ENC_RELAYOUT, "hps_nchw_to_padded_nhwc", "x y B Cin H W opad"),
@@ -314,6 +315,8 @@ ENC_ENTRY = {kind: (entry, tuple(fields.split())) for kind, entry, fields in (
     (ENC_CONV, "hps_conv2d_bn_act_pad", "x w scale shift residual y B H W ipad Cin Cout KH KW stride pad opad relu row_mode variant ksplit splitk_ws"),
     (ENC_CONV_DOWN, "hps_conv2d_bn_act_pad_down", "x w scale shift y w_down scale_down shift_down y_down B H W ipad Cin Cout KH KW stride pad opad "
                                                   "relu variant ksplit splitk_ws"),
+    (ENC_EXPAND_DOWN, "hps_bottleneck_expand_down", "x w scale shift x_down w_down scale_down shift_down y B H W stride ipad ipad_down opad Cin Cin_down "
+                                                    "Cout variant ksplit"),
     (ENC_CONV_WINOGRAD, "hps_conv3x3_winograd", "x w scale shift residual y B H W ipad Cin Cout opad relu splitk_ws"),
     (ENC_STEM_SPLIT, "hps_stem_phase_split", "x y B Cin H W"),
     (ENC_STEM_WINOGRAD, "hps_stem_winograd", "x w scale shift y B H W opad relu"),

@@ -37,6 +37,11 @@ extern "C" int hps_encoder_run(const hps_enc_op* ops, int n_ops, hps_stream_t st
                                                 o.W, o.ipad, o.Cin, o.Cout, o.KH, o.KW, o.stride, o.pad, o.opad, o.relu, o.variant, o.ksplit,
                                                 o.splitk_ws, stream);
                 break;
+            case HPS_ENC_EXPAND_DOWN:
+                rc = hps_bottleneck_expand_down(o.x, o.w, o.scale, o.shift, o.x_down, o.w_down, o.scale_down, o.shift_down, o.y, o.B, o.H,
+                                                o.W, o.stride, o.ipad, o.ipad_down, o.opad, o.Cin, o.Cin_down, o.Cout, o.variant, o.ksplit,
+                                                stream);
+                break;
             case HPS_ENC_CONV_WINOGRAD:
                 rc = hps_conv3x3_winograd(o.x, o.w, o.scale, o.shift, o.residual, o.y, o.B, o.H, o.W, o.ipad, o.Cin, o.Cout, o.opad,
                                           o.relu, o.splitk_ws, stream);

@@ -17,6 +17,7 @@ __device__ __forceinline__ float elu1(float x) { return x > 0.0f ? x : expm1f(x)
 constexpr int TB = 8;      // batch rows per workgroup
 constexpr int LCOLS = 16;  // output columns per workgroup of linear_kernel
 constexpr int LKS = 16;    // K slices of linear_kernel (LCOLS * LKS = 256 threads)
+constexpr size_t TRUNK_LDS_LIMIT = 160 * 1024;   // hps_head_trunk: dynamic LDS of one workgroup on gfx950 (above 64 KiB: grant_lds)
 
 // acc[r] += sum_{k in [k_lo, k_hi)} xs[k][r] * w[k * ldw]   with 8 weight loads in flight
 template <int ROWS>
@@ -387,9 +388,12 @@ __global__ void svd3_packed_kernel(const float* __restrict__ f, float* __restric
 using namespace hps;
 
 static int launch_linear(const char* who, const float* x, int ldx, const float* x2, int ldx2, int K1, const float* wt, const float* bias,
-                         const float* addend, float* out, int ldo, int B, int K, int N, int act, TrunkSplit split, hps_stream_t stream) {
+                         const float* addend, float* out, int ldo, int B, int K, int N, int act, TrunkSplit split, hps_stream_t stream,
+                         size_t lds_limit = 64 * 1024) {
     size_t lds = ((size_t)((K * TB + 3) & ~3) + LKS * TB * LCOLS) * sizeof(float);
-    if (lds > 64 * 1024) { set_error("%s: K=%d too large for the LDS tile", who, K); return HPS_E_UNSUPPORTED; }
+    if (lds > lds_limit) { set_error("%s: K=%d too large for the LDS tile", who, K); return HPS_E_UNSUPPORTED; }
+    if (lds > 64 * 1024)             // granted once per device: the limit itself, not this call's size
+        if (int rc = grant_lds<&linear_kernel>((int)lds_limit, who)) return rc;
     hipLaunchKernelGGL(linear_kernel, dim3(ceil_div(N, LCOLS), ceil_div(B, TB)), dim3(256), lds, (hipStream_t)stream, x,
                        ldx, x2, ldx2, K1, wt, bias, addend, out, ldo, B, K, N, act, split);
     return check_launch(who);
@@ -415,18 +419,21 @@ extern "C" int hps_head_trunk(const float* feats, int ldf, const float* fc1_wt, 
         return bad_arg("hps_head_trunk: dims");
     if (B <= 0) return HPS_OK;
     const int nt = 2 * num_shape + num_glob + num_cam;
+    // the trunk of the ResNet-50 net stages 2048 and 2048 + nt input columns of 8 images: up to the CU's whole 160 KiB of LDS (the
+    // same kernel, the same K slices; hps_linear itself keeps to 64 KiB)
+    const size_t lim = TRUNK_LDS_LIMIT;
     // x = ELU(fc1(feats))                                                                              (:95-96)
     int rc = launch_linear("hps_head_trunk", feats, ldf, nullptr, 0, num_feats, fc1_wt, fc1_b, nullptr, x_ws, hidden, B, num_feats,
-                           hidden, HPS_ACT_ELU, TrunkSplit{}, stream);
+                           hidden, HPS_ACT_ELU, TrunkSplit{}, stream, lim);
     if (rc != HPS_OK) return rc;
     // [shape_params | glob + init_glob | cam + init_cam] = fc_shape | fc_glob | fc_cam (x)             (:98-107)
     TrunkSplit sp{shape_loc, shape_scale, glob, cam, num_shape, num_glob, num_cam};
     rc = launch_linear("hps_head_trunk", x_ws, hidden, nullptr, 0, hidden, sgc_wt, sgc_b, sgc_add, sgc_out, nt, B, hidden, nt,
-                       HPS_ACT_NONE, sp, stream);
+                       HPS_ACT_NONE, sp, stream, lim);
     if (rc != HPS_OK) return rc;
     // embed = ELU(fc_embed(cat[feats, shape_params, glob, cam]))                                       (:108-110)
     return launch_linear("hps_head_trunk", feats, ldf, sgc_out, nt, num_feats, embed_wt, embed_b, nullptr, embed, embed_dim, B,
-                         num_feats + nt, embed_dim, HPS_ACT_ELU, TrunkSplit{}, stream);
+                         num_feats + nt, embed_dim, HPS_ACT_ELU, TrunkSplit{}, stream, lim);
 }
 
 static int joint_level_launch(const float* embed, int embed_dim, int hidden, const int32_t* joint_ids, int n_level,

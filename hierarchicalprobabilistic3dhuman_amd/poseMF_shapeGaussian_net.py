@@ -49,7 +49,7 @@ from torch.distributions import Normal
 from . import _capi
 from .device_optim import RefreshList, plain
 from .device_state import DeviceStateModule
-from .resnet import resnet18
+from .resnet import resnet18, resnet50
 from .rigid_transform_utils import rotmat_to_rot6d
 from .sharding import effective_cpus
 
@@ -143,10 +143,15 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         self.register_buffer("init_glob", rotmat_to_rot6d(torch.eye(3)[None, :].float()))
         self.register_buffer("init_cam", torch.tensor([0.9, 0.0, 0.0]).float())
 
-        if config.MODEL.NUM_RESNET_LAYERS != 18:
-            raise NotImplementedError("only the ResNet-18 encoder of the released model is implemented")
-        self.image_encoder = resnet18(in_channels=config.MODEL.NUM_IN_CHANNELS, pretrained=False)
-        num_image_features, fc1_dim = 512, 512
+        # models/poseMF_shapeGaussian_net.py:53-62
+        if config.MODEL.NUM_RESNET_LAYERS == 18:
+            self.image_encoder = resnet18(in_channels=config.MODEL.NUM_IN_CHANNELS, pretrained=False)
+            num_image_features, fc1_dim = 512, 512
+        elif config.MODEL.NUM_RESNET_LAYERS == 50:          # forward only (resnet.ResNet)
+            self.image_encoder = resnet50(in_channels=config.MODEL.NUM_IN_CHANNELS, pretrained=False)
+            num_image_features, fc1_dim = 2048, 1024
+        else:
+            raise ValueError("MODEL.NUM_RESNET_LAYERS must be 18 or 50, got %r" % (config.MODEL.NUM_RESNET_LAYERS,))
         embed_dim = config.MODEL.EMBED_DIM
 
         self.activation = nn.ELU()
@@ -225,7 +230,7 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         nsh, ng, nc = self.num_shape_params * 2, self.num_glob_params, self.num_cam_params
         p = {}
         p["fc1_wt"], p["fc1_b"] = t(self.fc1.weight), c(self.fc1.bias)
-        # fc_shape | fc_glob | fc_cam fused into one (512 -> 29) layer; init_glob / init_cam as addend
+        # fc_shape | fc_glob | fc_cam fused into one (fc1_dim -> 29) layer; init_glob / init_cam as addend
         p["sgc_wt"] = t(torch.cat([self.fc_shape.weight, self.fc_glob.weight, self.fc_cam.weight], dim=0))
         p["sgc_b"] = c(torch.cat([self.fc_shape.bias, self.fc_glob.bias, self.fc_cam.bias]))
         p["sgc_add"] = c(torch.cat([torch.zeros(nsh, device=dev), self.init_glob.reshape(-1), self.init_cam.reshape(-1)]))

@@ -1,4 +1,4 @@
-"""ResNet-18 image encoder (final FC removed) with the module tree and state-dict keys of the reference's
+"""ResNet-18 / ResNet-50 image encoder (final FC removed) with the module tree and state-dict keys of the reference's
 models/resnet.py, executed as implicit-GEMM convolutions on the gfx950 fp32 matrix cores.
 
 The ``nn.Conv2d`` / ``nn.BatchNorm2d`` children only hold parameters (so that
@@ -231,6 +231,31 @@ class _ConvBN:
         _capi.issue_enc_op(self.op(xp, ipad, out, opad, None, relu, self._scratch(xp, ipad, ws, down), ident[0], down, out_down, ident[1]))
         return out, out_down
 
+    def expands_with(self, down, B, H, W):
+        """This (a Bottleneck's conv3: 1x1 / 1) can take the block's down-sample ``down`` (1x1 / s on the block's (H, W) input) into its
+        own launch (hps_bottleneck_expand_down): two direct 1x1 / pad 0 layers with the same output channels, neither split over K --
+        a rule on the layers only."""
+        if down is None or self.wn is None or down.wn is None or down.cout != self.cout:
+            return False
+        if not (self.kh == self.kw == down.kh == down.kw == 1 and self.pad == down.pad == 0 and self.stride == 1 and down.stride in (1, 2)):
+            return False
+        Ho, Wo = down.out_hw(H, W)
+        return self._route(B, Ho, Wo, 1)[1] == 1 and down._route(B, H, W, 1)[1] == 1
+
+    def expand_down_op(self, t, tpad, x, xpad, down, out, opad):
+        """relu(this layer on ``t`` + ``down`` on the block's input ``x``) as ONE hps_enc_op (see expands_with); the bits of down.op(x -> d,
+        no ReLU) followed by self.op(t -> out, residual = d, ReLU).  Nothing is launched."""
+        B, Hp, Wp, C = x.shape
+        H, W = Hp - 2 * xpad, Wp - 2 * xpad
+        Ho, Wo = down.out_hw(H, W)
+        assert self.expands_with(down, B, H, W) and C == down.cin_p
+        assert tuple(t.shape) == (B, Ho + 2 * tpad, Wo + 2 * tpad, self.cin_p) and tuple(out.shape) == (B, Ho + 2 * opad, Wo + 2 * opad, self.cout)
+        P = _capi.ptr
+        return _capi.EncOp(kind=_capi.ENC_EXPAND_DOWN, x=P(t), w=P(self.wn), scale=P(self.scale), shift=P(self.shift), y=P(out),
+                           x_down=P(x), w_down=P(down.wn), scale_down=P(down.scale), shift_down=P(down.shift), B=B, H=H, W=W,
+                           stride=down.stride, ipad=tpad, ipad_down=xpad, opad=opad, Cin=self.cin_p, Cin_down=C, Cout=self.cout, KH=1, KW=1,
+                           relu=1, variant=self._tile_variant(1), ksplit=1)
+
     def out_hw(self, H, W):
         return (H + 2 * self.pad - self.kh) // self.stride + 1, (W + 2 * self.pad - self.kw) // self.stride + 1
 
@@ -342,13 +367,50 @@ class BasicBlock(nn.Module):
         self.stride = stride
 
 
+class Bottleneck(nn.Module):
+    """models/resnet.py:81-122 (parameter container; executed as the steps of ResNet._plan).  The 3x3 convolution carries the block's
+    stride (:91-97)."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=1, stride=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, planes * self.expansion, kernel_size=1, stride=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+
+def _block_convs(blk):
+    """[(suffix, conv, bn)] of a block's main branch in execution order: c1, c2 (BasicBlock) or c1, c2, c3 (Bottleneck)."""
+    n = 3 if isinstance(blk, Bottleneck) else 2
+    return [("c%d" % i, getattr(blk, "conv%d" % i), getattr(blk, "bn%d" % i)) for i in range(1, n + 1)]
+
+
+class _Block(tuple):
+    """A residual block on the kernel side: the tuple (c1, c2, down) of a BasicBlock or (c1, c2, c3, down) of a Bottleneck -- ``convs``,
+    the main branch's _ConvBN in execution order, then ``down``, the down-sample on the block's input or None."""
+
+    def __new__(cls, convs, down):
+        return super().__new__(cls, tuple(convs) + (down,))
+
+    convs = property(lambda self: list(self[:-1]))
+    down = property(lambda self: self[-1])
+
+
 class ResNet(DeviceStateModule):
-    """models/resnet.py:125-217 for BasicBlock stacks."""
+    """models/resnet.py:125-217 for BasicBlock and Bottleneck stacks.  A Bottleneck encoder runs forward only (eval-mode BatchNorm,
+    no_grad): its backward, training-mode BatchNorm and in-place weight refresh are refused, never computed wrongly."""
 
     SWITCHES = ("_winograd", "_latency", "composite", "fused_pool", "fold_downsample", "stem_reads_nchw", "_bn_training")
 
-    def __init__(self, layers, in_channels):
+    def __init__(self, layers, in_channels, block=BasicBlock):
         super().__init__()
+        self.block = block
         self.inplanes = 64
         self.conv1 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
@@ -377,6 +439,8 @@ class ResNet(DeviceStateModule):
         self.fused_pool = True
         # the 1x1 / 2 down-sample of layer2-4's first block rides in the launch of the block's 3x3 / 2 convolution (hps_conv2d_bn_act_pad_down:
         # three launches of 16-26 us at 0.24-0.32 MFMA-busy disappear; identical bits).  False: two launches per block (the cross-check of the tests)
+        # Bottleneck entry blocks (layer1-4): the 1x1 / s down-sample is formed inside the launch of the block's expand convolution, whose
+        # epilogue is its only reader (hps_bottleneck_expand_down: the identity's frame is neither written nor read; identical bits)
         self.fold_downsample = True
         # ... and gather its phase windows from the NCHW input itself (hps_stem_winograd_pooled_nchw: no hps_stem_phase_split, no phase frames;
         # identical values; needs fused_pool): phase split 0.118 + frame-fed stem 0.61 -> 0.67 ms.  The default since round 6.  In round 5
@@ -389,15 +453,27 @@ class ResNet(DeviceStateModule):
         self._track_versions = False   # set by the first differentiable forward: parameters may now change in place (optimiser steps)
 
     def _make_layer(self, planes, blocks, stride=1):
-        downsample = None
-        if stride != 1 or self.inplanes != planes:
-            downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes, kernel_size=1, stride=stride, bias=False),
-                                       nn.BatchNorm2d(planes))
-        blks = [BasicBlock(self.inplanes, planes, stride, downsample)]
-        self.inplanes = planes
+        """models/resnet.py:178-200 for either block."""
+        block, downsample = self.block, None
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * block.expansion, kernel_size=1, stride=stride, bias=False),
+                                       nn.BatchNorm2d(planes * block.expansion))
+        blks = [block(self.inplanes, planes, stride, downsample)]
+        self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            blks.append(BasicBlock(planes, planes))
+            blks.append(block(self.inplanes, planes))
         return nn.Sequential(*blks)
+
+    @property
+    def _forward_only(self):
+        """A Bottleneck encoder: forward under no_grad with eval-mode BatchNorm only."""
+        return self.block is not BasicBlock
+
+    def train(self, mode=True):
+        if mode and self._forward_only:
+            raise NotImplementedError("training-mode BatchNorm is not implemented for the Bottleneck (ResNet-50) encoder: it runs in "
+                                      ".eval() mode only")
+        return super().train(mode)
 
     # ---- weight preparation (BN folding, k-major filters); redone after .to() / load_state_dict / a switch ----
     def set_winograd(self, on):
@@ -432,6 +508,8 @@ class ResNet(DeviceStateModule):
         result from the batch size holds for eval layers only.  Like set_winograd a property of the model: it survives .to(),
         load_state_dict and deepcopy.  FilledStemFrames inputs and ``_gate`` belong to the inference pipeline and are refused while
         a layer is training."""
+        if on and self._forward_only:
+            raise NotImplementedError("training-mode BatchNorm is not implemented for the Bottleneck (ResNet-50) encoder")
         self._bn_training = bool(on)
 
     def prepare(self):
@@ -441,8 +519,8 @@ class ResNet(DeviceStateModule):
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for blk in layer:
                 down = _ConvBN(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None
-                prep["blocks"].append((_ConvBN(blk.conv1, blk.bn1), _ConvBN(blk.conv2, blk.bn2), down))
-        for c in [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]:
+                prep["blocks"].append(_Block([_ConvBN(conv, bn) for _, conv, bn in _block_convs(blk)], down))
+        for c in self._convs(prep):
             c.latency = self._latency
             c.use_winograd = self._winograd and not self._latency      # latency mode runs every layer on the direct kernel
         if self._track_versions:
@@ -492,14 +570,18 @@ class ResNet(DeviceStateModule):
         h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
         fs["pool"] = z(B, h + 2, w + 2, stem.cout)
         fs["blocks"] = []
-        for c1, c2, down in prep["blocks"]:
+        for blk in prep["blocks"]:
+            convs, down = blk.convs, blk.down
             hin, win = h, w
-            h, w = c1.out_hw(h, w)
-            ent = {"c1": z(B, h + 2, w + 2, c1.cout), "c2": z(B, h + 2, w + 2, c2.cout),
-                   "down": z(B, h + 2, w + 2, down.cout) if down is not None else None}
-            folded = self.fold_downsample and c1.folds_down(down, hin, win, 1)
-            ws_bytes = max(c1.workspace_bytes(B, hin, win, 1, down if folded else None), c2.workspace_bytes(B, h, w),
-                           down.workspace_bytes(B, hin, win) if down is not None else 0)
+            folded = self.fold_downsample and convs[0].folds_down(down, hin, win, 1)
+            ent, ws_bytes = {}, down.workspace_bytes(B, hin, win) if down is not None else 0
+            for i, c in enumerate(convs):          # one frame per convolution of the main branch: "c1", "c2", ...
+                ws_bytes = max(ws_bytes, c.workspace_bytes(B, h, w, 1, down if folded and i == 0 else None))
+                h, w = c.out_hw(h, w)
+                ent["c%d" % (i + 1)] = z(B, h + 2, w + 2, c.cout)
+            # (a Bottleneck entry block whose down-sample rides in conv3's launch never writes the identity's frame)
+            ent["down"] = z(B, h + 2, w + 2, down.cout) if down is not None and not self._expands(blk, B, hin, win) else None
+            ent["out"] = ent["c%d" % len(convs)]         # the block's output frame
             ent["ws"] = torch.empty(ws_bytes // 4, device=device, dtype=torch.float32) if ws_bytes else None
             fs["blocks"].append(ent)
         fs["hw"] = (h, w)
@@ -514,7 +596,8 @@ class ResNet(DeviceStateModule):
         the last one's output pointer are the caller's, set per forward) or, with ``flags`` (_train_flags()) naming a layer's BatchNorm as
         training, the _BNStep behind that layer's convolution, which then writes the raw frame: identity scale / shift, no ReLU, no
         residual.  Order within a block: the down-sample (its own launch or riding in c1's), c1, the BatchNorm of .down, of .c1, then
-        c2 and its BatchNorm (with the residual and the block's ReLU)."""
+        every further convolution of the main branch with its BatchNorm behind it -- c2 (BasicBlock), c2 and c3 (Bottleneck.forward
+        :102-122: c1 1x1, c2 3x3 with the block's stride, c3 1x1) -- the last one with the residual and the block's ReLU."""
         B, C, H, W = shape
         E, P = _capi.EncOp, _capi.ptr
         stem, steps = prep["stem"], []
@@ -548,28 +631,51 @@ class ResNet(DeviceStateModule):
             bn("stem", stem, y, 0, None, True)
             steps.append(E(kind=_capi.ENC_MAXPOOL, x=P(y), y=P(fs["pool"]), B=B, H=y.shape[1], W=y.shape[2], Cin=stem.cout, opad=1))
         y = fs["pool"]
-        for name, (c1, c2, down), ent in zip(self._block_names(), prep["blocks"], fs["blocks"]):
-            n1, n2, nd = name + ".c1", name + ".c2", name + ".down"
-            t1, t2, td = train(n1), train(n2), down is not None and train(nd)
+        for name, blk, ent in zip(self._block_names(), prep["blocks"], fs["blocks"]):
+            convs, down = blk.convs, blk.down
+            c1, n1, nd = convs[0], name + ".c1", name + ".down"
+            t1, td = train(n1), down is not None and train(nd)
             identity = y if down is None else ent["down"]
             folded = self.fold_downsample and c1.folds_down(down, y.shape[1] - 2, y.shape[2] - 2, 1)
-            if down is not None and not folded:
+            # Bottleneck entry: the down-sample inside the expand convolution's launch (hps_bottleneck_expand_down), where no BatchNorm
+            # of the two is training
+            expand = self._expands(blk, B, y.shape[1] - 2, y.shape[2] - 2) and not (td or train("%s.c%d" % (name, len(convs))))
+            x_in = y
+            assert expand or down is None or ent["down"] is not None
+            if down is not None and not folded and not expand:
                 steps.append(down.op(y, 1, target(nd, ent["down"]), 1, relu=False, ws=ent["ws"], ident=td))
             steps.append(c1.op(y, 1, target(n1, ent["c1"]), 1, relu=not t1, ws=ent["ws"], ident=t1,
                                down=down if folded else None, out_down=target(nd, ent["down"]) if folded else None, ident_down=td))
             if down is not None:
                 bn(nd, down, ent["down"], 1, None, False)
             bn(n1, c1, ent["c1"], 1, None, True)
-            steps.append(c2.op(ent["c1"], 1, target(n2, ent["c2"]), 1, residual=None if t2 else identity, relu=not t2, ws=ent["ws"], ident=t2))
-            bn(n2, c2, ent["c2"], 1, identity, True)
-            y = ent["c2"]
+            y = ent["c1"]
+            for i, c in enumerate(convs[1:], 2):
+                n, out = "%s.c%d" % (name, i), ent["c%d" % i]
+                t, res = train(n), identity if i == len(convs) else None              # the last one closes the block
+                if expand and i == len(convs):
+                    steps.append(c.expand_down_op(y, 1, x_in, 1, down, out, 1))
+                    y = out
+                    break
+                steps.append(c.op(y, 1, target(n, out), 1, residual=None if t else res, relu=not t, ws=ent["ws"], ident=t))
+                bn(n, c, out, 1, res, True)
+                y = out
         h, w = fs["hw"]
         steps.append(E(kind=_capi.ENC_AVGPOOL, x=P(y), y=None, B=B, H=h, W=w, Cin=y.shape[3], ipad=1))
         return steps
 
+    def _expands(self, blk, B, H, W):
+        """``fold_downsample`` for a Bottleneck entry block ``blk`` on (H, W) input maps: its down-sample rides in conv3's launch."""
+        return bool(self.fold_downsample and len(blk.convs) == 3 and blk.convs[-1].expands_with(blk.down, B, H, W))
+
+    @staticmethod
+    def _convs(prep):
+        """Every _ConvBN in the order of _enc_layers(): the stem, then per block the main branch and the down-sample."""
+        return [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]
+
     @staticmethod
     def _variant_state(prep):
-        convs = [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]
+        convs = ResNet._convs(prep)
         return tuple((c.variant, c.ksplit, c.use_winograd, c.latency) for c in convs)
 
     def stem_frames(self, B, C, H, W, device):
@@ -605,7 +711,7 @@ class ResNet(DeviceStateModule):
             fs["generation"] = fs.get("generation", 0) + 1      # the phase split below overwrites the frames
         # the frame set's launch list (_plan): one call across the C ABI for the whole encoder (csrc/composite.hip), two when it is
         # gated; ``composite`` False: the same list launch by launch through the public entry points (the cross-check of the tests)
-        feats = torch.empty(B, fs["blocks"][-1]["c2"].shape[3], device=x.device, dtype=torch.float32)
+        feats = torch.empty(B, fs["blocks"][-1]["out"].shape[3], device=x.device, dtype=torch.float32)
         ops = fs["ops"]
         n = len(ops)
         ops[n - 1].y = feats.data_ptr()
@@ -625,7 +731,7 @@ class ResNet(DeviceStateModule):
         return feats
 
     def forward(self, x, _gate=None):
-        """models/resnet.py:202-217: (B,C,H,W) NCHW fp32 -> (B,512)."""
+        """models/resnet.py:202-217: (B,C,H,W) NCHW fp32 -> (B, 512 * block.expansion)."""
         flags = self._train_flags()
         filled = isinstance(x, FilledStemFrames)
         if flags is not None:
@@ -635,6 +741,9 @@ class ResNet(DeviceStateModule):
             _capi.require_device(x, "encoder input")
         differentiable = torch.is_grad_enabled() and not filled and (
             (isinstance(x, torch.Tensor) and x.requires_grad) or any(w.requires_grad for w in self._enc_params()))
+        if differentiable and self._forward_only:
+            raise NotImplementedError("the backward of the Bottleneck (ResNet-50) encoder is not implemented: run it under torch.no_grad() "
+                                      "(or with no input / encoder parameter requiring grad)")
         if differentiable:
             self._track_versions = True
         prep = self._current_prep()
@@ -669,7 +778,7 @@ class ResNet(DeviceStateModule):
         out = {"stem": hw(H, W, 7, 2, 3)}
         h, w = hw(*out["stem"], 3, 2, 1)
         for name, conv, _ in self._enc_layers()[1:]:
-            if name.endswith(".c1"):
+            if not name.endswith(".down"):          # the down-sample's map is its block's output map
                 h, w = hw(h, w, conv.kernel_size[0], conv.stride[0], conv.padding[0])
             out[name] = (h, w)
         return out
@@ -701,7 +810,7 @@ class ResNet(DeviceStateModule):
         prep = self._prepared or self.prepare()
         stale = prep.get("stale_bn")
         if stale:
-            convs = [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]
+            convs = self._convs(prep)
             with torch.no_grad():
                 for (name, _, bn), cb in zip(self._enc_layers(), convs):
                     if name in stale:
@@ -722,7 +831,7 @@ class ResNet(DeviceStateModule):
         (the scaled data-gradient filters read them)."""
         ref = RefreshList(token)
         bwd = prep.get("bwd", {})
-        convs = [prep["stem"]] + [c for blk in prep["blocks"] for c in blk if c is not None]
+        convs = self._convs(prep)
         layers = list(zip(self._enc_layers(), convs))
         for (_, _, bn), cb in layers:
             ref.fold(bn, cb.scale, cb.shift)
@@ -755,6 +864,9 @@ class ResNet(DeviceStateModule):
         is dropped instead, as after any other edit."""
         prep = self._prepared
         if prep is None:
+            return
+        if self._forward_only:          # no in-place refresh for a Bottleneck encoder yet: drop the state, which is always correct
+            self.invalidate()
             return
         token = self._refresh_token(prep)
         ref = self._device_state.get("refresh")
@@ -823,7 +935,7 @@ class ResNet(DeviceStateModule):
             stats[name] = (mean, var, invstd, n)
 
         plan = fs["plan"]
-        feats = torch.empty(B, fs["blocks"][-1]["c2"].shape[3], device=dev, dtype=torch.float32)
+        feats = torch.empty(B, fs["blocks"][-1]["out"].shape[3], device=dev, dtype=torch.float32)
         plan[0].x, plan[-1].y = x.data_ptr(), feats.data_ptr()
         for step in plan:
             if isinstance(step, _BNStep):
@@ -836,12 +948,11 @@ class ResNet(DeviceStateModule):
 
     # ---- backward (csrc/conv_backward.hip) ----
     def _enc_layers(self):
-        """(name, conv, bn) of every convolution in the order of prepare(): the stem, then conv1 / conv2 / downsample per block."""
+        """(name, conv, bn) of every convolution in the order of prepare(): the stem, then conv1 / conv2 [/ conv3] / downsample per block."""
         out = [("stem", self.conv1, self.bn1)]
         for li, layer in enumerate((self.layer1, self.layer2, self.layer3, self.layer4), 1):
             for bi, blk in enumerate(layer):
-                out.append(("layer%d.%d.c1" % (li, bi), blk.conv1, blk.bn1))
-                out.append(("layer%d.%d.c2" % (li, bi), blk.conv2, blk.bn2))
+                out += [("layer%d.%d.%s" % (li, bi, k), conv, bn) for k, conv, bn in _block_convs(blk)]
                 if blk.downsample is not None:
                     out.append(("layer%d.%d.down" % (li, bi), blk.downsample[0], blk.downsample[1]))
         return out
@@ -1144,3 +1255,10 @@ def resnet18(in_channels, pretrained=False, progress=True, **kwargs):
     if pretrained:
         raise NotImplementedError("no network access: pretrained weights are not available")
     return ResNet([2, 2, 2, 2], in_channels)
+
+
+def resnet50(in_channels, pretrained=False, progress=True, **kwargs):
+    """models/resnet.py:251-259 (Bottleneck, [3, 4, 6, 3], 2048 features); forward only (see ResNet)."""
+    if pretrained:
+        raise NotImplementedError("no network access: pretrained weights are not available")
+    return ResNet([3, 4, 6, 3], in_channels, block=Bottleneck)

@@ -182,6 +182,9 @@ def train_poseMF_shapeGaussian_net(pose_shape_model,
     stage change as the reference appends it.  As there, the caller loads the model's and the optimiser's state dicts from
     ``checkpoint`` before the call.  The module docstring has the two differences (BatchNorm opt-in, datasets)."""
     cfg = pose_shape_cfg
+    if getattr(pose_shape_model.image_encoder, "_forward_only", False):          # before a file, a loader or a buffer is touched
+        raise NotImplementedError("training a net with the Bottleneck (ResNet-50) encoder is not implemented: its encoder runs forward "
+                                  "only (MODEL.NUM_RESNET_LAYERS = 18 trains)")
     loader = lambda dataset: DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, shuffle=True, drop_last=True,
                                         num_workers=cfg.TRAIN.NUM_WORKERS, pin_memory=cfg.TRAIN.PIN_MEMORY)
     dataloaders = {'train': loader(train_dataset), 'val': loader(val_dataset)}

@@ -47,6 +47,8 @@ typedef void* hps_stream_t; /* hipStream_t */
  *                                                    route for skinning weights with more than 12 influences)
  *   one hps_conv2d_bn_act_pad call for a block's
  *   1x1/2 down-sample                             -> hps_conv2d_bn_act_pad_down (rides in the 3x3/2 convolution's launch)
+ *   two hps_conv2d_bn_act_pad calls for a
+ *   Bottleneck entry's down-sample and conv3      -> hps_bottleneck_expand_down (the identity's tile stays in registers)
  *   hps_nchw_to_padded_nhwc (+ row-mode stem)     -> the Winograd stem for the released model's shapes; the relayout + direct stem remain
  *                                                    the route of every other (C, H, W) and of the latency mode */
 
@@ -416,7 +418,9 @@ int hps_linear(const float* x, int ldx, const float* wt, const float* bias, cons
  *            shape_loc = mean, shape_scale = exp(log std) (the Normal of :100-101), glob, cam, each contiguous
  *   embed  = ELU(fc_embed(cat[feats, sgc]))                         the concatenation (:108) is never materialised
  * Weights pre-transposed (K, N) like hps_linear; sgc_wt / sgc_b / sgc_add = the three layers stacked (sgc_add: zeros, init_glob,
- * init_cam).  feats rows have stride ldf. */
+ * init_cam).  feats rows have stride ldf.  Widths: a workgroup stages the K input columns of 8 images in LDS, up to 160 KiB here
+ * (K <= 4864: num_feats + 2 num_shape + num_glob + num_cam = 2077 for the ResNet-50 net; hps_linear itself keeps to 64 KiB,
+ * K <= 1792); wider: HPS_E_UNSUPPORTED before any launch. */
 int hps_head_trunk(const float* feats, int ldf, const float* fc1_wt, const float* fc1_b, const float* sgc_wt,
                    const float* sgc_b, const float* sgc_add, const float* embed_wt, const float* embed_b, float* x_ws,
                    float* sgc_out, float* embed, float* shape_loc, float* shape_scale, float* glob, float* cam, int B,
@@ -481,7 +485,7 @@ int hps_head_svd_finish(const float* usv_level, const int32_t* joint_ids, int n_
                         hps_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * ResNet-18 encoder  (models/resnet.py:202-217) -- NHWC activations
+ * ResNet-18 / ResNet-50 encoder  (models/resnet.py:202-217) -- NHWC activations
  * ---------------------------------------------------------------------------------------- */
 
 /* Halo-padded generation of the convolution (csrc/conv_pad.hip), same arithmetic and summation order as
@@ -510,6 +514,24 @@ int hps_conv2d_bn_act_pad_down(const float* x, const float* wn, const float* sca
                                const float* wn_down, const float* scale_down, const float* shift_down, float* y_down,
                                int B, int H, int W, int ipad, int Cin, int Cout, int KH, int KW, int stride, int pad,
                                int opad, int relu, int variant, int ksplit, float* splitk_ws, hps_stream_t stream);
+
+/* Bottleneck entry block (models/resnet.py:102-122: `out = bn3(conv3(out)); identity = self.downsample(x); out += identity;
+ * out = relu(out)`, the down-sample built at :184-188) in ONE launch (csrc/conv_expand_down.hip):
+ *     y = relu( (acc3 * scale3 + shift3) + identity ),     identity = acc_d * scale_down + shift_down + 0
+ * acc3: the 1x1 / 1 convolution of the frame t (B, Ho + 2 tpad, Wo + 2 tpad, Cmid) with w3 (Cout, Cmid) n-major; acc_d: the
+ * 1x1 / stride convolution of the frame x (B, H + 2 xpad, W + 2 xpad, Cin) with w_down (Cout, Cin) n-major, Ho = (H - 1) / stride + 1
+ * (Wo alike); y: the interior of the frame (B, Ho + 2 opad, Wo + 2 opad, Cout), the halo is the owner's.  The identity's tile is
+ * formed first and held in registers through the second K loop: its frame is never written or read.  Every output has the bits of
+ *     hps_conv2d_bn_act_pad(x, w_down, scale_down, shift_down, NULL, d, ..., stride, pad = 0, relu = 0)
+ *     hps_conv2d_bn_act_pad(t, w3, scale3, shift3, residual = d, y, ..., relu = 1)
+ * (both loops walk their chunks in that kernel's order; the epilogue expressions are the same).  Cmid % 32 == 0, Cin % 32 == 0,
+ * Cout % 64 == 0, stride 1 or 2; variant 1, 2, 3, 5 or 0 (automatic, hps_conv2d_bn_act_pad's rule).  No split K: ksplit > 1 is
+ * refused (a layer whose mode wants K slices takes the two launches).  Arguments are validated on the host before any launch: null
+ * pointers, geometry, the 32-bit lane offsets (tensors < 4 GiB). */
+int hps_bottleneck_expand_down(const float* t, const float* w3, const float* scale3, const float* shift3, const float* x,
+                               const float* w_down, const float* scale_down, const float* shift_down, float* y, int B, int H, int W,
+                               int stride, int tpad, int xpad, int opad, int Cmid, int Cin, int Cout, int variant, int ksplit,
+                               hps_stream_t stream);
 
 /* 3x3 / stride 1 / pad 1 convolution + BatchNorm (+ residual) (+ ReLU) by Winograd F(2x2, 3x3) on the fp32 MFMA pipe
  * (csrc/conv_wino.hip): 16 multiplications per 2x2 output tile and (cin, cout) pair instead of 36 -- the stride-1 3x3
@@ -582,7 +604,10 @@ enum { HPS_ENC_RELAYOUT = 0, HPS_ENC_CONV = 1, HPS_ENC_MAXPOOL = 2, HPS_ENC_AVGP
        HPS_ENC_STEM_SPLIT = 5, HPS_ENC_STEM_WINOGRAD = 6,
        HPS_ENC_RELAYOUT_GENERIC = 7 /* hps_nchw_to_padded_nhwc_generic (x, y, B, Cin = C, Cout = CP, H, W, KW = WF, opad = P) */,
        HPS_ENC_STEM_WINOGRAD_POOLED = 8, HPS_ENC_STEM_WINOGRAD_POOLED_NCHW = 9,
-       HPS_ENC_CONV_DOWN = 10 /* hps_conv2d_bn_act_pad_down: the HPS_ENC_CONV fields + w_down / scale_down / shift_down / y_down */ };
+       HPS_ENC_CONV_DOWN = 10 /* hps_conv2d_bn_act_pad_down: the HPS_ENC_CONV fields + w_down / scale_down / shift_down / y_down */,
+       HPS_ENC_EXPAND_DOWN = 11 /* hps_bottleneck_expand_down: x = t, w = w3, scale, shift, x_down = x, w_down, scale_down, shift_down, y,
+                                   B, H, W (of x_down), stride, ipad = tpad, ipad_down = xpad, opad, Cin = Cmid, Cin_down = Cin, Cout,
+                                   variant, ksplit */ };
 typedef struct hps_enc_op {
     int kind;
     const float* x;
@@ -597,6 +622,8 @@ typedef struct hps_enc_op {
     const float* scale_down;
     const float* shift_down;
     float* y_down;
+    const float* x_down;       /* HPS_ENC_EXPAND_DOWN only: the block's input frame, its halo and its channels */
+    int ipad_down, Cin_down;
 } hps_enc_op;
 
 /* sizeof(hps_enc_op) as compiled into the library: lets a hand-written mirror of the struct check itself. */
