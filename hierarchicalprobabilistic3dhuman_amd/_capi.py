@@ -148,6 +148,15 @@ _PROTOTYPES = {
     "hps_crop_bilinear": [_P, _P],
     "hps_sizeof_hrnet_keypoints_args": [],
     "hps_hrnet_keypoints": [_P, _P],
+    "hps_sizeof_texture_gather_args": [],
+    "hps_texture_gather": [_P, _P],
+    "hps_sizeof_resize_bilinear_u8_args": [],
+    "hps_resize_bilinear_u8": [_P, _P],
+    "hps_sizeof_eval_crop_u8_args": [],
+    "hps_eval_crop_u8": [_P, _P],
+    "hps_keypoints_scale_round": [_P, _P, _P, _P, _I, _I, _P],
+    "hps_sizeof_eval_heatmaps_args": [],
+    "hps_eval_heatmaps": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -295,6 +304,40 @@ class HrnetKeypointsArgs(_c.Structure):
     _fields_ = [(n, _I) for n in ("struct_bytes", "B", "K", "h", "w")] + [("factor", _c.c_float), ("vis_threshold", _c.c_float),
                                                                           ("always_visible", _c.c_uint32)] + [
         (n, _P) for n in ("heatmaps", "records", "joints_hrnet", "confs", "joints_crop", "visib")]
+
+
+class TextureGatherArgs(_c.Structure):
+    """include/hps.h: hps_texture_gather_args (struct_bytes = ctypes.sizeof(TextureGatherArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "Ht", "Wt", "n_grey", "n_nongrey")] + [(n, _P) for n in ("grey", "nongrey", "out")] + [
+        ("is_grey", _I * FRONTEND_MAX_IMAGES), ("idx", _I * FRONTEND_MAX_IMAGES)]
+
+
+class U8Image(_c.Structure):
+    """include/hps.h: hps_u8_image."""
+    _fields_ = [("src", _P), ("H", _I), ("W", _I)]
+
+
+class ResizeBilinearU8Args(_c.Structure):
+    """include/hps.h: hps_resize_bilinear_u8_args (struct_bytes = ctypes.sizeof(ResizeBilinearU8Args))."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "out_w", "out_h")] + [("out", _P), ("image", U8Image * FRONTEND_MAX_IMAGES)]
+
+
+class EvalCropImage(_c.Structure):
+    """include/hps.h: hps_eval_crop_image."""
+    _fields_ = [("rgb", _P), ("seg", _P), ("H", _I), ("W", _I), ("centre_v", _c.c_double), ("centre_h", _c.c_double), ("side", _c.c_double)]
+
+
+class EvalCropU8Args(_c.Structure):
+    """include/hps.h: hps_eval_crop_u8_args (struct_bytes = ctypes.sizeof(EvalCropU8Args))."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "out_wh", "K")] + [("scale_factor", _c.c_double)] + [
+        (n, _P) for n in ("keypoints", "rgb", "seg", "joints", "positions")] + [("image", EvalCropImage * FRONTEND_MAX_IMAGES)]
+
+
+class EvalHeatmapsArgs(_c.Structure):
+    """include/hps.h: hps_eval_heatmaps_args (struct_bytes = ctypes.sizeof(EvalHeatmapsArgs))."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "K", "wh", "use_threshold")] + [("std", _c.c_float), ("always_visible", _c.c_uint32),
+                                                                                       ("threshold", _c.c_double)] + [
+        (n, _P) for n in ("positions", "keypoints", "out")]
 
 
 C16_MAX_PROBLEMS, HRNET_MAX_TERMS = 4, 4

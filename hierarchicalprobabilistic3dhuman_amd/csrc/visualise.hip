@@ -20,6 +20,7 @@
 // special case -- a lane's run simply crosses pixels, rows and panels.  Only the last lane of an image whose byte count is no multiple
 // of 16 stores dwords and at most three single bytes.  Compiled with -ffp-contract=off: the float32 twin of tests/vis_scenario.py
 // rounds every product.
+#include "cv_warp.h"
 #include "hps_common.h"
 
 namespace hps {
@@ -210,10 +211,6 @@ __global__ __launch_bounds__(256) void vis_compose_kernel(const ComposeParams P,
 // ---------------------------------------------------------------------------------------------------------------------------------
 // uncrop
 // ---------------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cv_round(double v) {      // saturate_cast<int>(double)
-    return (int)rint(fmin(fmax(v, -2147483648.0), 2147483647.0));
-}
-
 __device__ __forceinline__ float tap_or_zero(const float* __restrict__ s, int wh, int y, int x) {
     return (y >= 0 && y < wh && x >= 0 && x < wh) ? s[y * wh + x] : 0.0f;
 }
@@ -228,27 +225,21 @@ __global__ __launch_bounds__(256) void vis_uncrop_kernel(const float* __restrict
     const float side = bbox_wh[0], owh = (float)wh, ocentre = owh * 0.5f;
     const float f00 = side / owh, f11 = side / owh;
     const float f02 = bbox_centre[1] - (side / owh) * ocentre, f12 = bbox_centre[0] - (side / owh) * ocentre;
-    // ... and cv2.warpAffine's inversion of it in float64 (no WARP_INVERSE_MAP)
-    double M0 = f00, M1 = 0.0, M2 = f02, M3 = 0.0, M4 = f11, M5 = f12;
-    double Dt = M0 * M4 - M1 * M3;
-    Dt = Dt != 0.0 ? 1.0 / Dt : 0.0;
-    const double A11 = M4 * Dt, A22 = M0 * Dt;
-    M0 = A11; M1 *= -Dt; M3 *= -Dt; M4 = A22;
-    const double b1 = -M0 * M2 - M1 * M5, b2 = -M3 * M2 - M4 * M5;
+    // ... and cv2.warpAffine's inversion of it in float64 (no WARP_INVERSE_MAP); the fixed-point positions are cv_warp.h's
+    const WarpInverse A = warp_invert(f00, 0.0, f02, 0.0, f11, f12);
     const size_t src_plane = (size_t)wh * wh, img_plane = (size_t)H * W;
     store_run16(out, nbytes, W, lane, [&](int y, int x) -> unsigned {
-        // AB_BITS = 10: per column rint(M x 1024), per row rint((M y + t) 1024) + the rounding offset
-        const unsigned ax = (unsigned)cv_round(M0 * x * 1024.0), ay = (unsigned)cv_round(M3 * x * 1024.0);
-        const unsigned rx = (unsigned)cv_round((M1 * y + b1) * 1024.0), ry = (unsigned)cv_round((M4 * y + b2) * 1024.0);
-        // INTER_NEAREST on the part plane: + 512, >> 10; outside reads 0
-        const int nx = (int)(rx + 512u + ax) >> 10, ny = (int)(ry + 512u + ay) >> 10;
+        const WarpFixed p = warp_fixed(A, x, y);
+        // INTER_NEAREST on the part plane; outside reads 0
+        int nx, ny;
+        warp_nearest(p, nx, ny);
         const size_t at = (size_t)y * W + x;
         if (tap_or_zero(iplane, wh, ny, nx) == 0.0f)
             return pack3(to_byte(image[at]), to_byte(image[at + img_plane]), to_byte(image[at + 2 * img_plane]));
-        // INTER_LINEAR on the colour: + 16, >> 5; the index is >> 5 (a short), the fraction & 31 thirty-seconds
-        const int lx = (int)(rx + 16u + ax) >> 5, ly = (int)(ry + 16u + ay) >> 5;
-        const int sx = max(-32768, min(32767, lx >> 5)), sy = max(-32768, min(32767, ly >> 5));
-        const float fx = (float)(lx & 31) * 0.03125f, fy = (float)(ly & 31) * 0.03125f;
+        // INTER_LINEAR on the colour: the fraction in thirty-seconds
+        int sx, sy, ix, iy;
+        warp_linear(p, sx, sy, ix, iy);
+        const float fx = (float)ix * 0.03125f, fy = (float)iy * 0.03125f;
         const float w00 = (1.0f - fy) * (1.0f - fx), w01 = (1.0f - fy) * fx, w10 = fy * (1.0f - fx), w11 = fy * fx;
         unsigned b[3];
 #pragma unroll

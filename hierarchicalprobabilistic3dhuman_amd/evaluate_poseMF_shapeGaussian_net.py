@@ -31,7 +31,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from . import _capi, cam_utils, sharding
+from . import _capi, cam_utils, data_layer, sharding
 from .eval_metrics_tracker import EvalMetricsTracker
 from .joints2d_utils import undo_keypoint_normalisation
 from .label_conversions import ALL_JOINTS_TO_COCO_MAP, ALL_JOINTS_TO_H36M_MAP, H36M_TO_J14
@@ -111,9 +111,12 @@ def evaluate_pose_MF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mo
     run_seed = _philox_seed(seed) if not sample_on_cpu else None
     if run_seed is not None and reduce_across_ranks:
         run_seed = sharding.broadcast_int(run_seed)
-    staged = _StagedCollate(pinned=device.type == "cuda") if num_workers == 0 else None
+    # a dataset with prepare_batch (ssp3d_eval_dataset.py, pw3d_eval_dataset.py) hands over raw items: its batch is formed on the device
+    prepare = data_layer.preparer(eval_dataset)
+    staged = _StagedCollate(pinned=device.type == "cuda") if num_workers == 0 and prepare is None else None
     loader = DataLoader(eval_dataset, batch_size=batch_size, shuffle=False, drop_last=False, num_workers=num_workers,
-                        pin_memory=pin_memory and staged is None, collate_fn=staged)
+                        pin_memory=pin_memory and staged is None and prepare is None,
+                        collate_fn=data_layer.passthrough_collate if prepare is not None else staged)
     tracker = EvalMetricsTracker(metrics, save_path=save_path, save_per_frame_metrics=save_per_frame_metrics,
                                  silhouette_renderer=silhouette_renderer)
     if silhouette_renderer is not None and any("silhouette" in m for m in metrics):
@@ -151,7 +154,7 @@ def flipped_target_rotmats(target_pose, flip=None):
 
 def _evaluate_loop(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male, smpl_model_female, edge_detect_model, device,
                    loader, staged, tracker, metrics, want_samples, N, flip, fnames, poses, shapes, cams, sample_on_cpu, run_seed, frame0,
-                   reduce_across_ranks, save_per_frame_metrics, save_path, silhouette_renderer, **_unused):
+                   reduce_across_ranks, save_per_frame_metrics, save_path, silhouette_renderer, prepare=None, **_unused):
     frame = frame0
     want_joints2d, want_silhouettes = any("joints2D" in m for m in metrics), any("silhouette" in m for m in metrics)
     wh = pose_shape_cfg.DATA.PROXY_REP_SIZE
@@ -164,6 +167,8 @@ def _evaluate_loop(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male
 
     for batch in loader:
         with torch.no_grad():
+            if prepare is not None:
+                batch = prepare(batch)
             image = batch["image"].to(device, non_blocking=True)
             heatmaps = batch["heatmaps"].to(device, non_blocking=True)
             edges = edge_detect_model(image)                                                          # :69-71

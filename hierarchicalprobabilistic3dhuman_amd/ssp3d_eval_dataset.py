@@ -1,0 +1,79 @@
+"""data/ssp3d_eval_dataset.py with the pixel work moved to the device (data_layer.py, csrc/data_layer.hip).
+
+Same constructor and files as the reference: ``ssp3d_dir_path`` holds images/, silhouettes/ and labels.npz ('fnames', 'shapes',
+'poses', 'joints2D' (n,17,3), 'bbox_centres' (n,2) as (vertical, horizontal), 'bbox_whs' (n,), 'genders').  ``__getitem__`` decodes
+the image and its silhouette and returns them with the label rows; ``prepare_batch`` crops both to the bounding box with
+cv2.warpAffine's arithmetic, moves the key points through the same matrix in float64 and draws the heat maps, all on the device.
+The labels are taken as float64 (what the reference's arithmetic gives with float64 label arrays).
+"""
+import os
+
+import numpy as np
+import torch
+from torch.utils.data import Dataset
+
+from . import data_layer
+
+
+class SSP3DEvalDataset(Dataset):
+    def __init__(self, ssp3d_dir_path, config, visible_joints_threshold=None):
+        super(SSP3DEvalDataset, self).__init__()
+        self.images_dir = os.path.join(ssp3d_dir_path, 'images')
+        self.silhouettes_dir = os.path.join(ssp3d_dir_path, 'silhouettes')
+
+        data = np.load(os.path.join(ssp3d_dir_path, 'labels.npz'))
+        self.frame_fnames = data['fnames']
+        self.body_shapes = data['shapes']
+        self.body_poses = data['poses']
+        self.keypoints = data['joints2D']
+        self.bbox_centres = data['bbox_centres']  # Tight bounding box centre
+        self.bbox_whs = data['bbox_whs']  # Tight bounding box width/height
+        self.genders = data['genders']
+
+        self.img_wh = config.DATA.PROXY_REP_SIZE
+        self.hmaps_gaussian_std = config.DATA.HEATMAP_GAUSSIAN_STD
+        self.bbox_scale_factor = config.DATA.BBOX_SCALE_FACTOR
+        self.visible_joints_threshold = visible_joints_threshold
+        self._staging = None
+
+    def __getstate__(self):                      # a worker process gets the host data only
+        state = dict(self.__dict__)
+        state['_staging'] = None
+        return state
+
+    def __len__(self):
+        return len(self.frame_fnames)
+
+    def __getitem__(self, index):
+        """{'image': (H,W,3) uint8, 'silhouette': (H,W) uint8, 'keypoints': (17,3) float64, 'bbox_centre': (2,) float64, 'bbox_wh':
+        float, 'shape', 'pose': float32, 'fname', 'gender': str}."""
+        if torch.is_tensor(index):
+            index = index.tolist()
+        fname = str(self.frame_fnames[index])
+        return {'image': data_layer.decode_rgb(os.path.join(self.images_dir, fname)),
+                'silhouette': data_layer.decode_grey(os.path.join(self.silhouettes_dir, fname)),
+                'keypoints': torch.from_numpy(np.array(self.keypoints[index], dtype=np.float64)),
+                'bbox_centre': torch.from_numpy(np.array(self.bbox_centres[index], dtype=np.float64)),
+                'bbox_wh': float(self.bbox_whs[index]),
+                'shape': torch.from_numpy(np.array(self.body_shapes[index])).float(),
+                'pose': torch.from_numpy(np.array(self.body_poses[index])).float(),
+                'fname': fname,
+                'gender': str(self.genders[index])}
+
+    def prepare_batch(self, items):
+        """-> {'image' (B,3,wh,wh), 'heatmaps' (B,17,wh,wh), 'shape', 'pose', 'silhouette' (B,wh,wh): float32; 'keypoints' (B,17,2)
+        float64; 'fname', 'gender': lists} on the current device."""
+        data_layer.require_gpu("SSP3DEvalDataset.prepare_batch")
+        if self._staging is None:
+            self._staging = data_layer.BatchStaging()
+        B, np_ = len(items), data_layer.as_numpy
+        labels = [np.stack([np_(it[k]) for it in items]) for k in ('keypoints', 'pose', 'shape')]
+        staged = self._staging.upload(labels + [np_(it['image']) for it in items] + [np_(it['silhouette']) for it in items])
+        keypoints, pose, shape = staged[:3]
+        boxes = [(float(it['bbox_centre'][0]), float(it['bbox_centre'][1]), it['bbox_wh']) for it in items]
+        crop = data_layer.eval_crop_u8(staged[3:3 + B], boxes, self.bbox_scale_factor, self.img_wh, segs=staged[3 + B:3 + 2 * B],
+                                       keypoints=keypoints)
+        heatmaps = data_layer.eval_heatmaps(crop['positions'], self.img_wh, self.hmaps_gaussian_std, keypoints=keypoints,
+                                            threshold=self.visible_joints_threshold)
+        return {'image': crop['rgb'], 'heatmaps': heatmaps, 'shape': shape.clone(), 'pose': pose.clone(), 'silhouette': crop['seg'],
+                'keypoints': crop['joints'], 'fname': [it['fname'] for it in items], 'gender': [it['gender'] for it in items]}

@@ -17,7 +17,8 @@ Two differences that this code base forces:
   loop itself drops the derived state once, at the start of every epoch, so that an epoch resumed from a checkpoint repeats the
   uninterrupted one bit for bit.
 * ``train_dataset`` / ``val_dataset`` are whatever yields the reference's item dict: 'pose' (72,) axis-angle, 'background'
-  (3, img_wh, img_wh), 'texture' (Ht, Wt, 3).  No dataset class and no image IO is part of this package.
+  (3, img_wh, img_wh), 'texture' (Ht, Wt, 3) -- or a dataset with ``prepare_batch`` (on_the_fly_smpl_train_dataset.py): its raw items
+  pass through the DataLoader as they are and each list of them becomes the batch on the device (data_layer.py).
 """
 import copy
 import os
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader
 
-from . import cam_utils, rigid_transform_utils as rtu, sampling_utils, textured_renderer, train_augmentation
+from . import cam_utils, data_layer, rigid_transform_utils as rtu, sampling_utils, textured_renderer, train_augmentation
 from .checkpoint_utils import load_training_info_from_checkpoint
 from .device_state import DeviceStateModule
 from .label_conversions import ALL_JOINTS_TO_COCO_MAP, ALL_JOINTS_TO_H36M_MAP, H36M_TO_J14
@@ -185,9 +186,13 @@ def train_poseMF_shapeGaussian_net(pose_shape_model,
     if getattr(pose_shape_model.image_encoder, "_forward_only", False):          # before a file, a loader or a buffer is touched
         raise NotImplementedError("training a net with the Bottleneck (ResNet-50) encoder is not implemented: its encoder runs forward "
                                   "only (MODEL.NUM_RESNET_LAYERS = 18 trains)")
-    loader = lambda dataset: DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, shuffle=True, drop_last=True,
-                                        num_workers=cfg.TRAIN.NUM_WORKERS, pin_memory=cfg.TRAIN.PIN_MEMORY)
+    def loader(dataset):
+        # a dataset with prepare_batch (on_the_fly_smpl_train_dataset.py) hands over raw items: its batch is formed on the device
+        raw = data_layer.preparer(dataset) is not None
+        return DataLoader(dataset, batch_size=cfg.TRAIN.BATCH_SIZE, shuffle=True, drop_last=True, num_workers=cfg.TRAIN.NUM_WORKERS,
+                          pin_memory=False if raw else cfg.TRAIN.PIN_MEMORY, collate_fn=data_layer.passthrough_collate if raw else None)
     dataloaders = {'train': loader(train_dataset), 'val': loader(val_dataset)}
+    prepare = {'train': data_layer.preparer(train_dataset), 'val': data_layer.preparer(val_dataset)}
 
     if checkpoint is not None:
         current_epoch, best_epoch, best_model_wts, best_epoch_val_metrics = load_training_info_from_checkpoint(checkpoint, save_val_metrics)
@@ -236,6 +241,8 @@ def train_poseMF_shapeGaussian_net(pose_shape_model,
                     print('Validation.')
                     pose_shape_model.eval()
                 for samples_batch in _progress(dataloaders[split]):
+                    if prepare[split] is not None:
+                        samples_batch = prepare[split](samples_batch)
                     step(samples_batch, split)
 
             metrics_tracker.update_per_epoch()                  # the epoch's one read-back; raises for an image that had no body pixel

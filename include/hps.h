@@ -1538,6 +1538,106 @@ typedef struct hps_hrnet_keypoints_args {
 int hps_sizeof_hrnet_keypoints_args(void);
 int hps_hrnet_keypoints(const hps_hrnet_keypoints_args* args /* HOST */, hps_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Device-side batch preparation for the datasets  (csrc/data_layer.hip; data/on_the_fly_smpl_train_dataset.py,
+ * data/ssp3d_eval_dataset.py, data/pw3d_eval_dataset.py, utils/image_utils.py:62-231)
+ * ---------------------------------------------------------------------------------------- */
+
+/* Bandwidth kernels: no LDS, no atomics, nothing allocated, bit-identical from run to run.  Per-image descriptors go BY VALUE in the
+ * argument structs (HOST memory), at most HPS_FRONTEND_MAX_IMAGES images per launch; every entry point validates on the host -- image
+ * sizes, bank indices -- before its launch and only enqueues.  cv2.resize and cv2.warpAffine are restated from OpenCV's sources as we
+ * understand them; they have NOT been run against OpenCV itself. */
+
+/* hps_texture_gather  (on_the_fly_smpl_train_dataset.py:72-81)
+ * out (B, Ht, Wt, 3) float32 = float(u8) / 255.0f, a true division (equal to float32(k / 255.), the reference's float64 route, for all
+ * 256 levels), of texture idx[b] of the grey (is_grey[b] != 0) or the non-grey bank; banks (n, Ht, Wt, 3) uint8 on the device.  Any
+ * Ht, Wt: a texture whose byte count is no multiple of 4, or whose place in the bank is unaligned, goes element by element. */
+typedef struct hps_texture_gather_args {
+    int struct_bytes;
+    int B, Ht, Wt;
+    int n_grey, n_nongrey;
+    const uint8_t* grey;                                       /* (n_grey, Ht, Wt, 3) or NULL with n_grey == 0 */
+    const uint8_t* nongrey;                                    /* (n_nongrey, Ht, Wt, 3) or NULL with n_nongrey == 0 */
+    float* out;                                                /* (B, Ht, Wt, 3) */
+    int is_grey[HPS_FRONTEND_MAX_IMAGES];
+    int idx[HPS_FRONTEND_MAX_IMAGES];
+} hps_texture_gather_args;
+int hps_sizeof_texture_gather_args(void);
+int hps_texture_gather(const hps_texture_gather_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_resize_bilinear_u8  (on_the_fly_smpl_train_dataset.py:88-94, pw3d_eval_dataset.py:45-46: cv2.resize(..., INTER_LINEAR) of a
+ * uint8 image, transposed, / 255)
+ * out (B, 3, out_h, out_w) float32 = level / 255.0f from (H, W, 3) uint8 sources of different sizes.  `level` is cv2.resize's uint8
+ * result: per axis f = float((d + 0.5) src / dst - 0.5) (the product in float64), s = floor(f), f -= s; horizontally s < 0 -> (0, f = 0)
+ * and s >= W - 1 -> (W - 1, f = 0), vertically the two ROWS are clamped and f is kept; coefficients rint((1 - f) 2048), rint(f 2048);
+ * rows h = S[x0] a0 + S[x1] a1, then level = (((b0 (h0 >> 4)) >> 16) + ((b1 (h1 >> 4)) >> 16) + 2) >> 2.  (At exactly half size OpenCV
+ * switches to INTER_AREA, (a + b + c + d + 2) >> 2: the formula above gives the same level there.) */
+typedef struct hps_u8_image {
+    const uint8_t* src;                                        /* (H, W, 3) */
+    int H, W;
+} hps_u8_image;
+typedef struct hps_resize_bilinear_u8_args {
+    int struct_bytes;
+    int B;
+    int out_w, out_h;
+    float* out;                                                /* (B, 3, out_h, out_w) */
+    hps_u8_image image[HPS_FRONTEND_MAX_IMAGES];
+} hps_resize_bilinear_u8_args;
+int hps_sizeof_resize_bilinear_u8_args(void);
+int hps_resize_bilinear_u8(const hps_resize_bilinear_u8_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_eval_crop_u8  (ssp3d_eval_dataset.py:49-61, :74-80 through image_utils.py:145-229 with bbox_whs, no augmentation)
+ * Per image the float32 matrix of image_utils.py:190-194 -- box side times scale_factor, out_wh / box, out_wh / 2 - (out_wh / box)
+ * centre, formed in float64 as NumPy does with float64 labels and rounded to float32 on assignment -- then cv2.warpAffine's fixed-point
+ * route (csrc/cv_warp.h), constant border 0:
+ *   rgb   (B, 3, out_wh, out_wh) float32 = level / 255.0f, INTER_LINEAR on the uint8 image: weights (32 - fy)(32 - fx), ... in 1024ths
+ *         (OpenCV's 15-bit table holds exactly 32 times these), level = (sum + 512) >> 10, a tap outside the image reads 0;
+ *   seg   (B, out_wh, out_wh) float32 = the uint8 level itself, INTER_NEAREST (NULL, or an image without seg: not written / zero);
+ *   joints    (B, K, 2) float64 = the matrix applied in float64 to columns 0, 1 of keypoints (B, K, 3) float64 (:212-214);
+ *   positions (B, K, 2) int32   = joints truncated toward zero (astype(np.int16), :62), held to [-32768, 32767].
+ * keypoints, joints and positions come together or are all NULL. */
+typedef struct hps_eval_crop_image {
+    const uint8_t* rgb;                                        /* (H, W, 3) */
+    const uint8_t* seg;                                        /* (H, W) or NULL */
+    int H, W;
+    double centre_v, centre_h, side;                           /* bbox_centres[i] = (vertical, horizontal), bbox_whs[i] */
+} hps_eval_crop_image;
+typedef struct hps_eval_crop_u8_args {
+    int struct_bytes;
+    int B, out_wh, K;
+    double scale_factor;
+    const double* keypoints;                                   /* DEVICE (B, K, 3) or NULL */
+    float* rgb;
+    float* seg;                                                /* or NULL */
+    double* joints;                                            /* or NULL */
+    int32_t* positions;                                        /* or NULL */
+    hps_eval_crop_image image[HPS_FRONTEND_MAX_IMAGES];
+} hps_eval_crop_u8_args;
+int hps_sizeof_eval_crop_u8_args(void);
+int hps_eval_crop_u8(const hps_eval_crop_u8_args* args /* HOST */, hps_stream_t stream);
+
+/* pw3d_eval_dataset.py:48-53: joints (n, 2) float64 = columns 0, 1 of keypoints (n, 3) times scale (n_images, 2) (img_wh / width,
+ * img_wh / height; K rows per image), positions (n, 2) int32 = joints rounded half to even (.round()) and held to [-32768, 32767]. */
+int hps_keypoints_scale_round(const double* keypoints, const double* scale, double* joints, int32_t* positions, int B, int K,
+                              hps_stream_t stream);
+
+/* ssp3d_eval_dataset.py:62-68 / pw3d_eval_dataset.py:53-60 with label_conversions.py:94-101: out (B, K, wh, wh) float32 =
+ * exp(-((x - u) / std)^2 / 2 - ((y - v) / std)^2 / 2) in float32 for the INTEGER positions (B, K, 2) = (u, v), times the visibility
+ * flag: use_threshold != 0 zeroes joint k where column 2 of keypoints (B, K, 3) float64 is not > threshold, unless bit k of
+ * always_visible is set.  K <= 32. */
+typedef struct hps_eval_heatmaps_args {
+    int struct_bytes;
+    int B, K, wh, use_threshold;
+    float std;
+    uint32_t always_visible;
+    double threshold;
+    const int32_t* positions;
+    const double* keypoints;                                   /* read only with use_threshold != 0 */
+    float* out;
+} hps_eval_heatmaps_args;
+int hps_sizeof_eval_heatmaps_args(void);
+int hps_eval_heatmaps(const hps_eval_heatmaps_args* args /* HOST */, hps_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
