@@ -104,6 +104,10 @@ _PROTOTYPES = {
     "hps_conv_wgrad_slice_pixels": [_I, _I],
     "hps_conv_wgrad_workspace": [_I] * 9,
     "hps_conv_dgrad": [_P] * 4 + [_I] * 12 + [_P],
+    "hps_conv1x1_dgrad": [_P] * 4 + [_I] * 9 + [_P],
+    "hps_conv1x1_wgrad": [_P] * 4 + [_I] * 9 + [_P],
+    "hps_conv1x1_wgrad_slice_pixels": [_I, _I],
+    "hps_conv1x1_wgrad_workspace": [_I] * 6,
     "hps_relu_gate_pad": [_P] * 4 + [_I] * 6 + [_P],
     "hps_relu_gate_workspace": [_I] * 4,
     "hps_maxpool3x3s2_backward": [_P] * 3 + [_I] * 5 + [_P],
@@ -160,7 +164,7 @@ _PROTOTYPES = {
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
-             "hps_conv_wgrad_workspace": _c.c_size_t, "hps_relu_gate_workspace": _c.c_size_t,
+             "hps_conv_wgrad_workspace": _c.c_size_t, "hps_conv1x1_wgrad_workspace": _c.c_size_t, "hps_relu_gate_workspace": _c.c_size_t,
              "hps_bn_batch_stats_workspace": _c.c_size_t, "hps_bn_train_backward_sums_workspace": _c.c_size_t}
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

@@ -9,7 +9,9 @@
 //
 // All four map kernels are bandwidth kernels of one shape.  The interior of a frame row (b, iy) is W C contiguous floats, so a
 // workgroup of 256 lanes walks whole rows with 16-byte loads, four independent loads per lane in flight; 256 % (C / 4) == 0 keeps a
-// lane on the same four channels for the whole walk (one division per row, none per pixel).  At most 2048 workgroups.  The two
+// lane on the same four channels for the whole walk (one division per row, none per pixel).  More than 1024 channels (a multiple of
+// 1024: the Bottleneck encoder's 2048) are cut into windows of 1024, one per blockIdx.y; up to 1024 channels the walk, and with it
+// every sum's order, is what it was.  At most 2048 workgroups per window.  The two
 // reductions cut the B H rows into bn_chunks(B H) contiguous chunks -- a rule on the row count alone --, accumulate in float64 per
 // lane, add the lanes of a channel in lane order through LDS and the chunks in a fixed order in a finish launch: no atomics, bitwise
 // repeatable.  The variance uses sums shifted by a per-channel pivot (the channel's first interior pixel), so |mean| >> std costs
@@ -33,9 +35,25 @@ __device__ __forceinline__ size_t bn_row_base(long r, int H, int W, int C, int p
 
 __device__ __forceinline__ float4 ld4(const float* p, int j) { return reinterpret_cast<const float4*>(p)[j]; }
 
+// The lane's place in a row of W pixels x cq channel quads: its quad c4 of the pixel (window blockIdx.y of cw = min(cq, 256) quads), its
+// first pixel p0 and the pixels it advances per step; the 16-byte element of pixel px is px cq + c4.  With cq <= 256 that is element
+// threadIdx.x + 256 k of the row for k = 0, 1, ...: the walk of a contiguous row.
+struct BnLane {
+    int cq, cw, q, c4, p0, pstep;
+    __device__ __forceinline__ BnLane(int C) {
+        cq = C >> 2;
+        cw = cq < BN_THREADS ? cq : BN_THREADS;
+        q = threadIdx.x % cw;
+        c4 = blockIdx.y * cw + q;
+        p0 = threadIdx.x / cw;
+        pstep = BN_THREADS / cw;
+    }
+    __device__ __forceinline__ int at(int px) const { return px * cq + c4; }
+};
+
 // the lanes of a channel quad (lane % cq) hold 8 doubles each: per value, the sum over those lanes in lane order -> part[chunk][8 cq]
 // laid out as [value / 4][channel] (value 0..3: first quantity of channels 4 q .. 4 q + 3, 4..7: second quantity)
-__device__ __forceinline__ void bn_block_reduce(const double (&a)[8], double* red, double* part_chunk, int cq, int C) {
+__device__ __forceinline__ void bn_block_reduce(const double (&a)[8], double* red, double* part_chunk, int cq, int C, int c0 = 0) {
     const int t = threadIdx.x;
 #pragma unroll
     for (int i = 0; i < 8; ++i) red[i * BN_THREADS + t] = a[i];
@@ -45,17 +63,18 @@ __device__ __forceinline__ void bn_block_reduce(const double (&a)[8], double* re
         const int i = o / cq, q = o - i * cq;
         double s = 0.0;
         for (int p = 0; p < peers; ++p) s += red[i * BN_THREADS + q + p * cq];
-        part_chunk[(i >> 2) * C + 4 * q + (i & 3)] = s;
+        part_chunk[(i >> 2) * C + c0 + 4 * q + (i & 3)] = s;
     }
 }
 
 __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const float* __restrict__ z, double* __restrict__ part, int B, int H, int W,
                                                               int C, int pad, int nchunks) {
     __shared__ double red[8 * BN_THREADS];
-    const int t = threadIdx.x, cq = C >> 2, q = t % cq, rowv = W * cq;
+    const BnLane L(C);
+    const int ps = L.pstep;
     const long R = (long)B * H;
     const long r0 = (long)blockIdx.x * R / nchunks, r1 = ((long)blockIdx.x + 1) * R / nchunks;
-    const float4 k = ld4(z + bn_row_base(0, H, W, C, pad), q);                 // the pivots of this lane's four channels
+    const float4 k = ld4(z + bn_row_base(0, H, W, C, pad), L.c4);              // the pivots of this lane's four channels
     double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     auto add = [&](const float4& v) {
         const double d0 = (double)v.x - (double)k.x, d1 = (double)v.y - (double)k.y, d2 = (double)v.z - (double)k.z,
@@ -65,14 +84,14 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const float* __res
     };
     for (long r = r0; r < r1; ++r) {
         const float* p = z + bn_row_base(r, H, W, C, pad);
-        int j = t;
-        for (; j + 3 * BN_THREADS < rowv; j += 4 * BN_THREADS) {
-            const float4 v0 = ld4(p, j), v1 = ld4(p, j + BN_THREADS), v2 = ld4(p, j + 2 * BN_THREADS), v3 = ld4(p, j + 3 * BN_THREADS);
+        int px = L.p0;
+        for (; px + 3 * ps < W; px += 4 * ps) {
+            const float4 v0 = ld4(p, L.at(px)), v1 = ld4(p, L.at(px + ps)), v2 = ld4(p, L.at(px + 2 * ps)), v3 = ld4(p, L.at(px + 3 * ps));
             add(v0); add(v1); add(v2); add(v3);
         }
-        for (; j < rowv; j += BN_THREADS) add(ld4(p, j));
+        for (; px < W; px += ps) add(ld4(p, L.at(px)));
     }
-    bn_block_reduce(a, red, part + (size_t)blockIdx.x * 2 * C, cq, C);
+    bn_block_reduce(a, red, part + (size_t)blockIdx.x * 2 * C, L.cw, C, 4 * (int)blockIdx.y * L.cw);
 }
 
 // the chunks' partials of BN_FIN_CH channels, both quantities: 32 slices (chunk % 32) in chunk order each, then the slices in order;
@@ -155,9 +174,10 @@ __global__ __launch_bounds__(BN_THREADS) void bn_fold_kernel(const double* __res
 __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const float* z, const float* __restrict__ scale,
                                                               const float* __restrict__ shift, const float* residual, float* y, int B,
                                                               int H, int W, int C, int zpad, int ypad, int relu) {
-    const int t = threadIdx.x, cq = C >> 2, q = t % cq, rowv = W * cq;
+    const BnLane L(C);
+    const int ps = L.pstep;
     const long R = (long)B * H;
-    const float4 sc = ld4(scale, q), sh = ld4(shift, q);
+    const float4 sc = ld4(scale, L.c4), sh = ld4(shift, L.c4);
     auto act = [&](const float4& a, const float4& r) {
         float4 v = make_float4(a.x * sc.x + sh.x + r.x, a.y * sc.y + sh.y + r.y, a.z * sc.z + sh.z + r.z, a.w * sc.w + sh.w + r.w);
         if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
@@ -169,17 +189,17 @@ __global__ __launch_bounds__(BN_THREADS) void bn_apply_kernel(const float* z, co
         const size_t yo = bn_row_base(r, H, W, C, ypad);
         const float* pr = residual ? residual + yo : nullptr;
         float4* py = reinterpret_cast<float4*>(y + yo);
-        int j = t;
-        for (; j + 3 * BN_THREADS < rowv; j += 4 * BN_THREADS) {
+        int px = L.p0;
+        for (; px + 3 * ps < W; px += 4 * ps) {
             float4 a[4], rr[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) a[u] = ld4(pz, j + u * BN_THREADS);
+            for (int u = 0; u < 4; ++u) a[u] = ld4(pz, L.at(px + u * ps));
 #pragma unroll
-            for (int u = 0; u < 4; ++u) rr[u] = pr ? ld4(pr, j + u * BN_THREADS) : zero;
+            for (int u = 0; u < 4; ++u) rr[u] = pr ? ld4(pr, L.at(px + u * ps)) : zero;
 #pragma unroll
-            for (int u = 0; u < 4; ++u) py[j + u * BN_THREADS] = act(a[u], rr[u]);
+            for (int u = 0; u < 4; ++u) py[L.at(px + u * ps)] = act(a[u], rr[u]);
         }
-        for (; j < rowv; j += BN_THREADS) py[j] = act(ld4(pz, j), pr ? ld4(pr, j) : zero);
+        for (; px < W; px += ps) py[L.at(px)] = act(ld4(pz, L.at(px)), pr ? ld4(pr, L.at(px)) : zero);
     }
 }
 
@@ -188,10 +208,11 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_sums_kernel(float* __restri
                                                                  const double* __restrict__ invstd, double* __restrict__ part, int B, int H,
                                                                  int W, int C, int gpad, int zpad, int ypad, int nchunks) {
     __shared__ double red[8 * BN_THREADS];
-    const int t = threadIdx.x, cq = C >> 2, q = t % cq, rowv = W * cq;
+    const BnLane L(C);
+    const int ps = L.pstep, c = 4 * L.c4;
     const long R = (long)B * H;
     const long r0 = (long)blockIdx.x * R / nchunks, r1 = ((long)blockIdx.x + 1) * R / nchunks;
-    const double m0 = mean[4 * q], m1 = mean[4 * q + 1], m2 = mean[4 * q + 2], m3 = mean[4 * q + 3];
+    const double m0 = mean[c], m1 = mean[c + 1], m2 = mean[c + 2], m3 = mean[c + 3];
     double a[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     auto add = [&](const float4& gv, const float4& zv) {
         a[0] += (double)gv.x; a[1] += (double)gv.y; a[2] += (double)gv.z; a[3] += (double)gv.w;
@@ -208,39 +229,39 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_sums_kernel(float* __restri
         float* pg = g + bn_row_base(r, H, W, C, gpad);
         const float* pz = z + bn_row_base(r, H, W, C, zpad);
         const float* py = y ? y + bn_row_base(r, H, W, C, ypad) : nullptr;
-        int j = t;
-        for (; j + 3 * BN_THREADS < rowv; j += 4 * BN_THREADS) {
+        int px = L.p0;
+        for (; px + 3 * ps < W; px += 4 * ps) {
             float4 gv[4], zv[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) gv[u] = ld4(pg, j + u * BN_THREADS);
+            for (int u = 0; u < 4; ++u) gv[u] = ld4(pg, L.at(px + u * ps));
 #pragma unroll
-            for (int u = 0; u < 4; ++u) zv[u] = ld4(pz, j + u * BN_THREADS);
+            for (int u = 0; u < 4; ++u) zv[u] = ld4(pz, L.at(px + u * ps));
             if (py) {
                 float4 yv[4];
 #pragma unroll
-                for (int u = 0; u < 4; ++u) yv[u] = ld4(py, j + u * BN_THREADS);
+                for (int u = 0; u < 4; ++u) yv[u] = ld4(py, L.at(px + u * ps));
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     gv[u] = gate(gv[u], yv[u]);
-                    reinterpret_cast<float4*>(pg)[j + u * BN_THREADS] = gv[u];
+                    reinterpret_cast<float4*>(pg)[L.at(px + u * ps)] = gv[u];
                 }
             }
 #pragma unroll
             for (int u = 0; u < 4; ++u) add(gv[u], zv[u]);
         }
-        for (; j < rowv; j += BN_THREADS) {
-            float4 gv = ld4(pg, j);
-            const float4 zv = ld4(pz, j);
+        for (; px < W; px += ps) {
+            float4 gv = ld4(pg, L.at(px));
+            const float4 zv = ld4(pz, L.at(px));
             if (py) {
-                gv = gate(gv, ld4(py, j));
-                reinterpret_cast<float4*>(pg)[j] = gv;
+                gv = gate(gv, ld4(py, L.at(px)));
+                reinterpret_cast<float4*>(pg)[L.at(px)] = gv;
             }
             add(gv, zv);
         }
     }
     // sum g (z - mean) -> sum g zhat: one multiplication per lane instead of one per element
-    a[4] *= invstd[4 * q]; a[5] *= invstd[4 * q + 1]; a[6] *= invstd[4 * q + 2]; a[7] *= invstd[4 * q + 3];
-    bn_block_reduce(a, red, part + (size_t)blockIdx.x * 2 * C, cq, C);
+    a[4] *= invstd[c]; a[5] *= invstd[c + 1]; a[6] *= invstd[c + 2]; a[7] *= invstd[c + 3];
+    bn_block_reduce(a, red, part + (size_t)blockIdx.x * 2 * C, L.cw, C, 4 * (int)blockIdx.y * L.cw);
 }
 
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dz_kernel(const float* __restrict__ g, const float* __restrict__ z,
@@ -248,12 +269,13 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dz_kernel(const float* __re
                                                                const float* __restrict__ gamma, const double* __restrict__ sums,
                                                                float* __restrict__ dz, int B, int H, int W, int C, int gpad, int zpad,
                                                                int dpad, double inv_n) {
-    const int t = threadIdx.x, cq = C >> 2, q = t % cq, rowv = W * cq;
+    const BnLane L(C);
+    const int ps = L.pstep;
     const long R = (long)B * H;
     double m[4], sc[4], k1[4], k2[4];                  // dz = sc (g - k1 - (z - mean) k2), k1 = d beta / n, k2 = d gamma invstd / n
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int c = 4 * q + i;
+        const int c = 4 * L.c4 + i;
         m[i] = mean[c];
         sc[i] = (double)gamma[c] * invstd[c];
         k1[i] = sums[c] * inv_n;
@@ -269,34 +291,38 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dz_kernel(const float* __re
         const float* pg = g + bn_row_base(r, H, W, C, gpad);
         const float* pz = z + bn_row_base(r, H, W, C, zpad);
         float4* pd = reinterpret_cast<float4*>(dz + bn_row_base(r, H, W, C, dpad));
-        int j = t;
-        for (; j + 3 * BN_THREADS < rowv; j += 4 * BN_THREADS) {
+        int px = L.p0;
+        for (; px + 3 * ps < W; px += 4 * ps) {
             float4 gv[4], zv[4];
 #pragma unroll
-            for (int u = 0; u < 4; ++u) gv[u] = ld4(pg, j + u * BN_THREADS);
+            for (int u = 0; u < 4; ++u) gv[u] = ld4(pg, L.at(px + u * ps));
 #pragma unroll
-            for (int u = 0; u < 4; ++u) zv[u] = ld4(pz, j + u * BN_THREADS);
+            for (int u = 0; u < 4; ++u) zv[u] = ld4(pz, L.at(px + u * ps));
 #pragma unroll
-            for (int u = 0; u < 4; ++u) pd[j + u * BN_THREADS] = one(gv[u], zv[u]);
+            for (int u = 0; u < 4; ++u) pd[L.at(px + u * ps)] = one(gv[u], zv[u]);
         }
-        for (; j < rowv; j += BN_THREADS) pd[j] = one(ld4(pg, j), ld4(pz, j));
+        for (; px < W; px += ps) pd[L.at(px)] = one(ld4(pg, L.at(px)), ld4(pz, L.at(px)));
     }
 }
 
-// C a multiple of 4 with 256 % (C / 4) == 0 (4, 8, ..., 1024: a lane stays on its channels), W C / 4 and B H W below 2^31
+// C a multiple of 4 with 256 % (C / 4) == 0 (4, 8, ..., 1024: a lane stays on its channels) or a multiple of 1024 (windows of 1024
+// channels, at most 64 of them), W C / 4 and B H W below 2^31
 bool bn_geometry(int B, int H, int W, int C) {
-    if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4 != 0 || BN_THREADS % (C / 4) != 0) return false;
+    if (B < 1 || H < 1 || W < 1 || C < 4 || C % 4 != 0 || C > 65536) return false;
+    if (BN_THREADS % (C / 4) != 0 && C % (4 * BN_THREADS) != 0) return false;
     return (long)W * (C / 4) < (1L << 31) && (long)B * H * W < (1L << 31);
 }
 
-unsigned bn_grid(int B, int H) { return (unsigned)bn_chunks((long)B * H); }
+unsigned bn_windows(int C) { return C > 4 * BN_THREADS ? (unsigned)(C / (4 * BN_THREADS)) : 1u; }
+
+dim3 bn_grid(int B, int H, int C) { return dim3((unsigned)bn_chunks((long)B * H), bn_windows(C)); }
 
 }  // namespace
 }  // namespace hps
 
 using namespace hps;
 
-static const char* BN_GEOMETRY = "geometry (B, H, W >= 1; C = 4, 8, 16, ..., 1024; pads >= 0; B H W < 2^31)";
+static const char* BN_GEOMETRY = "geometry (B, H, W >= 1; C = 4, 8, 16, ..., 1024 or a multiple of 1024; pads >= 0; B H W < 2^31)";
 
 extern "C" size_t hps_bn_batch_stats_workspace(int B, int H, int W, int C) {
     if (!bn_geometry(B, H, W, C)) return 0;
@@ -309,7 +335,7 @@ extern "C" int hps_bn_batch_stats(const float* z, double* workspace, double* mea
     if (!bn_geometry(B, H, W, C) || pad < 0) return bad_arg(BN_GEOMETRY);
     hipStream_t s = (hipStream_t)stream;
     const int nchunks = bn_chunks((long)B * H);
-    bn_stats_kernel<<<nchunks, BN_THREADS, 0, s>>>(z, workspace, B, H, W, C, pad, nchunks);
+    bn_stats_kernel<<<dim3(nchunks, bn_windows(C)), BN_THREADS, 0, s>>>(z, workspace, B, H, W, C, pad, nchunks);
     // the pivots: the first interior pixel of the frame
     const float* pivot = z + ((size_t)pad * (W + 2 * pad) + pad) * C;
     bn_finish_kernel<true><<<ceil_div(C, BN_FIN_CH), BN_THREADS, 0, s>>>(workspace, nchunks, C, (double)B * H * W, pivot, mean, var);
@@ -335,7 +361,7 @@ extern "C" int hps_bn_apply_act_pad(const float* z, const float* scale, const fl
     if (!z || !scale || !shift || !y) return bad_arg("hps_bn_apply_act_pad: null pointer");
     if (!bn_geometry(B, H, W, C) || zpad < 0 || ypad < 0) return bad_arg(BN_GEOMETRY);
     if (z == y && zpad != ypad) return bad_arg("hps_bn_apply_act_pad: in place needs zpad == ypad");
-    bn_apply_kernel<<<bn_grid(B, H), BN_THREADS, 0, (hipStream_t)stream>>>(z, scale, shift, residual, y, B, H, W, C, zpad, ypad, relu);
+    bn_apply_kernel<<<bn_grid(B, H, C), BN_THREADS, 0, (hipStream_t)stream>>>(z, scale, shift, residual, y, B, H, W, C, zpad, ypad, relu);
     return check_launch("hps_bn_apply_act_pad");
 }
 
@@ -348,7 +374,7 @@ extern "C" int hps_bn_train_backward_sums(float* g, const float* z, const float*
     if (!bn_geometry(B, H, W, C) || gpad < 0 || zpad < 0 || ypad < 0) return bad_arg(BN_GEOMETRY);
     hipStream_t s = (hipStream_t)stream;
     const int nchunks = bn_chunks((long)B * H);
-    bn_bwd_sums_kernel<<<nchunks, BN_THREADS, 0, s>>>(g, z, y, mean, invstd, workspace, B, H, W, C, gpad, zpad, ypad, nchunks);
+    bn_bwd_sums_kernel<<<dim3(nchunks, bn_windows(C)), BN_THREADS, 0, s>>>(g, z, y, mean, invstd, workspace, B, H, W, C, gpad, zpad, ypad, nchunks);
     bn_finish_kernel<false><<<ceil_div(C, BN_FIN_CH), BN_THREADS, 0, s>>>(workspace, nchunks, C, 1.0, nullptr, sums, sums + C);
     return check_launch("hps_bn_train_backward_sums");
 }
@@ -359,7 +385,7 @@ extern "C" int hps_bn_train_backward_dz(const float* g, const float* z, const do
     if (!g || !z || !mean || !invstd || !gamma || !sums || !dz) return bad_arg("hps_bn_train_backward_dz: null pointer");
     if (!bn_geometry(B, H, W, C) || gpad < 0 || zpad < 0 || dpad < 0) return bad_arg(BN_GEOMETRY);
     if (dz == g || dz == z) return bad_arg("hps_bn_train_backward_dz: out of place only (the gated cotangent has other readers)");
-    bn_bwd_dz_kernel<<<bn_grid(B, H), BN_THREADS, 0, (hipStream_t)stream>>>(g, z, mean, invstd, gamma, sums, dz, B, H, W, C, gpad, zpad, dpad,
+    bn_bwd_dz_kernel<<<bn_grid(B, H, C), BN_THREADS, 0, (hipStream_t)stream>>>(g, z, mean, invstd, gamma, sums, dz, B, H, W, C, gpad, zpad, dpad,
                                                                            1.0 / ((double)B * H * W));
     return check_launch("hps_bn_train_backward_dz");
 }

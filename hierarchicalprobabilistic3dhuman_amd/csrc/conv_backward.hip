@@ -14,32 +14,15 @@
 // is cut into slices of wgrad_slice_pixels(Ho, Wo) pixels (a rule on the map alone), each slice's partial goes to the workspace and
 // the finish pass adds the partials in slice order in float64 and rounds once.  The data gradient contracts over taps x Cout.  Inside
 // a slice / over taps x Cout the chain is cut into pieces of 64 products whose partials are added in order in fp32 (see WGRAD_CHAIN).
-#include "hps_common.h"
+#include "conv_backward.h"      // f32x16, WGRAD_CHAIN, DGRAD_CHAIN, zero16, mfma_row: shared with csrc/conv1x1_backward.hip
 
 namespace hps {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __host__ __device__ inline int wgrad_slice_pixels(int Ho, int Wo) {
     const long p = (long)Ho * Wo;
     return p < 128 ? 128 : (p > 512 ? 512 : (int)p);
 }
-
-// An MFMA accumulator is a serial fp32 chain; both GEMMs cut theirs into pieces of 64 products (WGRAD_CHAIN pixels, DGRAD_CHAIN output
-// channels) and add the pieces in order: the rounding error of a sum of n terms grows like sqrt(n) of the piece, not of the whole.
-constexpr int WGRAD_CHAIN = 64;
-constexpr int DGRAD_CHAIN = 64;
-
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 z;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) z[i] = 0.0f;
-    return z;
-}
-
-// row of a 32x32 MFMA result held in register i of lane half h (the column is lane & 31)
-__device__ __forceinline__ int mfma_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
 // ---- weight gradient: one wave per (64 output channels, 32 NT input channels, tap, pixel slice) ----
 template <int NT>

@@ -191,6 +191,12 @@ class PoseMFShapeGaussianNet(DeviceStateModule):
         default, ``.train()`` stays refused."""
         self.image_encoder.set_batchnorm_training(on)
 
+    def set_differentiable_encoder(self, on=True):
+        """Opt a net with the Bottleneck (MODEL.NUM_RESNET_LAYERS = 50) encoder in to the encoder's backward, its training-mode
+        BatchNorm, its in-place weight refresh and the training loop (ResNet.set_differentiable); a no-op for the 18-layer encoder, which
+        always is."""
+        self.image_encoder.set_differentiable(on)
+
     def set_differentiable_factors(self, on=True):
         """Opt in to ``pose_U`` / ``pose_V`` as differentiable outputs, as the reference's stage-2 step needs them
         (train/train_poseMF_shapeGaussian_net.py:292-320: the sampled rotations depend on them, utils/sampling_utils.py:105-111, 140-141).

@@ -31,6 +31,10 @@ statistics.  Bitwise repeatable; a training layer's output depends on the whole 
 the batch size holds for eval layers only.  From the first differentiable forward on
 the module compares its parameters' ``_version`` counters with those recorded by ``prepare()`` and refolds the filters after an
 optimiser step, as PoseMFShapeGaussianNet does for the head.
+
+The Bottleneck (ResNet-50) encoder takes all of this after ``ResNet.set_differentiable(True)`` and nothing of it before: the backward
+walks a block's convolutions from the last to the first (``_backward``), and the two gradients of its 1x1 layers run as LDS-tiled GEMMs
+(csrc/conv1x1_backward.hip, ``gemm_backward``) where ``_gemm_dgrad`` / ``_gemm_wgrad`` send them.
 """
 import collections
 
@@ -403,10 +407,14 @@ class _Block(tuple):
 
 
 class ResNet(DeviceStateModule):
-    """models/resnet.py:125-217 for BasicBlock and Bottleneck stacks.  A Bottleneck encoder runs forward only (eval-mode BatchNorm,
-    no_grad): its backward, training-mode BatchNorm and in-place weight refresh are refused, never computed wrongly."""
+    """models/resnet.py:125-217 for BasicBlock and Bottleneck stacks.  A freshly built Bottleneck encoder runs forward only (eval-mode
+    BatchNorm, no_grad): a differentiable forward, training-mode BatchNorm and the in-place weight refresh are refused, never computed
+    wrongly.  ``set_differentiable(True)`` opts such an encoder in to what the ResNet-18 encoder does: the differentiable forward
+    (_EncoderFunction, the block walk of _backward, the 1x1 GEMM kernels of csrc/conv1x1_backward.hip), set_batchnorm_training(True)
+    and then ``.train()``, refresh_weights() in place, the training loop.  A BasicBlock encoder is always differentiable."""
 
     SWITCHES = ("_winograd", "_latency", "composite", "fused_pool", "fold_downsample", "stem_reads_nchw", "_bn_training")
+    # (``_differentiable`` and ``gemm_backward`` change no forward launch and nothing the device state holds: no SWITCHES entry)
 
     def __init__(self, layers, in_channels, block=BasicBlock):
         super().__init__()
@@ -451,6 +459,11 @@ class ResNet(DeviceStateModule):
         # themselves -- stem_frames -- use the frame-fed kernel either way).
         self.stem_reads_nchw = True
         self._track_versions = False   # set by the first differentiable forward: parameters may now change in place (optimiser steps)
+        self._differentiable = block is BasicBlock      # set_differentiable: a Bottleneck encoder opts in
+        # the backward's 1x1 / pad 0 layers on the LDS-tiled GEMM kernels (hps_conv1x1_dgrad: the bits of hps_conv_dgrad; hps_conv1x1_wgrad:
+        # another slice length, other last bits) where _gemm_dgrad / _gemm_wgrad -- rules on the layer's shape alone -- say so.  False:
+        # every layer on hps_conv_dgrad / hps_conv_wgrad (the cross-check of the tests)
+        self.gemm_backward = True
 
     def _make_layer(self, planes, blocks, stride=1):
         """models/resnet.py:178-200 for either block."""
@@ -466,8 +479,21 @@ class ResNet(DeviceStateModule):
 
     @property
     def _forward_only(self):
-        """A Bottleneck encoder: forward under no_grad with eval-mode BatchNorm only."""
-        return self.block is not BasicBlock
+        """A Bottleneck encoder that has not opted in (set_differentiable): forward under no_grad with eval-mode BatchNorm only."""
+        return self.block is not BasicBlock and not self.__dict__.get("_differentiable", False)
+
+    def set_differentiable(self, on=True):
+        """Opt a Bottleneck (ResNet-50) encoder in to the backward: with it on, a forward under grad mode runs through
+        _EncoderFunction as the ResNet-18 encoder's does (the launches and bits of a no_grad forward), set_batchnorm_training(True) and
+        then .train() are accepted (every BatchNorm by its own flag, as for ResNet-18), and refresh_weights() rewrites the kernel-side
+        weights in place.  Off (the default for Bottleneck): the refusals of a forward-only encoder.  A BasicBlock encoder is always
+        differentiable: True is a no-op, False a ValueError.  The call allocates nothing and changes no forward launch; like
+        set_winograd a property of the model: it survives .to(), load_state_dict, deepcopy and pickling."""
+        if self.block is BasicBlock:
+            if not on:
+                raise ValueError("the BasicBlock (ResNet-18) encoder is always differentiable")
+            return
+        self._differentiable = bool(on)
 
     def train(self, mode=True):
         if mode and self._forward_only:
@@ -545,7 +571,9 @@ class ResNet(DeviceStateModule):
         return self._derived("frames", key, lambda: self._new_frame_set(prep, B, C, H, W, device, stem_wino, fused_pool, from_nchw),
                              limit=6)                # a handful of batch shapes / streams at most
 
-    def _new_frame_set(self, prep, B, C, H, W, device, stem_wino, fused_pool, from_nchw):
+    def _new_frame_set(self, prep, B, C, H, W, device, stem_wino, fused_pool, from_nchw, train=False):
+        """``train``: a frame set for training flags (_train_frames, _backward_frames with flags): it owns the identity's frame of a
+        Bottleneck entry block too -- with the down-sample's or conv3's BatchNorm training, _plan takes the block apart."""
         stem = prep["stem"]
         z = lambda *shape: torch.zeros(*shape, device=device, dtype=torch.float32)
         # input frame of the direct stem: channels as the stem's filters expect them (row mode: row_c; Cin % 32 == 0: cin_p), an even
@@ -580,7 +608,7 @@ class ResNet(DeviceStateModule):
                 h, w = c.out_hw(h, w)
                 ent["c%d" % (i + 1)] = z(B, h + 2, w + 2, c.cout)
             # (a Bottleneck entry block whose down-sample rides in conv3's launch never writes the identity's frame)
-            ent["down"] = z(B, h + 2, w + 2, down.cout) if down is not None and not self._expands(blk, B, hin, win) else None
+            ent["down"] = z(B, h + 2, w + 2, down.cout) if down is not None and (train or not self._expands(blk, B, hin, win)) else None
             ent["out"] = ent["c%d" % len(convs)]         # the block's output frame
             ent["ws"] = torch.empty(ws_bytes // 4, device=device, dtype=torch.float32) if ws_bytes else None
             fs["blocks"].append(ent)
@@ -865,7 +893,7 @@ class ResNet(DeviceStateModule):
         prep = self._prepared
         if prep is None:
             return
-        if self._forward_only:          # no in-place refresh for a Bottleneck encoder yet: drop the state, which is always correct
+        if self._forward_only:          # a Bottleneck encoder that has not opted in (set_differentiable): drop the state, which is always correct
             self.invalidate()
             return
         token = self._refresh_token(prep)
@@ -884,13 +912,14 @@ class ResNet(DeviceStateModule):
         and pool: the statistics are needed between the convolution and the pool) plus one raw frame per training layer."""
         key = (B, C, H, W, _capi.stream().value, tuple(flags.values()), self._variant_state(prep))
         return self._derived("train_frames", key, lambda: self._add_raw_frames(
-            prep, self._new_frame_set(prep, B, C, H, W, device, prep["stem"].stem_winograd_ok(C, H, W), False, False), (B, C, H, W), flags), limit=4)
+            prep, self._new_frame_set(prep, B, C, H, W, device, prep["stem"].stem_winograd_ok(C, H, W), False, False, train=True), (B, C, H, W),
+            flags), limit=4)
 
     def _add_raw_frames(self, prep, fs, shape, flags):
         """... and with them the training forward's steps, ``fs["plan"]`` (_plan with ``flags``: every pointer in it is fixed)."""
         raw = {"stem": torch.empty_like(fs["stem"]) if flags["stem"] else None}
         for name, ent in zip(self._block_names(), fs["blocks"]):
-            for k in ("c1", "c2", "down"):
+            for k in [k for k in ("c1", "c2", "c3") if k in ent] + ["down"]:
                 raw[name + "." + k] = torch.empty_like(ent[k]) if ent[k] is not None and flags[name + "." + k] else None
         fs["raw"] = raw
         fs["plan"] = self._plan(prep, fs, shape, flags)
@@ -979,20 +1008,28 @@ class ResNet(DeviceStateModule):
 
         def build():
             stem = prep["stem"]
-            fs = self._new_frame_set(prep, B, C, H, W, device, stem.stem_winograd_ok(C, H, W), False, False)
+            fs = self._new_frame_set(prep, B, C, H, W, device, stem.stem_winograd_ok(C, H, W), False, False, train=bool(flags))
             z = lambda *shape: torch.zeros(*shape, device=device, dtype=torch.float32)
             g = {"xin": z(B, H + 6, W + 6, C), "stem": torch.empty_like(fs["stem"]), "pool": torch.zeros_like(fs["pool"]), "blocks": []}
             y = fs["pool"]
-            for (c1, c2, down), ent in zip(prep["blocks"], fs["blocks"]):
-                g["blocks"].append({"c1": torch.zeros_like(ent["c1"]), "c2": torch.zeros_like(ent["c2"]),
-                                    "tmp": torch.zeros_like(y) if down is not None else None})
-                y = ent["c2"]
+            for blk, ent in zip(prep["blocks"], fs["blocks"]):
+                # one cotangent frame per convolution of the main branch ("c1", "c2" [, "c3"]); "out": the block's output cotangent
+                ge = {"c%d" % i: torch.zeros_like(ent["c%d" % i]) for i in range(1, len(blk.convs) + 1)}
+                ge["out"] = ge["c%d" % len(blk.convs)]
+                ge["tmp"] = torch.zeros_like(y) if blk.down is not None else None
+                g["blocks"].append(ge)
+                y = ent["out"]
             if flags:        # raw maps of the training layers; their dz frames (out of place: the gated cotangent has other readers)
                 self._add_raw_frames(prep, fs, (B, C, H, W), flags)
                 g["dz_stem"] = torch.empty_like(fs["stem"]) if flags["stem"] else None
                 for name, ent, ge in zip(self._block_names(), fs["blocks"], g["blocks"]):
-                    ge["dz"] = torch.zeros_like(ent["c2"]) if flags[name + ".c1"] or flags[name + ".c2"] else None
-                    ge["dzd"] = torch.zeros_like(ent["c2"]) if ent["down"] is not None and flags[name + ".down"] else None
+                    by_shape = {}          # one dz frame per map shape of the block: a convolution's dz is consumed before the next is written
+                    for k in [k for k in ("c1", "c2", "c3") if k in ent]:
+                        if flags[name + "." + k]:
+                            if tuple(ent[k].shape) not in by_shape:
+                                by_shape[tuple(ent[k].shape)] = torch.zeros_like(ent[k])
+                            ge["dz_" + k] = by_shape[tuple(ent[k].shape)]
+                    ge["dzd"] = torch.zeros_like(ent["out"]) if ent["down"] is not None and flags[name + ".down"] else None
             return fs, g, prep
         return self._derived("backward_frames", key, build, limit=6)[:2]
 
@@ -1006,7 +1043,8 @@ class ResNet(DeviceStateModule):
         """(features, {name: NCHW clone}) of the recompute the backward differentiates -- the very code path: 'stem' (conv1 + bn1 +
         relu), 'pool', and per block 'layerL.j.c1' (after its ReLU), 'layerL.j.c2' (the block's output) and 'layerL.j.down'.  The
         ReLU masks (map > 0) and the pool winners of the device's function are read off these maps (the tests pin their float64
-        restatement to them)."""
+        restatement to them).  A Bottleneck: 'layerL.j.c1' and '.c2' after their ReLUs, 'layerL.j.c3' the block's output; no
+        '.down' where the down-sample rides in conv3's launch (fold_downsample: its frame is never written, and no ReLU reads it)."""
         if self._train_flags() is not None:
             raise RuntimeError("a BatchNorm is in training mode: use training_activations()")
         _capi.require_device(x, "encoder input")
@@ -1018,7 +1056,9 @@ class ResNet(DeviceStateModule):
         nchw = lambda t, p: (t[:, p:t.shape[1] - p, p:t.shape[2] - p] if p else t).permute(0, 3, 1, 2).clone()
         maps = {"stem": nchw(fs["stem"], 0), "pool": nchw(fs["pool"], 1)}
         for name, ent in zip(self._block_names(), fs["blocks"]):
-            maps[name + ".c1"], maps[name + ".c2"] = nchw(ent["c1"], 1), nchw(ent["c2"], 1)
+            for k in ("c1", "c2", "c3"):
+                if k in ent:
+                    maps[name + "." + k] = nchw(ent[k], 1)
             if ent["down"] is not None:
                 maps[name + ".down"] = nchw(ent["down"], 1)
         return maps
@@ -1064,9 +1104,22 @@ class ResNet(DeviceStateModule):
             q[key] = w.permute(2, 3, 0, 1).float().contiguous()
         return q[key]
 
+    def _gemm_dgrad(self, cb):
+        """This layer's data gradient runs on hps_conv1x1_dgrad: every 1x1 / pad 0 layer the kernel takes (identical bits, so the rule
+        is one of speed alone)."""
+        return bool(self.gemm_backward and cb.kh == cb.kw == 1 and cb.pad == 0 and cb.stride in (1, 2) and cb.cout % 8 == 0)
+
+    def _gemm_wgrad(self, cb):
+        """This layer's weight gradient runs on hps_conv1x1_wgrad (other last bits than hps_conv_wgrad): the 1x1 / pad 0 layers with
+        Cin Cout >= 16384 (at 64 -> 64 the two kernels' quartiles overlap, tools/resnet50_backward_time.py) and stride 1, or stride 2
+        from 1024 output channels on -- a rule on the layer alone that leaves the ResNet-18 encoder's three down-samples (1x1 / 2, up
+        to 512 channels) on hps_conv_wgrad, whose bits its tests pin; the price is layer2's 256 -> 512 / 2 down-sample of the
+        Bottleneck encoder, the same layer shape, which stays there too (0.63 against 0.32 ms at B = 72)."""
+        return bool(self._gemm_dgrad(cb) and cb.cin * cb.cout >= 16384 and (cb.stride == 1 or cb.cout >= 1024))
+
     def _backward(self, prep, x, g_feats, needs, flags=None, saved=None):
         """(input gradient or None, parameter gradients in _enc_params() order, None where ``needs`` does not ask) for the cotangent
-        ``g_feats`` (B, 512).  ``flags`` / ``saved``: the layers that ran on batch statistics and the (mean, invstd) the forward saved --
+        ``g_feats`` (B, 512 * block.expansion). ``flags`` / ``saved``: the layers that ran on batch statistics and the (mean, invstd) the forward saved --
         the recompute applies them (no reduction, no running-buffer update) and writes the raw maps; such a layer's backward is
         hps_bn_train_backward_sums (with the ReLU gate in the same sweep where the block allows it) and hps_bn_train_backward_dz, then
         the weight gradient of dz IS dW and the data gradient takes the unscaled filter.  ``needs``: [input] + one flag per parameter.  Kernels whose result nobody wants are not launched: no
@@ -1120,17 +1173,25 @@ class ResNet(DeviceStateModule):
                        D(sums), P(dz), B, h, w, cb.cout, gpad, gpad, gpad, s)
             return dz
 
+        def wgrad(cb, xf, ipad, cx, cin, hin, win, g, gpad):
+            """G (Cout, KH, KW, Cin) = corr(xf, g): hps_conv1x1_wgrad where _gemm_wgrad sends the layer, else hps_conv_wgrad."""
+            G = torch.empty(cb.cout, cb.kh, cb.kw, cin, device=dev, dtype=torch.float32)
+            if self._gemm_wgrad(cb):
+                ws = scratch(int(lib.hps_conv1x1_wgrad_workspace(B, hin, win, cin, cb.cout, cb.stride)), torch.float32)
+                _capi.call("hps_conv1x1_wgrad", P(xf), P(g), P(G), P(ws), B, hin, win, ipad, cx, cin, cb.cout, cb.stride, gpad, s)
+            else:
+                ws = scratch(int(lib.hps_conv_wgrad_workspace(B, hin, win, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad)), torch.float32)
+                _capi.call("hps_conv_wgrad", P(xf), P(g), P(G), P(ws), B, hin, win, ipad, cx, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad,
+                           gpad, s)
+            return G
+
         def train_params(name, cb, xf, ipad, cx, cin, hin, win, dz, gpad, sums):
             """Gradients of a training layer: dW = corr(x, dz), d gamma and d beta are the sums themselves."""
             conv, bn = mods[name]
             w_w, w_g, w_b = want[name]
             dW = None
             if w_w:
-                G = torch.empty(cb.cout, cb.kh, cb.kw, cin, device=dev, dtype=torch.float32)
-                ws = scratch(int(lib.hps_conv_wgrad_workspace(B, hin, win, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad)), torch.float32)
-                _capi.call("hps_conv_wgrad", P(xf), P(dz), P(G), P(ws), B, hin, win, ipad, cx, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad,
-                           gpad, s)
-                dW = G.permute(0, 3, 1, 2).to(conv.weight.dtype).contiguous()
+                dW = wgrad(cb, xf, ipad, cx, cin, hin, win, dz, gpad).permute(0, 3, 1, 2).to(conv.weight.dtype).contiguous()
             if w_w or w_g or w_b:
                 grads[name] = (dW, sums[cb.cout:].to(bn.weight.dtype) if w_g else None, sums[:cb.cout].to(bn.bias.dtype) if w_b else None)
 
@@ -1144,11 +1205,7 @@ class ResNet(DeviceStateModule):
             inv_std = torch.rsqrt(bn.running_var.detach().to(d) + bn.eps)
             dW = dscale = None
             if w_w or w_g:
-                G = torch.empty(cb.cout, cb.kh, cb.kw, cin, device=dev, dtype=torch.float32)
-                ws = scratch(int(lib.hps_conv_wgrad_workspace(B, hin, win, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad)), torch.float32)
-                _capi.call("hps_conv_wgrad", P(xf), P(g), P(G), P(ws), B, hin, win, ipad, cx, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad,
-                           gpad, s)
-                Gd = G.permute(0, 3, 1, 2).to(d)                                        # (Cout, Cin, KH, KW), the weight's layout
+                Gd = wgrad(cb, xf, ipad, cx, cin, hin, win, g, gpad).permute(0, 3, 1, 2).to(d)      # (Cout, Cin, KH, KW), the weight's layout
                 if w_w:
                     dW = (Gd * cb.scale.to(d)[:, None, None, None]).to(conv.weight.dtype).contiguous()
                 if w_g:
@@ -1159,69 +1216,93 @@ class ResNet(DeviceStateModule):
 
         def dgrad(name, cb, g, gpad, other, dx, dpad, cdx, cin, hin, win):
             conv, _ = mods[name]
-            _capi.call("hps_conv_dgrad", P(g), P(self._dgrad_filter(prep, name, conv, cb, trains(name))), P(other), P(dx), B, hin, win, cin, cb.cout,
-                       cb.kh, cb.kw, cb.stride, cb.pad, gpad, dpad, cdx, s)
+            wt = self._dgrad_filter(prep, name, conv, cb, trains(name))
+            if self._gemm_dgrad(cb):               # the same bits (hps_conv1x1_dgrad keeps hps_conv_dgrad's summation order)
+                _capi.call("hps_conv1x1_dgrad", P(g), P(wt), P(other), P(dx), B, hin, win, cin, cb.cout, cb.stride, gpad, dpad, cdx, s)
+            else:
+                _capi.call("hps_conv_dgrad", P(g), P(wt), P(other), P(dx), B, hin, win, cin, cb.cout, cb.kh, cb.kw, cb.stride, cb.pad, gpad, dpad,
+                           cdx, s)
 
         # which blocks still have somebody below them asking for a gradient
         names = self._block_names()
+        conv_names = lambda name, blk: [name + ".c%d" % i for i in range(1, len(blk.convs) + 1)]
         below = [needs[0] or any(want["stem"])]
-        for name, (c1, c2, down) in zip(names, prep["blocks"]):
-            here = any(want[name + ".c1"]) or any(want[name + ".c2"]) or (down is not None and any(want[name + ".down"]))
+        for name, blk in zip(names, prep["blocks"]):
+            here = any(any(want[n]) for n in conv_names(name, blk)) or (blk.down is not None and any(want[name + ".down"]))
             below.append(below[-1] or here)
         h, w = fs["hw"]
-        last = fs["blocks"][-1]["c2"]
-        _capi.call("hps_global_avgpool_backward", P(_capi.f32c(g_feats)), P(gf["blocks"][-1]["c2"]), B, h, w, last.shape[3], 1, s)
+        last = fs["blocks"][-1]["out"]
+        _capi.call("hps_global_avgpool_backward", P(_capi.f32c(g_feats)), P(gf["blocks"][-1]["out"]), B, h, w, last.shape[3], 1, s)
+        # Per block (BasicBlock.forward models/resnet.py:62-78, Bottleneck.forward :102-122), last convolution first: the block's ReLU gate
+        # on the last convolution's output frame, then per convolution its parameter gradients, the data gradient into the previous
+        # convolution's cotangent frame and that frame's gate; the first one's data gradient takes the identity branch as ``other``.
         for k in range(len(names) - 1, -1, -1):
-            name, (c1, c2, down), ent, ge = names[k], prep["blocks"][k], fs["blocks"][k], gf["blocks"][k]
-            y_in = fs["blocks"][k - 1]["c2"] if k else fs["pool"]
-            g_in = gf["blocks"][k - 1]["c2"] if k else gf["pool"]
+            name, blk, ent, ge = names[k], prep["blocks"][k], fs["blocks"][k], gf["blocks"][k]
+            convs, down, n = blk.convs, blk.down, len(blk.convs)
+            cn, nd = conv_names(name, blk), name + ".down"
+            y_in = fs["blocks"][k - 1]["out"] if k else fs["pool"]
+            g_in = gf["blocks"][k - 1]["out"] if k else gf["pool"]
             hin, win, cin = y_in.shape[1] - 2, y_in.shape[2] - 2, y_in.shape[3]
-            ho, wo = ent["c2"].shape[1] - 2, ent["c2"].shape[2] - 2
-            t1, t2, td = trains(name + ".c1"), trains(name + ".c2"), down is not None and trains(name + ".down")
-            more = below[k] or any(want[name + ".c1"])                                           # somebody below c2 wants something
-            sums_d = want[name + ".c2"][1] or want[name + ".c2"][2] or (down is not None and (want[name + ".down"][1] or want[name + ".down"][2]))
-            g2 = gd = ge["c2"]
-            if t2 and (td or down is None):        # g2: the block's ReLU, both branches -- in the sweep of c2's sums
-                s2 = train_sums(name + ".c2", c2, ge["c2"], 1, ent["c2"], 1, ho, wo)
-                sums2 = None
+            out, g_out = ent["out"], ge["out"]
+            ho, wo = out.shape[1] - 2, out.shape[2] - 2
+            cl, nl = convs[-1], cn[-1]
+            xl = ent["c%d" % (n - 1)]                                                            # the last convolution's input frame
+            hl, wl = xl.shape[1] - 2, xl.shape[2] - 2
+            tl, td = trains(nl), down is not None and trains(nd)
+            asks = [below[k]]                      # asks[i]: somebody below convolution i + 1 wants something
+            for i in range(1, n):
+                asks.append(asks[-1] or any(want[cn[i - 1]]))
+            more = asks[n - 1]
+            sums_d = want[nl][1] or want[nl][2] or (down is not None and (want[nd][1] or want[nd][2]))
+            gl = gd = g_out
+            if tl and (td or down is None):        # the block's ReLU, both branches -- in the sweep of the last convolution's sums
+                sl = train_sums(nl, cl, g_out, 1, out, 1, ho, wo)
+                sums_l = None
             else:
-                sums2 = gate(ge["c2"], ent["c2"], B, ho, wo, c2.cout, 1, 1, sums_d)
-                s2 = train_sums(name + ".c2", c2, ge["c2"], 1, None, 1, ho, wo) if t2 else None
-            if t2:
-                if more or want[name + ".c2"][0]:
-                    g2 = train_dz(name + ".c2", c2, ge["c2"], 1, s2, ge["dz"], ho, wo)
-                train_params(name + ".c2", c2, ent["c1"], 1, c2.cin_p, c2.cin_p, ho, wo, g2, 1, s2)
+                sums_l = gate(g_out, out, B, ho, wo, cl.cout, 1, 1, sums_d)
+                sl = train_sums(nl, cl, g_out, 1, None, 1, ho, wo) if tl else None
+            if tl:
+                if more or want[nl][0]:
+                    gl = train_dz(nl, cl, g_out, 1, sl, ge["dz_c%d" % n], ho, wo)
+                train_params(nl, cl, xl, 1, cl.cin_p, cl.cin_p, hl, wl, gl, 1, sl)
             else:
-                params(name + ".c2", c2, ent["c1"], 1, c2.cin_p, c2.cin_p, ho, wo, ge["c2"], 1, sums2)
+                params(nl, cl, xl, 1, cl.cin_p, cl.cin_p, hl, wl, g_out, 1, sums_l)
             if td:
-                if below[k] or any(want[name + ".down"]):
-                    sd = train_sums(name + ".down", down, ge["c2"], 1, None, 1, ho, wo)
-                    if below[k] or want[name + ".down"][0]:
-                        gd = train_dz(name + ".down", down, ge["c2"], 1, sd, ge["dzd"], ho, wo)
-                    train_params(name + ".down", down, y_in, 1, cin, cin, hin, win, gd, 1, sd)
+                if below[k] or any(want[nd]):
+                    sd = train_sums(nd, down, g_out, 1, None, 1, ho, wo)
+                    if below[k] or want[nd][0]:
+                        gd = train_dz(nd, down, g_out, 1, sd, ge["dzd"], ho, wo)
+                    train_params(nd, down, y_in, 1, cin, cin, hin, win, gd, 1, sd)
             elif down is not None:
-                params(name + ".down", down, y_in, 1, cin, cin, hin, win, ge["c2"], 1, sums2)
-            if not more:
-                break                                                                            # nobody below wants anything
-            dgrad(name + ".c2", c2, g2, 1, None, ge["c1"], 1, c2.cin_p, c2.cin_p, ho, wo)
-            g1 = ge["c1"]
-            if t1:
-                s1 = train_sums(name + ".c1", c1, ge["c1"], 1, ent["c1"], 1, ho, wo)
-                if below[k] or want[name + ".c1"][0]:
-                    g1 = train_dz(name + ".c1", c1, ge["c1"], 1, s1, ge["dz"], ho, wo)           # dz2 has been consumed (stream order)
-                train_params(name + ".c1", c1, y_in, 1, cin, cin, hin, win, g1, 1, s1)
-            else:
-                sums1 = gate(ge["c1"], ent["c1"], B, ho, wo, c1.cout, 1, 1, want[name + ".c1"][1] or want[name + ".c1"][2])
-                params(name + ".c1", c1, y_in, 1, cin, cin, hin, win, ge["c1"], 1, sums1)
-            if not below[k]:
+                params(nd, down, y_in, 1, cin, cin, hin, win, g_out, 1, sums_l)
+            stop, gprev = not more, gl                                                           # nobody below wants anything
+            for i in range(n - 1, 0, -1):          # convolution i: its cotangent frame <- the data gradient of convolution i + 1
+                if stop:
+                    break
+                ci, ni, ei, gi = convs[i - 1], cn[i - 1], ent["c%d" % i], ge["c%d" % i]
+                hi, wi = ei.shape[1] - 2, ei.shape[2] - 2
+                dgrad(cn[i], convs[i], gprev, 1, None, gi, 1, convs[i].cin_p, convs[i].cin_p, hi, wi)
+                xi = y_in if i == 1 else ent["c%d" % (i - 1)]
+                hx, wx, cx = xi.shape[1] - 2, xi.shape[2] - 2, xi.shape[3]
+                gprev = gi
+                if trains(ni):
+                    si = train_sums(ni, ci, gi, 1, ei, 1, hi, wi)
+                    if asks[i - 1] or want[ni][0]:
+                        gprev = train_dz(ni, ci, gi, 1, si, ge["dz_c%d" % i], hi, wi)            # the later dz has been consumed (stream order)
+                    train_params(ni, ci, xi, 1, cx, cx, hx, wx, gprev, 1, si)
+                else:
+                    sums_i = gate(gi, ei, B, hi, wi, ci.cout, 1, 1, want[ni][1] or want[ni][2])
+                    params(ni, ci, xi, 1, cx, cx, hx, wx, gi, 1, sums_i)
+                stop = not asks[i - 1]
+            if stop:
                 break
             # the identity / down-sample branch's gradient first, the main branch's data gradient adds it in its epilogue (fixed order)
             if down is not None:
-                dgrad(name + ".down", down, gd, 1, None, ge["tmp"], 1, cin, cin, hin, win)
+                dgrad(nd, down, gd, 1, None, ge["tmp"], 1, cin, cin, hin, win)
                 other = ge["tmp"]
             else:
-                other = ge["c2"]
-            dgrad(name + ".c1", c1, g1, 1, other, g_in, 1, cin, cin, hin, win)
+                other = g_out
+            dgrad(cn[0], convs[0], gprev, 1, other, g_in, 1, cin, cin, hin, win)
         else:
             stem = prep["stem"]
             hs, wst = fs["stem"].shape[1], fs["stem"].shape[2]
@@ -1258,7 +1339,8 @@ def resnet18(in_channels, pretrained=False, progress=True, **kwargs):
 
 
 def resnet50(in_channels, pretrained=False, progress=True, **kwargs):
-    """models/resnet.py:251-259 (Bottleneck, [3, 4, 6, 3], 2048 features); forward only (see ResNet)."""
+    """models/resnet.py:251-259 (Bottleneck, [3, 4, 6, 3], 2048 features); forward only until set_differentiable(True) opts in to the
+    backward, training-mode BatchNorm and the in-place refresh (see ResNet)."""
     if pretrained:
         raise NotImplementedError("no network access: pretrained weights are not available")
     return ResNet([3, 4, 6, 3], in_channels, block=Bottleneck)

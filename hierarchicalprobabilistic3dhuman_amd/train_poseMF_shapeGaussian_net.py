@@ -185,7 +185,7 @@ def train_poseMF_shapeGaussian_net(pose_shape_model,
     cfg = pose_shape_cfg
     if getattr(pose_shape_model.image_encoder, "_forward_only", False):          # before a file, a loader or a buffer is touched
         raise NotImplementedError("training a net with the Bottleneck (ResNet-50) encoder is not implemented: its encoder runs forward "
-                                  "only (MODEL.NUM_RESNET_LAYERS = 18 trains)")
+                                  "only (MODEL.NUM_RESNET_LAYERS = 18 trains; so does 50 after set_differentiable_encoder(True))")
     def loader(dataset):
         # a dataset with prepare_batch (on_the_fly_smpl_train_dataset.py) hands over raw items: its batch is formed on the device
         raw = data_layer.preparer(dataset) is not None

@@ -781,6 +781,31 @@ size_t hps_conv_wgrad_workspace(int B, int H, int W, int Cin, int Cout, int KH, 
 int hps_conv_dgrad(const float* g, const float* wt, const float* other, float* dx, int B, int H, int W, int Cin, int Cout, int KH,
                    int KW, int stride, int pad, int gpad, int dpad, int Cdx, hps_stream_t stream);
 
+/* The two gradients of a 1x1 / pad 0 convolution as LDS-tiled GEMMs over NHWC rows (csrc/conv1x1_backward.hip): the pointwise
+ * layers of Bottleneck.forward (models/resnet.py:105 conv1, :113 conv3, built at :92 and :96) and the down-sample of _make_layer
+ * (:184-188, applied at :116-117), differentiated under torch autograd.  Four waves per workgroup on a 128 x 128 (128 x 64) tile, both
+ * operands staged through LDS 32 K at a time.  Cout % 8 == 0, stride 1 or 2; frames of 2^31 pixels or more are refused.
+ *
+ * hps_conv1x1_dgrad: the contract of hps_conv_dgrad at KH = KW = 1, pad = 0 -- wt is (Cout, Cin); every interior pixel of dx is
+ * written, off the stride lattice with ``other`` or 0; halos and channels Cin .. Cdx-1 are never touched -- and ITS BITS: the same K
+ * order (MFMA j of a step of 8 channels contracts co0 + j and co0 + 4 + j), the chain cut every 64 channels, pieces added in order in
+ * fp32.  A pixel's sum depends on the layer alone, never on B or on the tile it falls in. */
+int hps_conv1x1_dgrad(const float* g, const float* wt, const float* other, float* dx, int B, int H, int W, int Cin, int Cout, int stride,
+                      int gpad, int dpad, int Cdx, hps_stream_t stream);
+
+/* hps_conv1x1_wgrad: G (Cout, Cin) = sum over b, oy, ox of g[b, oy, ox, co] * x[b, oy stride, ox stride, ci]; x, g, Cx, ipad, gpad as
+ * in hps_conv_wgrad (ipad >= 0).  The B Ho Wo pixels are cut into slices of hps_conv1x1_wgrad_slice_pixels(Cin, Cout) pixels -- a rule
+ * on the layer alone: twice the harmonic mean of Cin and Cout, rounded up to a multiple of 64, at least 1024.  Inside a slice chain
+ * pieces of 64 pixels are added in order in fp32; the slices' partials go to ``workspace`` (hps_conv1x1_wgrad_workspace bytes) and are
+ * added in slice order in float64, rounded once.  No atomics.  Other bits than hps_conv_wgrad (another slice length).
+ * Workspace bound: with P = B Ho Wo >= one slice, ceil(P / S) Cin Cout <= P (Cin + Cout) / 2 + Cin Cout floats, the two operands hold
+ * P (Cin + Cout) or more.  Every 1x1 layer of ResNet-50 at B = 72 on 256 x 256 inputs stays below 0.42 of its operand frames
+ * (layer4's conv1 / conv3: 5 slices of 4 MB against 47 MB; hps_conv_wgrad_workspace: 36 slices). */
+int hps_conv1x1_wgrad(const float* x, const float* g, float* G, float* workspace, int B, int H, int W, int ipad, int Cx, int Cin,
+                      int Cout, int stride, int gpad, hps_stream_t stream);
+int hps_conv1x1_wgrad_slice_pixels(int Cin, int Cout);
+size_t hps_conv1x1_wgrad_workspace(int B, int H, int W, int Cin, int Cout, int stride);
+
 /* ReLU gate in place: interior of g (B, H + 2 gpad, W + 2 gpad, C) <- g where y > 0 (strict, as torch), else 0; y (B, H + 2 ypad,
  * W + 2 ypad, C) is the layer's output.  sums (C,), optional together with workspace (hps_relu_gate_workspace bytes, float64): the
  * per-channel sums of the gated cotangent (d shift) -- float64 per 64 pixels, then float64 over the chunks in order, rounded once. */
@@ -802,7 +827,8 @@ int hps_global_avgpool_backward(const float* gfeat, float* gframe, int B, int H,
  * with the batch's per-channel mean and biased variance over the n = B H W pixels, and running <- (1 - momentum) running +
  * momentum batch with the unbiased variance var n / (n - 1).  A training layer's convolution runs with identity scale / shift, no
  * residual and no ReLU into a raw frame z; the kernels below work on such (B, H + 2 pad, W + 2 pad, C) NHWC frames (interior only;
- * halos are neither read nor written).  C = 4, 8, 16, ..., 1024 (a multiple of 4 with 256 % (C / 4) == 0), B H W < 2^31.
+ * halos are neither read nor written).  C = 4, 8, 16, ..., 1024 (a multiple of 4 with 256 % (C / 4) == 0) or a multiple of 1024 up
+ * to 65536 (models/resnet.py:97, :186: the Bottleneck encoder's 2048; windows of 1024 channels), B H W < 2^31.
  * No atomics, fixed summation orders: every result is bitwise repeatable.
  * ---------------------------------------------------------------------------------------- */
 
