@@ -138,6 +138,10 @@ _PROTOTYPES = {
     "hps_vis_compose": [_P, _P],
     "hps_sizeof_vis_uncrop_args": [],
     "hps_vis_uncrop": [_P, _P],
+    "hps_sizeof_png_encode_args": [],
+    "hps_png_bound": [_I, _I, _I],
+    "hps_png_segment_rows": [_I, _I, _I],
+    "hps_png_encode": [_P, _P],
     "hps_sizeof_c16_problem": [],
     "hps_conv2d_bn_act_c16": [_P, _I, _P],
     "hps_hrnet_pack_input": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -165,7 +169,8 @@ _PROTOTYPES = {
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
              "hps_conv_wgrad_workspace": _c.c_size_t, "hps_conv1x1_wgrad_workspace": _c.c_size_t, "hps_relu_gate_workspace": _c.c_size_t,
-             "hps_bn_batch_stats_workspace": _c.c_size_t, "hps_bn_train_backward_sums_workspace": _c.c_size_t}
+             "hps_bn_batch_stats_workspace": _c.c_size_t, "hps_bn_train_backward_sums_workspace": _c.c_size_t,
+             "hps_png_bound": _c.c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
@@ -257,6 +262,20 @@ class VisUncropArgs(_c.Structure):
     """include/hps.h: hps_vis_uncrop_args (struct_bytes = ctypes.sizeof(VisUncropArgs); the library rejects any other value)."""
     _fields_ = [(n, _I) for n in ("struct_bytes", "H", "W", "wh")] + [
         (n, _P) for n in ("rgb", "iplane", "image", "bbox_centre", "bbox_wh", "out")]
+
+
+PNG_MAX_IMAGES = 8
+
+
+class PngImage(_c.Structure):
+    """include/hps.h: hps_png_image."""
+    _fields_ = [("pixels", _P), ("H", _I), ("W", _I), ("C", _I), ("reserved", _I), ("out", _P), ("capacity", _c.c_int64), ("length", _P),
+                ("workspace", _P)]
+
+
+class PngEncodeArgs(_c.Structure):
+    """include/hps.h: hps_png_encode_args (struct_bytes = ctypes.sizeof(PngEncodeArgs); the library rejects any other value)."""
+    _fields_ = [("struct_bytes", _I), ("num_images", _I), ("image", PngImage * PNG_MAX_IMAGES)]
 
 
 class C16Problem(_c.Structure):
@@ -557,6 +576,7 @@ WS_SEG_BBOX = 13
 WS_RENDER = 14
 WS_SILHOUETTE = 15
 WS_TRAIN_METRICS = 16
+WS_PNG = 17
 
 
 def silhouette_d2(num_faces, W):

@@ -44,6 +44,11 @@ extern "C" int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t
             return hps::silhouette_ws_bytes(d0, d1, faces, W);
         }
         case HPS_WS_TRAIN_METRICS: return hps::train_metrics_ws_bytes(d0);
+        case HPS_WS_PNG: {
+            const int64_t n = hps::png_ws_bytes(d0, d1, d2);
+            if (n < 0) hps::set_error("hps_query_workspace: HPS_WS_PNG takes d0 = H in [1, 32768], d1 = W, d2 = C in {1, 3} with W C <= 12288");
+            return n;
+        }
         default: hps::set_error("hps_query_workspace: unknown item %d", what); return -1;
     }
 }

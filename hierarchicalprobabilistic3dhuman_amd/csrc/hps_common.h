@@ -30,6 +30,8 @@ int64_t render_ws_bytes(int64_t B, int64_t Nd, int64_t F);
 int64_t silhouette_ws_bytes(int64_t M, int64_t Nd, int64_t F, int64_t W);
 // bytes of the hps_train_metrics_update workspace (csrc/metrics.hip; HPS_WS_TRAIN_METRICS)
 int64_t train_metrics_ws_bytes(int64_t B);
+// bytes of one picture's hps_png_encode workspace, -1 outside the supported range (csrc/png.hip; HPS_WS_PNG)
+int64_t png_ws_bytes(int64_t H, int64_t W, int64_t C);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -648,7 +648,7 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                                      edge_detect_model, device, image_dir, save_dir, object_detect_model=None,
                                      joints2Dvisib_threshold=0.75, visualise_wh=512, visualise_uncropped=True,
                                      visualise_samples=False, proxy_rep_fn=None, num_samples=50, batch_size=1,
-                                     result_fn=None, vis_renderer=None, batched_front_end=None):
+                                     result_fn=None, vis_renderer=None, batched_front_end=None, png_encoder="pil"):
     """Signature of predict/predict_poseMF_shapeGaussian_net.py:19-32 plus keyword extensions.
 
     Called exactly like the reference (run_predict.py:77-89) it runs the reference's front end (:61-100) on the injected
@@ -668,6 +668,9 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     A custom ``proxy_rep_fn`` may return a dict with ``proxy_rep`` and, for the pictures, ``cropped_rgb`` (1,3,D,D), ``joints2D``
     (1,K,2) in crop pixels, ``image`` (3,H,W) float in [0,1], ``bbox_centre`` (2,) and ``bbox_wh`` (max(h, w) BBOX_SCALE_FACTOR),
     all on the device; a bare tensor gives black crop panels, no joint discs and no uncropped picture (one warning).
+    ``png_encoder``: "pil" (the default) encodes the pictures with PIL on visualise.PngWriter's host threads; "device" makes the PNG
+    files on the device (visualise.DevicePngWriter, hps_png_encode: an image's pictures in one library call, only the compressed bytes
+    cross to the host).  The decoded pixels are the same; the files are not (another compressor).  Anything else is a ValueError.
 
     ``batched_front_end``: None runs the front end of a whole group of ``batch_size`` images on the device with ONE HRNet forward
     (predict_frontend.DevicePredictFrontEnd: box, crops and key points are libhps kernels, no host synchronisation of its own) when it
@@ -675,6 +678,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     ``edge_map_into`` -- and the per-image route of predict_hrnet / image_utils otherwise; True demands it (HpsError when it cannot be
     used), False forbids it.
     """
+    if png_encoder not in ("pil", "device"):
+        raise ValueError("png_encoder is 'pil' or 'device', not %r" % (png_encoder,))
     device = torch.device(device)
     batched = None
     if use_batched_front_end(batched_front_end, proxy_rep_fn, device, hrnet_model, edge_detect_model):
@@ -694,8 +699,9 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     vis = writer = None
     extras = {}                                          # image name -> what the front end kept for the pictures
     if vis_renderer is not None:
-        from .visualise import PngWriter, predict_visualiser
-        vis, writer = predict_visualiser(vis_renderer, pose_shape_cfg, visualise_wh), PngWriter()
+        from .visualise import DevicePngWriter, PngWriter, predict_visualiser
+        vis = predict_visualiser(vis_renderer, pose_shape_cfg, visualise_wh)
+        writer = DevicePngWriter() if png_encoder == "device" else PngWriter()
     warned = []
 
     def get_proxy(name):
@@ -727,16 +733,20 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         if not proxy.is_cuda:
             proxy = proxy.to(device, non_blocking=True)
         crop, joints = ex.get("cropped_rgb"), ex.get("joints2D")
-        writer.write(vis.figure(item, crop, proxy.float(), joints), stem + ".png")
+        pictures = []                                    # the device encoder takes an image's pictures in one call
+        write = (lambda image, path: pictures.append((image, path))) if png_encoder == "device" else writer.write
+        write(vis.figure(item, crop, proxy.float(), joints), stem + ".png")
         if visualise_uncropped:
             if all(ex.get(k) is not None for k in ("image", "bbox_centre", "bbox_wh")):
-                writer.write(vis.uncropped(ex["image"], ex["bbox_centre"], ex["bbox_wh"]), stem + "_uncrop.png")
+                write(vis.uncropped(ex["image"], ex["bbox_centre"], ex["bbox_wh"]), stem + "_uncrop.png")
             elif not warned:
                 import warnings
                 warned.append(True)
                 warnings.warn("predict: proxy_rep_fn gave no image / bbox_centre / bbox_wh; the uncropped pictures are skipped")
         if visualise_samples:
-            writer.write(vis.samples_figure(item, crop, proxy.float()), stem + "_samples.png")
+            write(vis.samples_figure(item, crop, proxy.float()), stem + "_samples.png")
+        if pictures:
+            writer.write_many([image for image, _ in pictures], [path for _, path in pictures])
     # The loop is software-pipelined (InferencePipeline): while batch k's head, sampling and meshes run, batch k+1's proxy
     # representations are already staged (page-locked host tensors go up by non-blocking copies on a copy stream, StagedUpload)
     # and its encoder is enqueued.  Same results as infer() per batch.

@@ -4,7 +4,8 @@ the body projected back onto the original photograph, and the sheet of the eight
 ``PredictVisualiser`` holds the reference's fixed light and camera (:47-52) and builds every picture from three kernels of
 csrc/visualise.hip around ONE hps_render call over all of the picture's views (include/hps.h: hps_vis_views, hps_vis_compose,
 hps_vis_uncrop).  The kernels write finished uint8 RGB images, so only bytes cross to the host; ``PngWriter`` copies them into
-page-locked buffers without blocking and encodes them with PIL on a small thread pool.
+page-locked buffers without blocking and encodes them with PIL on a small thread pool.  ``DevicePngWriter`` is the opt-in beside it:
+the PNG file itself is made on the device (hps_png_encode) and only the compressed bytes cross.
 
 Differences from the reference, all deliberate:
   * the joint numbers and confidences it prints into the proxy-representation panel with cv2.putText (:256-263) are NOT drawn: the
@@ -264,6 +265,133 @@ class PngWriter:
             os.replace(tmp, path)
         finally:
             self._free.setdefault(host.numel(), []).append(host)
+
+    def drain(self):
+        pending, self._pending = self._pending, []
+        error = None
+        for f in pending:
+            try:
+                f.result()
+            except Exception as e:      # every file is waited for before the first error goes up
+                error = error or e
+        if error is not None:
+            raise error
+
+    def close(self):
+        self.drain()
+        self._pool.shutdown(wait=True)
+
+
+class _PngSlot:
+    """What one picture of DevicePngWriter holds while it is in flight: the file's device buffer (hps_png_bound bytes), the library's
+    workspace, the device length, and page-locked mirrors of file and length.  Reused by picture shape."""
+
+    def __init__(self, key, device):
+        H, W, C = key
+        self.key, self.bound = key, png_bound(H, W, C)
+        self.out = torch.empty(self.bound, dtype=torch.uint8, device=device)
+        self.workspace = torch.empty(max(16, _capi.query_workspace(_capi.WS_PNG, H, W, C)), dtype=torch.uint8, device=device)
+        self.length = torch.zeros(1, dtype=torch.int64, device=device)
+        self.host = torch.empty(self.bound, dtype=torch.uint8).pin_memory()
+        self.host_length = torch.zeros(1, dtype=torch.int64).pin_memory()
+
+
+def png_bound(H, W, C):
+    """include/hps.h: hps_png_bound -- a capacity no file of an (H, W, C) picture exceeds."""
+    n = _capi.load(dev=_capi._use_dev).hps_png_bound(int(H), int(W), int(C))
+    if n < 0:
+        raise _capi.HpsError("hps_png_bound(%d, %d, %d): %s" % (H, W, C, _capi.load(dev=_capi._use_dev).hps_last_error().decode()))
+    return int(n)
+
+
+def png_segment_rows(H, W, C):
+    """include/hps.h: hps_png_segment_rows -- the rows of one independently compressed segment."""
+    n = _capi.load(dev=_capi._use_dev).hps_png_segment_rows(int(H), int(W), int(C))
+    if n < 0:
+        raise _capi.HpsError("hps_png_segment_rows(%d, %d, %d): %s" % (H, W, C, _capi.load(dev=_capi._use_dev).hps_last_error().decode()))
+    return int(n)
+
+
+class DevicePngWriter:
+    """PngWriter's interface with the encoder on the device (include/hps.h: hps_png_encode): ``write`` / ``write_many`` launch the
+    library's two kernels on the current stream into reused device buffers and never block the caller; a worker thread waits for the
+    file's length, copies exactly that many bytes through a reused page-locked buffer on a copy stream of its own, writes
+    ``path + ".part"`` and renames it.  No host thread compresses anything.  ``write_many`` puts up to _capi.PNG_MAX_IMAGES pictures
+    -- one predicted image's three -- into one library call.  At most 2 x workers pictures are in flight; ``drain`` waits for every
+    file and re-raises the first error.  Pictures are (H, W), (H, W, 1) or (H, W, 3) uint8 device tensors."""
+
+    def __init__(self, workers=4):
+        self.workers = max(1, min(4, int(workers)))
+        self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers)
+        self._free = {}
+        self._pending = []
+        self._copy_streams = {}
+
+    def _slot(self, key, device):
+        free = self._free.setdefault((key, device), [])
+        return free.pop() if free else _PngSlot(key, device)
+
+    def write(self, image, path):
+        self.write_many([image], [path])
+
+    def write_many(self, images, paths):
+        if len(images) != len(paths) or not 1 <= len(images) <= _capi.PNG_MAX_IMAGES:
+            raise _capi.HpsError("write_many takes 1 .. %d pictures and as many paths" % _capi.PNG_MAX_IMAGES)
+        while len(self._pending) + len(images) > 2 * self.workers and self._pending:
+            self._pending.pop(0).result()
+        a = _capi.PngEncodeArgs()
+        a.struct_bytes, a.num_images = ctypes.sizeof(_capi.PngEncodeArgs), len(images)
+        slots, keep = [], []
+        for i, image in enumerate(images):
+            _capi.require_device(image, "image")
+            if image.dtype != torch.uint8 or image.dim() not in (2, 3) or (image.dim() == 3 and image.shape[2] not in (1, 3)):
+                raise _capi.HpsError("a picture is (H, W), (H, W, 1) or (H, W, 3) uint8")
+            image = image.contiguous()
+            if image.data_ptr() % 16:
+                image = image.clone()
+            keep.append(image)
+            key = (int(image.shape[0]), int(image.shape[1]), int(image.shape[2]) if image.dim() == 3 else 1)
+            slot = self._slot(key, image.device)
+            slots.append(slot)
+            im = a.image[i]
+            im.pixels, (im.H, im.W, im.C) = _capi.ptr(image, torch.uint8, "image"), key
+            im.out, im.capacity = _capi.ptr(slot.out, torch.uint8), slot.bound
+            im.length, im.workspace = _capi.ptr(slot.length, torch.int64), _capi.ptr(slot.workspace, torch.uint8)
+        try:
+            _capi.call("hps_png_encode", ctypes.addressof(a), _capi.stream())
+        except Exception:
+            for slot in slots:
+                self._free[(slot.key, slot.out.device)].append(slot)
+            raise
+        for slot in slots:
+            slot.host_length.copy_(slot.length, non_blocking=True)
+        encoded = torch.cuda.Event()
+        encoded.record()
+        for slot, path in zip(slots, paths):
+            self._pending.append(self._pool.submit(self._deliver, slot, encoded, path))
+
+    def _deliver(self, slot, encoded, path):
+        try:
+            encoded.synchronize()
+            n = int(slot.host_length[0])
+            if not 0 < n <= slot.bound:
+                raise _capi.HpsError("hps_png_encode reported a file of %d bytes, the bound is %d" % (n, slot.bound))
+            device = slot.out.device
+            with torch.cuda.device(device):
+                stream = self._copy_streams.get(device)
+                if stream is None:
+                    stream = self._copy_streams.setdefault(device, torch.cuda.Stream(device=device))
+                with torch.cuda.stream(stream):
+                    slot.host[:n].copy_(slot.out[:n], non_blocking=True)
+                    copied = torch.cuda.Event()
+                    copied.record()
+                copied.synchronize()
+            tmp = path + ".part"
+            with open(tmp, "wb") as f:
+                f.write(memoryview(slot.host.numpy())[:n])
+            os.replace(tmp, path)
+        finally:
+            self._free[(slot.key, slot.out.device)].append(slot)
 
     def drain(self):
         pending, self._pending = self._pending, []

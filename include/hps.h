@@ -108,11 +108,12 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_RENDER      (d0 = B, d1 = DensePose vertices, d2 = faces)  workspace of hps_render
  *   HPS_WS_SILHOUETTE  (d0 = M, d1 = DensePose vertices, d2 = HPS_WS_SILHOUETTE_D2(faces, W))  workspace of hps_silhouette_iou
  *   HPS_WS_TRAIN_METRICS (d0 = B)                               workspace of hps_train_metrics_update
+ *   HPS_WS_PNG         (d0 = H, d1 = W, d2 = C)                 a picture's workspace of hps_png_encode (-1 outside the supported range)
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
        HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
        HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13, HPS_WS_RENDER = 14,
-       HPS_WS_SILHOUETTE = 15, HPS_WS_TRAIN_METRICS = 16 };
+       HPS_WS_SILHOUETTE = 15, HPS_WS_TRAIN_METRICS = 16, HPS_WS_PNG = 17 };
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -1396,6 +1397,46 @@ typedef struct hps_vis_uncrop_args {
 } hps_vis_uncrop_args;
 int hps_sizeof_vis_uncrop_args(void);
 int hps_vis_uncrop(const hps_vis_uncrop_args* args, hps_stream_t stream);
+
+/* hps_png_encode  (no reference counterpart: the reference hands its pictures to cv2.imwrite; csrc/png.hip)  finished uint8 pictures
+ * to the bytes of complete PNG files, so that only the compressed file crosses to the host.  Up to HPS_PNG_MAX_IMAGES pictures per
+ * call share TWO launches; no atomics on global memory, nothing allocated, no host synchronisation, bitwise repeatable, and the bytes
+ * of a picture do not depend on what else is in the call.  Picture i: pixels (H, W, C) contiguous uint8, C = 1 (greyscale) or 3 (RGB);
+ * out receives the file -- signature, IHDR (8 bit, colour type 0 or 2, no interlace), IDAT chunks, IEND, every chunk CRC and the zlib
+ * Adler-32 formed on the device -- and *length (device int64) its length in bytes; capacity, the bytes behind out, must be at least
+ * hps_png_bound(H, W, C); workspace is hps_query_workspace(HPS_WS_PNG, H, W, C) bytes.  pixels, out and workspace are 16-byte
+ * aligned, length 8-byte aligned; the buffers of different pictures do not overlap.
+ *
+ * The stream inside: the picture is cut into segments of hps_png_segment_rows(H, W, C) whole rows (the last may be shorter), each
+ * compressed on its own and carried by its own IDAT chunk; a first IDAT chunk holds the zlib header 78 01, a last one the final empty
+ * block 03 00 and the Adler-32.  A row takes filter Sub where the sum of its |Sub| residuals (as signed bytes) is smaller than that of
+ * its |Up| residuals, else Up (the first row's Up is the row itself).  In a segment's filtered bytes, maximal runs of bytes equal to
+ * their predecessor become matches of distance 1, cut into pieces of 258 from the run's start (a last piece shorter than 3 stays
+ * literals); nothing reaches before the segment.  Tokens are coded with deflate's fixed Huffman tables and the segment closes with an
+ * empty stored block, which ends it on a byte boundary; where one stored block is shorter, the segment is that stored block.
+ *
+ * Supported: C in {1, 3}, W C in [1, 12288] (4096 RGB pixels), H in [1, 32768]; anything else is HPS_E_BADARG, as are null pointers,
+ * a wrong struct_bytes, num_images outside [1, HPS_PNG_MAX_IMAGES] and a capacity below the bound -- all before any launch.
+ * hps_png_bound and hps_png_segment_rows are host functions; both return -1 (and set hps_last_error) outside the supported range.
+ * hps_png_bound(H, W, C) = 77 + H (1 + W C) + 17 ceil(H / rows per segment): no file is longer (derivation: csrc/png.hip). */
+#define HPS_PNG_MAX_IMAGES 8
+typedef struct hps_png_image {
+    const uint8_t* pixels;                                     /* (H, W, C) */
+    int H, W, C, reserved;
+    uint8_t* out;                                              /* (capacity) */
+    int64_t capacity;
+    int64_t* length;                                           /* (1) */
+    void* workspace;
+} hps_png_image;
+typedef struct hps_png_encode_args {
+    int struct_bytes;
+    int num_images;
+    hps_png_image image[HPS_PNG_MAX_IMAGES];
+} hps_png_encode_args;
+int hps_sizeof_png_encode_args(void);
+int64_t hps_png_bound(int H, int W, int C);
+int hps_png_segment_rows(int H, int W, int C);
+int hps_png_encode(const hps_png_encode_args* args, hps_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * HRNet 2D keypoint detector, inference forward  (models/pose2D_hrnet.py:426-461)
