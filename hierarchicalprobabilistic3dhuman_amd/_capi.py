@@ -269,7 +269,7 @@ PNG_MAX_IMAGES = 8
 
 class PngImage(_c.Structure):
     """include/hps.h: hps_png_image."""
-    _fields_ = [("pixels", _P), ("H", _I), ("W", _I), ("C", _I), ("reserved", _I), ("out", _P), ("capacity", _c.c_int64), ("length", _P),
+    _fields_ = [("pixels", _P), ("H", _I), ("W", _I), ("C", _I), ("strategy", _I), ("out", _P), ("capacity", _c.c_int64), ("length", _P),
                 ("workspace", _P)]
 
 

@@ -12,8 +12,15 @@
 //   png_assemble_kernel  one workgroup per segment again: the exclusive sum of the chunk lengths before it places the chunk in the
 //                        file; the first also writes signature, IHDR and the two-byte zlib header chunk, the last the closing chunk
 //                        (final empty fixed block + Adler-32), IEND and the file length.
-// No global atomics; the LDS atomics are integer OR / XOR / ADD, whose results do not depend on arrival order.  Every loop bound is a
-// function of the sizes.
+// No global atomics; the LDS atomics are integer OR / XOR / ADD / MAX, whose results do not depend on arrival order.  Every loop bound is
+// a function of the sizes.
+//
+// A picture of strategy 1 (hps_png_image.strategy; include/hps.h documents the stream) goes through the same two launches; its segments
+// take the filter among all five types by the same rule, count the tokens' 286 literal/length symbols in LDS, build a length-limited
+// canonical code from the counts (build_code), code its lengths with the code-length alphabet (a second, 7-bit-limited code of the same
+// construction) and emit ONE dynamic block where strategy 0 emits a fixed one.  Everything but the two-queue Huffman merge (one lane,
+// at most 285 steps of two or three dependent LDS reads) and the Kraft repair over 15 counters runs on all lanes.  The dynamic coder's
+// scratch lies in the staging buffer behind the place of the finished chunk: no LDS is added beyond three more filter sums per row.
 #include "hps_common.h"
 
 namespace {
@@ -37,6 +44,7 @@ struct PngPic {
     uint8_t* out;
     long long* length;
     int H, W, C, R, nseg, seg0;           // R rows per segment, nseg segments, seg0 = segments of the pictures before this one
+    int strategy;                         // 0: fixed Huffman, Sub / Up; 1: one dynamic block per segment, all five filters
 };
 struct PngParams {
     PngPic pic[HPS_PNG_MAX_IMAGES];
@@ -143,7 +151,7 @@ struct CountSink {
 struct EmitSink {
     uint32_t* w;
     uint32_t pos;
-    __device__ void put(uint32_t v, int nb) {                                   // nb <= 18 bits, already in stream order (LSB first)
+    __device__ void put(uint32_t v, int nb) {                                   // nb <= 21 bits, already in stream order (LSB first)
         const uint64_t x = (uint64_t)v << (pos & 31);
         atomicOr(&w[pos >> 5], (uint32_t)x);
         const uint32_t hi = (uint32_t)(x >> 32);
@@ -187,6 +195,182 @@ __device__ void walk_tokens(const uint8_t* filt, int b0, int b1, int prevz, int 
     }
 }
 
+// ---- strategy 1: a dynamic Huffman block -------------------------------------------------------------------------------------------
+constexpr int PNG_LL = 286, PNG_CL = 19;  // the literal/length and the code-length alphabets
+constexpr int PNG_SYMS = 288;
+constexpr int PNG_LL_BITS = 15, PNG_CL_BITS = 7;
+// The dynamic coder's scratch.  It lies in the staging buffer behind the finished chunk (12 + S + 5 bytes rounded up to 16 <= 16 416),
+// which is free once the rows are filtered.
+constexpr int PNG_DYN_OFFSET = PNG_SEG_BYTES + 64;
+struct DynScratch {
+    uint32_t cnt[PNG_SYMS];               // the literal/length counts
+    int sw[PNG_SYMS], iw[PNG_SYMS];       // leaf weights ascending; internal nodes' weights in the order of their creation
+    uint16_t pl[PNG_SYMS], pi[PNG_SYMS];  // the parent (an internal node) of every leaf and of every internal node
+    uint16_t code[PNG_SYMS];              // canonical codes, already bit-reversed for the LSB-first stream
+    uint8_t len[PNG_SYMS];
+    uint8_t seq[PNG_SYMS];                // the code length sequence: hlit literal/length lengths, one distance length
+    uint32_t clcnt[32];
+    uint16_t clcode[32];
+    uint8_t cllen[32];
+    uint32_t bl[16], next[16];            // codes per length; the first code of each length
+    int n, hlit, hclen;
+};
+static_assert(PNG_DYN_OFFSET % 16 == 0 && PNG_DYN_OFFSET + (int)sizeof(DynScratch) <= PNG_RAW_LDS, "the scratch fits behind the chunk");
+static_assert(12 + PNG_SEG_BYTES + 5 + 15 <= PNG_DYN_OFFSET, "the finished chunk ends before the scratch");
+__constant__ uint8_t c_clorder[PNG_CL] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
+
+__device__ inline int paeth(int a, int b, int c) {
+    const int p = a + b - c, pa = abs(p - a), pb = abs(p - b), pc = abs(p - c);
+    return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
+}
+__device__ inline uint32_t magnitude(int d) {                                    // |d mod 256 read as a signed byte|
+    d &= 255;
+    return d < 128 ? d : 256 - d;
+}
+
+// The code lengths and canonical codes of an alphabet of N <= 2 PNG_THREADS symbols from its counts (0 = unused), no length above M;
+// called by the whole workgroup.  include/hps.h states the rule:
+//   1. the used symbols in descending order of count, ties in ascending order of index (every lane ranks its symbols by counting: N
+//      broadcast LDS reads each);
+//   2. the leaves per depth of the two-queue Huffman tree on the counts, a leaf before an internal node of equal weight (lane 0 merges:
+//      n - 1 steps; then every lane climbs from its leaves to the root), depths above M counted as M;
+//   3. while the Kraft sum exceeds 1, one code of M bits leaves and one code of the greatest length below M that has any becomes two
+//      codes one bit longer (lane 0; at most n steps over M counters);
+//   4. the first symbols in the order of 1 take the shortest lengths; codes are deflate's canonical ones (every lane counts the symbols
+//      of its length before it).
+__device__ void build_code(const uint32_t* cnt, int N, int M, DynScratch& W, uint8_t* len, uint16_t* code) {
+    const int tid = threadIdx.x;
+    if (tid < 16) W.bl[tid] = 0;
+    if (tid == 0) W.n = 0;
+    __syncthreads();
+    uint32_t c[2];
+    int rank[2];
+    for (int h = 0; h < 2; ++h) {
+        const int s = tid + h * PNG_THREADS;
+        c[h] = s < N ? cnt[s] : 0;
+        rank[h] = 0;
+        if (c[h]) {
+            for (int t = 0; t < N; ++t) {
+                const uint32_t ct = cnt[t];
+                rank[h] += (ct > c[h] || (ct == c[h] && t < s)) ? 1 : 0;
+            }
+            atomicAdd(&W.n, 1);
+        }
+    }
+    __syncthreads();
+    const int n = W.n;
+    for (int h = 0; h < 2; ++h)
+        if (c[h]) W.sw[n - 1 - rank[h]] = (int)c[h];
+    __syncthreads();
+    if (tid == 0 && n >= 2) {
+        int li = 0, ii = 0;
+        for (int k = 0; k < n - 1; ++k) {
+            int w2 = 0;
+            for (int pick = 0; pick < 2; ++pick) {
+                if (li < n && (ii >= k || W.sw[li] <= W.iw[ii])) { w2 += W.sw[li]; W.pl[li++] = (uint16_t)k; }
+                else { w2 += W.iw[ii]; W.pi[ii++] = (uint16_t)k; }
+            }
+            W.iw[k] = w2;
+        }
+    }
+    __syncthreads();
+    for (int h = 0; h < 2; ++h)
+        if (c[h]) {
+            int d = 1;
+            if (n >= 2) {
+                int k = W.pl[n - 1 - rank[h]];
+                for (int step = 0; step < n && k != n - 2; ++step) { k = W.pi[k]; ++d; }
+            }
+            atomicAdd(&W.bl[min(d, M)], 1u);
+        }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t total = 0;
+        for (int d = 1; d <= M; ++d) total += W.bl[d] << (M - d);
+        for (int it = 0; it < N && total > (1u << M); ++it) {
+            --W.bl[M];
+            for (int i = M - 1; i >= 1; --i)
+                if (W.bl[i]) { --W.bl[i]; W.bl[i + 1] += 2; break; }
+            --total;
+        }
+        uint32_t first = 0;
+        for (int d = 1; d <= M; ++d) W.next[d] = first = (first + W.bl[d - 1]) << 1;
+    }
+    __syncthreads();
+    for (int h = 0; h < 2; ++h) {
+        const int s = tid + h * PNG_THREADS;
+        if (s >= N) continue;
+        int L = 0;
+        if (c[h]) {
+            int cum = 0;
+            for (int d = 1; d <= M; ++d) {
+                cum += (int)W.bl[d];
+                if (rank[h] < cum) { L = d; break; }
+            }
+        }
+        len[s] = (uint8_t)L;
+    }
+    __syncthreads();
+    for (int h = 0; h < 2; ++h)
+        if (c[h]) {
+            const int s = tid + h * PNG_THREADS, L = len[s];
+            uint32_t k = W.next[L];
+            for (int t = 0; t < s; ++t) k += len[t] == L ? 1 : 0;
+            code[s] = (uint16_t)(__brev(k) >> (32 - L));
+        }
+    __syncthreads();
+}
+
+// One position of the code length sequence as a code-length symbol: position k of a maximal run of r equal values v.  A run of zeros is
+// cut into pieces of 138 from its start: 11 .. 138 is symbol 18, 3 .. 10 symbol 17 (emitted by the piece's first position), 1 or 2
+// stay symbols 0.  A run of a length v > 0 is v once, then pieces of 6: 3 .. 6 is symbol 16, 1 or 2 stay symbols v.  sym < 0: no symbol.
+__device__ inline void cl_token(int v, int k, int r, int& sym, int& eb, int& ext) {
+    sym = -1; eb = 0; ext = 0;
+    if (v != 0 && k == 0) { sym = v; return; }
+    const int cut = v ? 6 : 138;
+    if (v) { --k; --r; }
+    const int q = k / cut, off = k - q * cut, piece = min(cut, r - q * cut);
+    if (piece < 3) sym = v;
+    else if (off == 0) {
+        if (v) { sym = 16; eb = 2; ext = piece - 3; }
+        else if (piece >= 11) { sym = 18; eb = 7; ext = piece - 11; }
+        else { sym = 17; eb = 3; ext = piece - 3; }
+    }
+}
+
+struct HistSink {                          // the fixed code's bits and the symbols' counts in one walk
+    uint32_t* cnt;
+    int bits = 0;
+    __device__ void literal(uint32_t v) { bits += literal_bits(v); atomicAdd(&cnt[v], 1u); }
+    __device__ void match(int L) {
+        int sym, eb, extra;
+        length_symbol(L, sym, eb, extra);
+        bits += match_bits(L);
+        atomicAdd(&cnt[sym], 1u);
+    }
+};
+struct DynCountSink {
+    const uint8_t* len;
+    int bits = 0;
+    __device__ void literal(uint32_t v) { bits += len[v]; }
+    __device__ void match(int L) {
+        int sym, eb, extra;
+        length_symbol(L, sym, eb, extra);
+        bits += len[sym] + eb + 1;                                               // + the one-bit code of distance 1
+    }
+};
+struct DynEmitSink {
+    EmitSink out;
+    const uint8_t* len;
+    const uint16_t* code;
+    __device__ void literal(uint32_t v) { out.put(code[v], len[v]); }
+    __device__ void match(int L) {
+        int sym, eb, extra;
+        length_symbol(L, sym, eb, extra);
+        out.put(code[sym] | ((uint32_t)extra << len[sym]), len[sym] + eb + 1);   // at most 15 + 5 + 1 bits; distance 1 is the bit 0
+    }
+};
+
 __device__ inline const PngPic& find_picture(const PngParams& P, int block) {
     int p = 0;
     for (int i = 1; i < HPS_PNG_MAX_IMAGES; ++i)
@@ -199,7 +383,8 @@ __global__ void __launch_bounds__(PNG_THREADS) png_segment_kernel(const PngParam
     __shared__ __attribute__((aligned(16))) uint8_t s_filt[PNG_SEG_BYTES];
     __shared__ uint32_t s_crc[256];
     __shared__ int s_scan[PNG_THREADS];
-    __shared__ uint32_t s_rowsum[PNG_MAX_SEG_ROWS][2];
+    __shared__ uint32_t s_rowsum[PNG_MAX_SEG_ROWS][5];     // sum of |residual| per row and filter type
+    __shared__ uint8_t s_rowtype[PNG_MAX_SEG_ROWS];
     __shared__ uint32_t s_red[3];                          // Adler sum a, sum b, the chunk's CRC register
     uint8_t* const s_img = reinterpret_cast<uint8_t*>(s_img4);
     uint32_t* const s_words = reinterpret_cast<uint32_t*>(s_img4);
@@ -223,33 +408,57 @@ __global__ void __launch_bounds__(PNG_THREADS) png_segment_kernel(const PngParam
             for (int b = 0; b < 16; ++b) s_img[16 * u + b] = addr + b < total ? px[addr + b] : 0;
     }
     s_crc[tid] = crc_table_entry(tid);
-    if (tid < PNG_MAX_SEG_ROWS) s_rowsum[tid][0] = s_rowsum[tid][1] = 0;
+    if (tid < PNG_MAX_SEG_ROWS)
+        for (int f = 0; f < 5; ++f) s_rowsum[tid][f] = 0;
     if (tid < 3) s_red[tid] = 0;
     __syncthreads();
 
+    const bool dynamic = pic.strategy == 1;
     const int K = hps::ceil_div(S, PNG_THREADS);
     const int b0 = min(S, tid * K), b1 = min(S, b0 + K);
     const uint8_t* raw = s_img - a0;                       // raw[g] = byte g of the picture
 
-    // the filter of every row: sums of |Sub| and |Up| residuals, read as signed bytes
+    // the filter of every row: sums of |residual| per type, residuals read as signed bytes (strategy 0: Sub and Up only).  Paeth's
+    // upper-left byte is 0 for x < C and on the picture's first row; it lies in the staged row above otherwise.
     {
         int r = b0 / rb, c = b0 - r * rb;
-        uint32_t asub = 0, aup = 0;
+        uint32_t acc[5] = {0, 0, 0, 0, 0};
         for (int i = b0; i < b1; ++i) {
             if (c > 0) {
                 const int x = c - 1, g = (row0 + r) * WC + x;
-                const int cur = raw[g], left = x >= C ? raw[g - C] : 0, up = row0 + r > 0 ? raw[g - WC] : 0;
-                const int ds = (cur - left) & 255, du = (cur - up) & 255;
-                asub += ds < 128 ? ds : 256 - ds;
-                aup += du < 128 ? du : 256 - du;
+                const bool top = row0 + r == 0;
+                const int cur = raw[g], left = x >= C ? raw[g - C] : 0, up = top ? 0 : raw[g - WC];
+                acc[1] += magnitude(cur - left);
+                acc[2] += magnitude(cur - up);
+                if (dynamic) {
+                    const int ul = (x >= C && !top) ? raw[g - WC - C] : 0;
+                    acc[0] += magnitude(cur);
+                    acc[3] += magnitude(cur - ((left + up) >> 1));
+                    acc[4] += magnitude(cur - paeth(left, up, ul));
+                }
             }
             if (++c == rb || i + 1 == b1) {
-                atomicAdd(&s_rowsum[r][0], asub);
-                atomicAdd(&s_rowsum[r][1], aup);
-                asub = aup = 0;
+                atomicAdd(&s_rowsum[r][1], acc[1]);
+                atomicAdd(&s_rowsum[r][2], acc[2]);
+                if (dynamic) {
+                    atomicAdd(&s_rowsum[r][0], acc[0]);
+                    atomicAdd(&s_rowsum[r][3], acc[3]);
+                    atomicAdd(&s_rowsum[r][4], acc[4]);
+                }
+                for (int f = 0; f < 5; ++f) acc[f] = 0;
                 if (c == rb) { c = 0; ++r; }
             }
         }
+    }
+    __syncthreads();
+    if (tid < rows) {
+        int type = s_rowsum[tid][1] < s_rowsum[tid][2] ? 1 : 2;              // strategy 0: Sub only where strictly smaller than Up
+        if (dynamic) {                                                          // strategy 1: the smallest sum, ties to the lowest type
+            type = 0;
+            for (int f = 1; f < 5; ++f)
+                if (s_rowsum[tid][f] < s_rowsum[tid][type]) type = f;
+        }
+        s_rowtype[tid] = (uint8_t)type;
     }
     __syncthreads();
     // the filtered bytes and their Adler-32 sums: a = sum v, b = sum (S - i) v
@@ -257,13 +466,17 @@ __global__ void __launch_bounds__(PNG_THREADS) png_segment_kernel(const PngParam
         int r = b0 / rb, c = b0 - r * rb;
         uint32_t sa = 0, sb = 0;
         for (int i = b0; i < b1; ++i) {
-            const bool sub = s_rowsum[r][0] < s_rowsum[r][1];
+            const int type = s_rowtype[r];
             uint32_t v;
-            if (c == 0) v = sub ? 1 : 2;
+            if (c == 0) v = (uint32_t)type;
             else {
                 const int x = c - 1, g = (row0 + r) * WC + x;
-                const int cur = raw[g];
-                const int ref = sub ? (x >= C ? raw[g - C] : 0) : (row0 + r > 0 ? raw[g - WC] : 0);
+                const bool top = row0 + r == 0;
+                const int cur = raw[g], left = x >= C ? raw[g - C] : 0, up = top ? 0 : raw[g - WC];
+                int ref = type == 1 ? left : up;
+                if (type == 0) ref = 0;
+                else if (type == 3) ref = (left + up) >> 1;
+                else if (type == 4) ref = paeth(left, up, (x >= C && !top) ? raw[g - WC - C] : 0);
                 v = (cur - ref) & 255;
             }
             s_filt[i] = (uint8_t)v;
@@ -285,15 +498,77 @@ __global__ void __launch_bounds__(PNG_THREADS) png_segment_kernel(const PngParam
         }
     const int prevz = block_scan_excl<OpMax>(lastz, -1, s_scan, false, nullptr);
     const int nextz = block_scan_excl<OpMin>(firstz, S, s_scan, true, nullptr);
-    CountSink count;
-    walk_tokens(s_filt, b0, b1, prevz, nextz, count);
+    DynScratch& W = *reinterpret_cast<DynScratch*>(s_img + PNG_DYN_OFFSET);   // the raw rows are no longer needed
+    int lane_fixed_bits;
+    if (dynamic) {
+        for (int i = tid; i < PNG_SYMS; i += PNG_THREADS) W.cnt[i] = 0;
+        if (tid < 32) W.clcnt[tid] = 0;
+        if (tid == 0) W.hlit = 257;
+        __syncthreads();
+        HistSink hist{W.cnt};
+        walk_tokens(s_filt, b0, b1, prevz, nextz, hist);
+        if (tid == 0) atomicAdd(&W.cnt[256], 1u);                               // the end-of-block symbol
+        lane_fixed_bits = hist.bits;
+    } else {
+        CountSink count;
+        walk_tokens(s_filt, b0, b1, prevz, nextz, count);
+        lane_fixed_bits = count.bits;
+    }
     int token_bits = 0;
-    const int pos = block_scan_excl<OpAdd>(count.bits, 0, s_scan, false, &token_bits);
+    const int pos = block_scan_excl<OpAdd>(lane_fixed_bits, 0, s_scan, false, &token_bits);
 
     // fixed block: 3 header bits, the tokens, end of block (7), an empty stored block (3 bits, pad, 00 00 FF FF); or one stored block
     const int nfixed = (3 + token_bits + 7 + 3 + 7) / 8 + 4;
-    const bool stored = nfixed > S + 5;
-    const int n = stored ? S + 5 : nfixed;
+    int n = nfixed;
+
+    // strategy 1, the dynamic block: 17 header bits, 3 hclen bits, the code length symbols, the tokens, end of block, the same close
+    bool use_dynamic = false;
+    int hlit = 0, hclen = 0, hdr_bits = 0, dyn_bits = 0, dpos = 0, clpos = 0;
+    int clsym[2] = {-1, -1}, cleb[2] = {0, 0}, clext[2] = {0, 0};
+    if (dynamic) {
+        build_code(W.cnt, PNG_LL, PNG_LL_BITS, W, W.len, W.code);
+        for (int s = 257 + tid; s < PNG_LL; s += PNG_THREADS)
+            if (W.len[s]) atomicMax(&W.hlit, s + 1);
+        __syncthreads();
+        hlit = W.hlit;
+        const int nseq = hlit + 1;                                              // and the one distance code: length 1 for symbol 0
+        for (int i = tid; i < nseq; i += PNG_THREADS) W.seq[i] = i < hlit ? W.len[i] : 1;
+        __syncthreads();
+        // two positions of the sequence per lane; the runs of equal values they lie in, from scans over the run starts
+        const int i0 = 2 * tid, i1 = i0 + 1;
+        const bool in0 = i0 < nseq, in1 = i1 < nseq;
+        const int v0 = in0 ? W.seq[i0] : -1, v1 = in1 ? W.seq[i1] : -1;
+        const bool bd0 = in0 && (i0 == 0 || v0 != W.seq[i0 - 1]), bd1 = in1 && v1 != v0;
+        const int prevb = block_scan_excl<OpMax>(bd1 ? i1 : (bd0 ? i0 : -1), -1, s_scan, false, nullptr);
+        const int nextb = block_scan_excl<OpMin>(bd0 ? i0 : (bd1 ? i1 : nseq), nseq, s_scan, true, nullptr);
+        const int st0 = bd0 ? i0 : prevb, st1 = bd1 ? i1 : st0;
+        if (in0) cl_token(v0, i0 - st0, (bd1 ? i1 : nextb) - st0, clsym[0], cleb[0], clext[0]);
+        if (in1) cl_token(v1, i1 - st1, nextb - st1, clsym[1], cleb[1], clext[1]);
+        for (int h = 0; h < 2; ++h)
+            if (clsym[h] >= 0) atomicAdd(&W.clcnt[clsym[h]], 1u);
+        __syncthreads();
+        build_code(W.clcnt, PNG_CL, PNG_CL_BITS, W, W.cllen, W.clcode);
+        if (tid == 0) {
+            int h = 4;
+            for (int k = PNG_CL - 1; k >= 4; --k)
+                if (W.cllen[c_clorder[k]]) { h = k + 1; break; }
+            W.hclen = h;
+        }
+        __syncthreads();
+        hclen = W.hclen;
+        int clbits = 0, cl_total = 0;
+        for (int h = 0; h < 2; ++h)
+            if (clsym[h] >= 0) clbits += W.cllen[clsym[h]] + cleb[h];
+        clpos = block_scan_excl<OpAdd>(clbits, 0, s_scan, false, &cl_total);
+        hdr_bits = 17 + 3 * hclen + cl_total;
+        DynCountSink dcount{W.len};
+        walk_tokens(s_filt, b0, b1, prevz, nextz, dcount);
+        dpos = block_scan_excl<OpAdd>(dcount.bits, 0, s_scan, false, &dyn_bits);
+        const int ndyn = (hdr_bits + dyn_bits + W.len[256] + 3 + 7) / 8 + 4;
+        if (ndyn <= nfixed) { use_dynamic = true; n = ndyn; }                   // on a tie the dynamic block
+    }
+    const bool stored = n > S + 5;
+    if (stored) { n = S + 5; use_dynamic = false; }
     const int units = (12 + n + 15) / 16;
     for (int u = tid; u < units; u += PNG_THREADS) s_img4[u] = make_uint4(0, 0, 0, 0);
     __syncthreads();
@@ -304,6 +579,23 @@ __global__ void __launch_bounds__(PNG_THREADS) png_segment_kernel(const PngParam
             s_img[9] = (uint8_t)S; s_img[10] = (uint8_t)(S >> 8);
             s_img[11] = (uint8_t)~S; s_img[12] = (uint8_t)(~S >> 8);
         }
+    } else if (use_dynamic) {
+        if (tid == 0) {
+            // BFINAL = 0, BTYPE = 10, HLIT - 257 (5 bits), HDIST - 1 = 0 (5), HCLEN - 4 (4); the code-length code's lengths in deflate's order
+            EmitSink head{s_words, 64u};
+            head.put(4u | ((uint32_t)(hlit - 257) << 3) | ((uint32_t)(hclen - 4) << 13), 17);
+            for (int k = 0; k < hclen; ++k) head.put(W.cllen[c_clorder[k]], 3);
+            EmitSink eob{s_words, (uint32_t)(64 + hdr_bits + dyn_bits)};
+            eob.put(W.code[256], W.len[256]);
+        }
+        EmitSink lengths{s_words, (uint32_t)(64 + 17 + 3 * hclen + clpos)};
+        for (int h = 0; h < 2; ++h)
+            if (clsym[h] >= 0) {
+                const int L = W.cllen[clsym[h]];
+                lengths.put(W.clcode[clsym[h]] | ((uint32_t)clext[h] << L), L + cleb[h]);
+            }
+        DynEmitSink emit{EmitSink{s_words, (uint32_t)(64 + hdr_bits + dpos)}, W.len, W.code};
+        walk_tokens(s_filt, b0, b1, prevz, nextz, emit);
     } else {
         EmitSink emit{s_words, (uint32_t)(64 + 3 + pos)};
         walk_tokens(s_filt, b0, b1, prevz, nextz, emit);
@@ -432,7 +724,8 @@ extern "C" int hps_png_segment_rows(int H, int W, int C) {
 // 12 + 6, IEND 12.  A segment of S_k filtered bytes is coded with the fixed tables in ceil((3 + t + 7 + 3) / 8) + 4 bytes, t <= 9 S_k
 // token bits (a literal takes at most 9 bits, and a match of L >= 3 bytes at most 18 bits <= 9 L) -- the 9 / 8 bound -- but the
 // kernel takes one stored block, 5 + S_k bytes, whenever the fixed form is longer, so n_k <= S_k + 5 always (S_k <= 16 384 < 65 536:
-// one stored block holds it).  The S_k sum to H (1 + W C).  Hence
+// one stored block holds it), and strategy 1 takes its dynamic block only where that is no longer than the fixed form, so the same
+// holds for it.  The S_k sum to H (1 + W C).  Hence
 //     file <= 8 + 25 + 14 + H (1 + W C) + 17 ceil(H / R) + 18 + 12.
 extern "C" int64_t hps_png_bound(int H, int W, int C) {
     if (!supported(H, W, C)) {
@@ -454,20 +747,21 @@ extern "C" int hps_png_encode(const hps_png_encode_args* a, hps_stream_t stream)
     for (int i = 0; i < HPS_PNG_MAX_IMAGES; ++i) {
         PngPic& p = P.pic[i];
         if (i >= a->num_images) {
-            p = PngPic{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1, 0, 0x7fffffff};
+            p = PngPic{nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 1, 0, 0x7fffffff, 0};
             continue;
         }
         const hps_png_image& im = a->image[i];
         if (!im.pixels || !im.out || !im.length || !im.workspace) return bad_arg("hps_png_encode: null pointer (a picture's pixels, out, length, workspace)");
         if (im.C != 1 && im.C != 3) return bad_arg("hps_png_encode: C is 1 (greyscale) or 3 (RGB)");
         if (im.H < 1 || im.W < 1) return bad_arg("hps_png_encode: H and W are at least 1");
+        if (im.strategy != 0 && im.strategy != 1) return bad_arg("hps_png_encode: strategy is 0 (fixed Huffman code) or 1 (dynamic Huffman code)");
         if (!supported(im.H, im.W, im.C)) return bad_arg("hps_png_encode: supported pictures have W C <= 12288 and H <= 32768");
         if (im.capacity < hps_png_bound(im.H, im.W, im.C)) return bad_arg("hps_png_encode: a picture's capacity is below hps_png_bound(H, W, C)");
         if ((reinterpret_cast<uintptr_t>(im.pixels) | reinterpret_cast<uintptr_t>(im.out) | reinterpret_cast<uintptr_t>(im.workspace)) & 15)
             return bad_arg("hps_png_encode: pixels, out and workspace must be 16-byte aligned");
         if (reinterpret_cast<uintptr_t>(im.length) & 7) return bad_arg("hps_png_encode: length must be 8-byte aligned");
         p.px = im.pixels; p.ws = static_cast<uint8_t*>(im.workspace); p.out = im.out; p.length = reinterpret_cast<long long*>(im.length);
-        p.H = im.H; p.W = im.W; p.C = im.C;
+        p.H = im.H; p.W = im.W; p.C = im.C; p.strategy = im.strategy;
         p.R = seg_rows(im.W, im.C);
         p.nseg = ceil_div(im.H, p.R);
         p.seg0 = segs;

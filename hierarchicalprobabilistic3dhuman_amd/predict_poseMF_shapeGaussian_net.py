@@ -670,7 +670,9 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     all on the device; a bare tensor gives black crop panels, no joint discs and no uncropped picture (one warning).
     ``png_encoder``: "pil" (the default) encodes the pictures with PIL on visualise.PngWriter's host threads; "device" makes the PNG
     files on the device (visualise.DevicePngWriter, hps_png_encode: an image's pictures in one library call, only the compressed bytes
-    cross to the host).  The decoded pixels are the same; the files are not (another compressor).  Anything else is a ValueError.
+    cross to the host); "device-dynamic" is the same route with DevicePngWriter(strategy="dynamic"): a dynamic Huffman code per segment
+    and all five filters, for smaller files.  The decoded pixels are the same; the files are not (another compressor).  Anything else is
+    a ValueError.
 
     ``batched_front_end``: None runs the front end of a whole group of ``batch_size`` images on the device with ONE HRNet forward
     (predict_frontend.DevicePredictFrontEnd: box, crops and key points are libhps kernels, no host synchronisation of its own) when it
@@ -678,8 +680,9 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     ``edge_map_into`` -- and the per-image route of predict_hrnet / image_utils otherwise; True demands it (HpsError when it cannot be
     used), False forbids it.
     """
-    if png_encoder not in ("pil", "device"):
-        raise ValueError("png_encoder is 'pil' or 'device', not %r" % (png_encoder,))
+    if png_encoder not in ("pil", "device", "device-dynamic"):
+        raise ValueError("png_encoder is 'pil', 'device' or 'device-dynamic', not %r" % (png_encoder,))
+    on_device = png_encoder != "pil"
     device = torch.device(device)
     batched = None
     if use_batched_front_end(batched_front_end, proxy_rep_fn, device, hrnet_model, edge_detect_model):
@@ -701,7 +704,7 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     if vis_renderer is not None:
         from .visualise import DevicePngWriter, PngWriter, predict_visualiser
         vis = predict_visualiser(vis_renderer, pose_shape_cfg, visualise_wh)
-        writer = DevicePngWriter() if png_encoder == "device" else PngWriter()
+        writer = DevicePngWriter(strategy="dynamic" if png_encoder == "device-dynamic" else "fixed") if on_device else PngWriter()
     warned = []
 
     def get_proxy(name):
@@ -734,7 +737,7 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
             proxy = proxy.to(device, non_blocking=True)
         crop, joints = ex.get("cropped_rgb"), ex.get("joints2D")
         pictures = []                                    # the device encoder takes an image's pictures in one call
-        write = (lambda image, path: pictures.append((image, path))) if png_encoder == "device" else writer.write
+        write = (lambda image, path: pictures.append((image, path))) if on_device else writer.write
         write(vis.figure(item, crop, proxy.float(), joints), stem + ".png")
         if visualise_uncropped:
             if all(ex.get(k) is not None for k in ("image", "bbox_centre", "bbox_wh")):

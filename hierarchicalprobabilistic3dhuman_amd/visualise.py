@@ -318,9 +318,16 @@ class DevicePngWriter:
     file's length, copies exactly that many bytes through a reused page-locked buffer on a copy stream of its own, writes
     ``path + ".part"`` and renames it.  No host thread compresses anything.  ``write_many`` puts up to _capi.PNG_MAX_IMAGES pictures
     -- one predicted image's three -- into one library call.  At most 2 x workers pictures are in flight; ``drain`` waits for every
-    file and re-raises the first error.  Pictures are (H, W), (H, W, 1) or (H, W, 3) uint8 device tensors."""
+    file and re-raises the first error.  Pictures are (H, W), (H, W, 1) or (H, W, 3) uint8 device tensors.  ``strategy``: "fixed" (the
+    default: deflate's fixed Huffman code, filters Sub and Up) or "dynamic" (one dynamic Huffman code per segment, all five filters:
+    smaller files for more device time) -- hps_png_image.strategy 0 and 1."""
 
-    def __init__(self, workers=4):
+    STRATEGIES = {"fixed": 0, "dynamic": 1}
+
+    def __init__(self, workers=4, strategy="fixed"):
+        if strategy not in self.STRATEGIES:
+            raise ValueError("strategy is 'fixed' or 'dynamic', not %r" % (strategy,))
+        self.strategy = strategy
         self.workers = max(1, min(4, int(workers)))
         self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers)
         self._free = {}
@@ -355,6 +362,7 @@ class DevicePngWriter:
             slots.append(slot)
             im = a.image[i]
             im.pixels, (im.H, im.W, im.C) = _capi.ptr(image, torch.uint8, "image"), key
+            im.strategy = self.STRATEGIES[self.strategy]
             im.out, im.capacity = _capi.ptr(slot.out, torch.uint8), slot.bound
             im.length, im.workspace = _capi.ptr(slot.length, torch.int64), _capi.ptr(slot.workspace, torch.uint8)
         try:

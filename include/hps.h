@@ -1415,14 +1415,47 @@ int hps_vis_uncrop(const hps_vis_uncrop_args* args, hps_stream_t stream);
  * literals); nothing reaches before the segment.  Tokens are coded with deflate's fixed Huffman tables and the segment closes with an
  * empty stored block, which ends it on a byte boundary; where one stored block is shorter, the segment is that stored block.
  *
+ *
+ * The above is a picture's stream under strategy = 0.  strategy = 1 keeps the container, the segments, the tokens and the close, and
+ * changes the filters and the code; pictures of one call may differ in strategy, and the same two launches serve both.
+ *   Filter: a row takes the type among None 0, Sub 1, Up 2, Average 3, Paeth 4 with the smallest sum of |residual| (as signed bytes);
+ *     ties go to the lowest type.  Bytes left of the row and above the picture are 0, Average is floor((left + up) / 2).
+ *   Counts: the segment's tokens' literal/length symbols (RFC 1951: 0..255, 257..285), and one end-of-block symbol 256.
+ *   Code lengths, for an alphabet with counts and a limit M (M = 15 here, M = 7 for the code-length alphabet below):
+ *     1. order the used symbols by descending count, ties by ascending symbol index;
+ *     2. build the Huffman tree by the two-queue method: the leaves in ascending order of count, the internal nodes in the order of
+ *        their creation, each step joining the two smallest heads, a leaf before an internal node of equal weight; count the leaves at
+ *        every depth, a depth above M counting as M;
+ *     3. while sum over depths d of leaves(d) 2^(M - d) exceeds 2^M: leaves(M) falls by one, and for the greatest i < M with
+ *        leaves(i) > 0, leaves(i) falls by one and leaves(i + 1) rises by two (each round lowers the sum by one);
+ *     4. the first leaves(1) symbols in the order of 1 take length 1, the next leaves(2) length 2, and so on.
+ *     A single used symbol takes length 1 (this cannot happen to either alphabet here: a segment has a literal and the end-of-block
+ *     symbol, its lengths have a non-zero value and a zero run or two different values).  Codes are deflate's canonical codes.  The
+ *     result depends on the counts alone and is complete (Kraft sum 1).  On the device all lanes rank the symbols (286 broadcast LDS
+ *     reads per symbol), climb from their leaves to the root and place their codes; one lane merges the two queues (at most 285 steps
+ *     of two or three dependent LDS reads per segment) and runs step 3 over M counters.
+ *   Distance code: one code of length 1 for distance symbol 0 (HDIST = 1 code), declared also when the segment holds no match.
+ *   Header: BFINAL 0, BTYPE 10, HLIT = last used literal/length symbol + 1, HDIST = 1, HCLEN trimmed to the last used code-length symbol
+ *     in deflate's permuted order.  The sequence of HLIT lengths and the one distance length is coded run by run of equal values: a run
+ *     of z zeros is cut into pieces of 138 from its start, a piece of 11..138 is symbol 18, of 3..10 symbol 17, of 1 or 2 that many
+ *     symbols 0; a run of r equal lengths v > 0 is v once, then the r - 1 others cut into pieces of 6 from their start, a piece of 3..6
+ *     is symbol 16, of 1 or 2 that many symbols v.  The code-length alphabet's code comes from these symbols' counts by the rule above.
+ *   A token is its literal/length code, the length's extra bits and, for a match, the one bit 0 of distance 1: at most 15 + 5 + 1 bits.
+ *   Choice: the segment is its dynamic block and the closing empty stored block unless its strategy-0 form (the fixed block with the
+ *     same close, or one stored block where that is shorter) is strictly shorter in bytes; then it is that form, on strategy 1's filtered
+ *     bytes.  The fixed block stays a candidate because a segment of a few dozen bytes cannot pay for a code's header.  So no segment
+ *     is longer than S + 5 bytes and hps_png_bound holds for both strategies.
+ *
  * Supported: C in {1, 3}, W C in [1, 12288] (4096 RGB pixels), H in [1, 32768]; anything else is HPS_E_BADARG, as are null pointers,
- * a wrong struct_bytes, num_images outside [1, HPS_PNG_MAX_IMAGES] and a capacity below the bound -- all before any launch.
+ * a strategy other than 0 and 1, a wrong struct_bytes, num_images outside [1, HPS_PNG_MAX_IMAGES] and a capacity below the bound --
+ * all before any launch.
  * hps_png_bound and hps_png_segment_rows are host functions; both return -1 (and set hps_last_error) outside the supported range.
  * hps_png_bound(H, W, C) = 77 + H (1 + W C) + 17 ceil(H / rows per segment): no file is longer (derivation: csrc/png.hip). */
 #define HPS_PNG_MAX_IMAGES 8
 typedef struct hps_png_image {
     const uint8_t* pixels;                                     /* (H, W, C) */
-    int H, W, C, reserved;
+    int H, W, C;
+    int strategy;                                              /* 0: fixed Huffman code, Sub / Up; 1: dynamic code, five filters */
     uint8_t* out;                                              /* (capacity) */
     int64_t capacity;
     int64_t* length;                                           /* (1) */

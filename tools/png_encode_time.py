@@ -1,13 +1,15 @@
 """Time per image of writing the three predict pictures as PNG files, on one MI355X: visualise.PngWriter (bytes to the host, PIL on four
-threads -- the yardstick, untouched) against visualise.DevicePngWriter (hps_png_encode on the device, only the file crosses).
+threads -- the yardstick, untouched) against visualise.DevicePngWriter (hps_png_encode on the device, only the file crosses) with
+strategy "fixed" and with strategy "dynamic".
 
     python tools/png_encode_time.py [--out profiles/png_encode_time.txt] [--commit ID]
 
 tools/predict_vis_time.py's scene and its three pictures at visualise_wh = 512: the eight-panel figure (1024 x 2048), the body over a
 720 x 960 photograph, the 3 x 6 sample sheet (1536 x 3072).  The pictures are composed once; a round is, per writer, the host clock from
-the finished device pictures to drained files in a temporary directory.  The two writers alternate round by round in one process:
+the finished device pictures to drained files in a temporary directory.  The three writers alternate round by round in one process:
 3 warm-up rounds, then ``--rounds`` timed ones; median and quartiles.  Also recorded: the library's launches per image, the device
-time of the library call alone, the bytes copied to the host, and each picture's file size beside PIL's compress_level=1 size."""
+time of the library call alone under either strategy, the bytes copied to the host, and each picture's file sizes beside PIL's
+compress_level=1 size.  The output is appended to ``--out``."""
 import argparse
 import ctypes
 import os
@@ -67,7 +69,7 @@ def main():
     dev = torch.device("cuda", torch.cuda.current_device())
     pics = pictures(dev)
     tmp = tempfile.mkdtemp(prefix="png_encode_time_")
-    writers = {"pil": visualise.PngWriter(), "device": visualise.DevicePngWriter()}
+    writers = {"pil": visualise.PngWriter(), "device": visualise.DevicePngWriter(), "dynamic": visualise.DevicePngWriter(strategy="dynamic")}
     path = lambda route, name: os.path.join(tmp, "%s_%s.png" % (route, name))
 
     def pil():
@@ -75,18 +77,22 @@ def main():
             writers["pil"].write(t, path("pil", name))
         writers["pil"].drain()
 
-    def device():
-        writers["device"].write_many([t for _, t in pics], [path("device", name) for name, _ in pics])
-        writers["device"].drain()
+    def on_device(route):
+        def fn():
+            writers[route].write_many([t for _, t in pics], [path(route, name) for name, _ in pics])
+            writers[route].drain()
+        return fn
 
-    routes = {"pil": pil, "device": device}
-    seen = []
+    routes = {"pil": pil, "device": on_device("device"), "dynamic": on_device("dynamic")}
+    seen = {}
     original = _capi.call
-    _capi.call = lambda entry, *a: (seen.append(entry), original(entry, *a))[1]
-    try:
-        device()
-    finally:
-        _capi.call = original
+    for route in ("device", "dynamic"):
+        seen[route] = []
+        _capi.call = lambda entry, *a: (seen[route].append(entry), original(entry, *a))[1]
+        try:
+            routes[route]()
+        finally:
+            _capi.call = original
     for _ in range(3):
         for fn in routes.values():
             fn()
@@ -97,25 +103,28 @@ def main():
             t0 = time.perf_counter()
             fn()
             t[k].append((time.perf_counter() - t0) * 1e3)
-    # the library call alone: device events around windows of 20 calls on the writer's own buffers
+    # the library call alone: device events around windows of 20 calls on a writer's own buffers, the two strategies window by window
     dw = writers["device"]
     slots = [dw._slot((int(t.shape[0]), int(t.shape[1]), int(t.shape[2])), t.device) for _, t in pics]
-    a = _capi.PngEncodeArgs()
-    a.struct_bytes, a.num_images = ctypes.sizeof(_capi.PngEncodeArgs), len(pics)
-    for im, slot, (_, tensor) in zip(a.image, slots, pics):
-        im.pixels, (im.H, im.W, im.C) = _capi.ptr(tensor, torch.uint8), slot.key
-        im.out, im.capacity = _capi.ptr(slot.out, torch.uint8), slot.bound
-        im.length, im.workspace = _capi.ptr(slot.length, torch.int64), _capi.ptr(slot.workspace, torch.uint8)
-    kernel_ms = []
+    calls = {}
+    for route, strategy in (("device", 0), ("dynamic", 1)):
+        a = calls[route] = _capi.PngEncodeArgs()
+        a.struct_bytes, a.num_images = ctypes.sizeof(_capi.PngEncodeArgs), len(pics)
+        for im, slot, (_, tensor) in zip(a.image, slots, pics):
+            im.pixels, (im.H, im.W, im.C), im.strategy = _capi.ptr(tensor, torch.uint8), slot.key, strategy
+            im.out, im.capacity = _capi.ptr(slot.out, torch.uint8), slot.bound
+            im.length, im.workspace = _capi.ptr(slot.length, torch.int64), _capi.ptr(slot.workspace, torch.uint8)
+    kernel_ms = {route: [] for route in calls}
     for _ in range(1 + 9):
-        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        start.record()
-        for _ in range(20):
-            _capi.call("hps_png_encode", ctypes.addressof(a), _capi.stream())
-        stop.record()
-        stop.synchronize()
-        kernel_ms.append(start.elapsed_time(stop) / 20)
-    kernel_ms = np.percentile(kernel_ms[1:], [0, 50, 100])
+        for route, a in calls.items():
+            start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            for _ in range(20):
+                _capi.call("hps_png_encode", ctypes.addressof(a), _capi.stream())
+            stop.record()
+            stop.synchronize()
+            kernel_ms[route].append(start.elapsed_time(stop) / 20)
+    kernel_ms = {route: np.percentile(v[1:], [0, 50, 100]) for route, v in kernel_ms.items()}
     for w in writers.values():
         w.close()
     q = {k: np.percentile(v, [25, 50, 75]) for k, v in t.items()}
@@ -123,32 +132,39 @@ def main():
     sizes, same = [], True
     for name, tensor in pics:
         raw = tensor.cpu().numpy()
-        a, b = os.path.getsize(path("pil", name)), os.path.getsize(path("device", name))
-        same = same and np.array_equal(np.asarray(Image.open(path("device", name))), raw) and np.array_equal(np.asarray(Image.open(path("pil", name))), raw)
-        sizes.append((name, tuple(raw.shape), raw.size, a, b))
-    raw_total, dev_total = sum(s[2] for s in sizes), sum(s[4] for s in sizes)
-    wins = q["device"][1] < q["pil"][1] - (iqr["pil"] + iqr["device"])
+        a, b, c = (os.path.getsize(path(route, name)) for route in ("pil", "device", "dynamic"))
+        same = same and all(np.array_equal(np.asarray(Image.open(path(route, name))), raw) for route in ("pil", "device", "dynamic"))
+        sizes.append((name, tuple(raw.shape), raw.size, a, b, c))
+    raw_total, dev_total, dyn_total = sum(s[2] for s in sizes), sum(s[4] for s in sizes), sum(s[5] for s in sizes)
+    wins = {k: q[k][1] < q["pil"][1] - (iqr["pil"] + iqr[k]) for k in ("device", "dynamic")}
+    launches = lambda route: "%s = %d launches" % (", ".join("%d x %s" % (seen[route].count(e), e) for e in sorted(set(seen[route]))), 2 * seen[route].count("hps_png_encode"))
     lines = ["Writing the three predict pictures of one image as PNG files on one MI355X (gfx950), visualise_wh = 512: tools/png_encode_time.py,",
              "commit: %s.  Host clock from the finished device pictures to drained files; %d rounds of each writer, alternating," % (args.commit, args.rounds),
              "after 3 warm-up rounds; median (quartiles).", "",
-             "  PngWriter        (PIL, compress_level 1, four host threads)  %9.2f ms  (%.2f .. %.2f)" % (q["pil"][1], q["pil"][0], q["pil"][2]),
-             "  DevicePngWriter  (hps_png_encode, one call per image)         %9.2f ms  (%.2f .. %.2f)" % (q["device"][1], q["device"][0], q["device"][2]), "",
-             "  PngWriter / DevicePngWriter, medians   %6.2f" % (q["pil"][1] / q["device"][1]),
-             "  the device writer's median is lower by more than the sum of the two interquartile ranges (%.2f + %.2f ms): %s"
-             % (iqr["pil"], iqr["device"], "yes" if wins else "NO"), "",
-             "libhps calls per image, device writer: %s = %d launches" % (", ".join("%d x %s" % (seen.count(e), e) for e in sorted(set(seen))), 2 * seen.count("hps_png_encode")),
-             "hps_png_encode alone, the three pictures in one call (device events around 20 calls, median of 9 windows, fastest .. slowest): %.3f ms (%.3f .. %.3f)"
-             % (kernel_ms[1], kernel_ms[0], kernel_ms[2]),
-             "bytes copied to the host per image: PngWriter %d (the raw pictures), DevicePngWriter %d (the files) + %d (their lengths)" % (raw_total, dev_total, 8 * len(sizes)), "",
+             "  PngWriter        (PIL, compress_level 1, four host threads)          %9.2f ms  (%.2f .. %.2f)" % (q["pil"][1], q["pil"][0], q["pil"][2]),
+             "  DevicePngWriter  (hps_png_encode, strategy fixed, one call per image)   %6.2f ms  (%.2f .. %.2f)" % (q["device"][1], q["device"][0], q["device"][2]),
+             "  DevicePngWriter  (hps_png_encode, strategy dynamic, one call per image) %6.2f ms  (%.2f .. %.2f)" % (q["dynamic"][1], q["dynamic"][0], q["dynamic"][2]), "",
+             "  PngWriter / DevicePngWriter fixed, medians     %6.2f" % (q["pil"][1] / q["device"][1]),
+             "  PngWriter / DevicePngWriter dynamic, medians   %6.2f" % (q["pil"][1] / q["dynamic"][1]),
+             "  DevicePngWriter dynamic / fixed, medians       %6.2f" % (q["dynamic"][1] / q["device"][1]),
+             "  a device writer's median is lower than PIL's by more than the sum of the two interquartile ranges: fixed (%.2f + %.2f ms) %s, dynamic (%.2f + %.2f ms) %s"
+             % (iqr["pil"], iqr["device"], "yes" if wins["device"] else "NO", iqr["pil"], iqr["dynamic"], "yes" if wins["dynamic"] else "NO"), "",
+             "libhps calls per image: fixed %s; dynamic %s" % (launches("device"), launches("dynamic")),
+             "hps_png_encode alone, the three pictures in one call (device events around 20 calls, median of 9 windows, fastest .. slowest; the two",
+             "strategies window by window): fixed %.3f ms (%.3f .. %.3f), dynamic %.3f ms (%.3f .. %.3f), dynamic / fixed %.2f"
+             % (kernel_ms["device"][1], kernel_ms["device"][0], kernel_ms["device"][2], kernel_ms["dynamic"][1], kernel_ms["dynamic"][0], kernel_ms["dynamic"][2],
+                kernel_ms["dynamic"][1] / kernel_ms["device"][1]),
+             "bytes copied to the host per image: PngWriter %d (the raw pictures), DevicePngWriter fixed %d, dynamic %d (the files) + %d (their lengths)"
+             % (raw_total, dev_total, dyn_total, 8 * len(sizes)), "",
              "file sizes in bytes (every file decodes to the picture's bytes: %s):" % ("yes" if same else "NO"),
-             "  %-8s %-16s %10s %12s %12s %8s" % ("picture", "shape", "raw", "PIL level 1", "device", "ratio")]
-    for name, shape, raw, a, b in sizes:
-        lines.append("  %-8s %-16s %10d %12d %12d %8.2f" % (name, "x".join(map(str, shape)), raw, a, b, b / a))
+             "  %-8s %-16s %10s %12s %12s %12s %14s %16s" % ("picture", "shape", "raw", "PIL level 1", "fixed", "dynamic", "dynamic / PIL", "dynamic / fixed")]
+    for name, shape, raw, a, b, c in sizes:
+        lines.append("  %-8s %-16s %10d %12d %12d %12d %14.2f %16.2f" % (name, "x".join(map(str, shape)), raw, a, b, c, c / a, c / b))
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    with open(args.out, "w") as f:
-        f.write(text)
+    with open(args.out, "a") as f:                                   # appended: the file keeps the records of earlier commits
+        f.write(("\n" if os.path.getsize(args.out) else "") + text)
 
 
 if __name__ == "__main__":
