@@ -14,43 +14,21 @@
 // The stem (7x7 / 2, 18 channels) runs on the same kernel in "row mode": in NHWC one filter row of a window is
 // KW * C = 126 contiguous floats, so it is treated as one tap of 128 "channels" (the two extra floats meet zero
 // filter entries): K = 7 * 128 = 896 instead of 7 * 7 * 20 = 980, no channel padding of the image.
+// The K loop, its lane offsets and the epilogue's patch layout are csrc/conv_tile.h's (shared with csrc/conv_expand_down.hip); this file
+// holds the geometry of a k x k window, the down-sample workgroups, split K, the store of a sub-tile, and the layout and pool kernels.
 #include <type_traits>
 
-#include "hps_common.h"
+#include "conv_tile.h"
 
 namespace hps {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int PBK = 32;   // K-chunk (floats); one 128-byte LDS row per tile row
-
-// n / d for n < 2^32 with magic = floor(2^32 / d) (0xffffffff for d = 1): the estimate is at most one short
-__device__ __forceinline__ unsigned fastdiv(unsigned n, unsigned d, unsigned magic) {
-    unsigned q = __umulhi(n, magic);
-    if (n - q * d >= d) ++q;
-    return q;
-}
-static unsigned div_magic(unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ull / d); }
-
-// one 1-KiB LDS-DMA piece: lane l fetches 16 bytes at sbase + voff and they land at lds_addr + 16 l.
-// Issued from inline asm so that hipcc does not drain it in front of the next ds_read (conv.hip lds_dma16).
-__device__ __forceinline__ void lds_dma16_sv(unsigned voff, const float* sbase, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(voff), "s"(sbase), "s"(lds_addr)
-                 : "memory");
-}
-
 struct PadGeom {
-    int img_pitch, row_pitch, pix_pitch;   // input strides in floats (padded frame)
+    InFrame in;                            // the padded input frame; output (0,0) / tap (0,0) reads padded input (off, off)
     int cin_k;                             // contiguous floats per tap, multiple of 32
     int kw;                                // taps per filter row
-    int stride, off;                       // output (0,0) / tap (0,0) reads padded input (off, off)
-    int Ho, Wo, Mtot, Kp, Cout;
-    int opad;                              // halo of the output (and residual) frame
+    int Kp;
+    OutGeom out;                           // opad: halo of the output (and residual) frame
     int relu, tiles_m, ksplit;
-    unsigned magic_howo, magic_wo;
     int ablate;                            // tuning only (hps_dev_conv_pad_ablate): 1 = no epilogue
 };
 // The 1x1 / stride-s down-sample convolution of a residual block's entry (models/resnet.py:71-72, 184-188) issued by EXTRA WORKGROUPS OF
@@ -76,19 +54,7 @@ static int g_pad_ablate = 0;               // dev library only (hps_dev_conv_pad
 constexpr int g_pad_ablate = 0;            // product library: no process-global switches
 #endif
 
-// offset (floats) of output pixel m, channel 0, in the output frame
-__device__ __forceinline__ unsigned out_pixel_offset(unsigned m, const PadGeom& g) {
-    const unsigned howo = (unsigned)(g.Ho * g.Wo);
-    const unsigned b = fastdiv(m, howo, g.magic_howo), rem = m - b * howo;
-    const unsigned ho = fastdiv(rem, (unsigned)g.Wo, g.magic_wo), wo = rem - ho * g.Wo;
-    return ((b * (g.Ho + 2 * g.opad) + ho + g.opad) * (g.Wo + 2 * g.opad) + wo + g.opad) * (unsigned)g.Cout;
-}
-
-// ST = K-loop stages (LDS buffers per operand).  2: the next chunk's DMA pieces are issued during this chunk's MFMAs (the throughput
-// form: several workgroups per CU cover each other's DMA latency).  3 / 4 (round 5, latency mode: hps_conv2d_bn_act_pad variant 5):
-// two / three chunks ahead -- at batch 1 a 64 x 64 tile's chunk is 16 MFMAs per wave (0.43 us) with ONE workgroup on the CU, and a
-// chunk fetched one ahead arrived ~0.6 us after it was needed: 1.0 us per chunk, 18.3 us for a layer1 convolution of 18 chunks
-// (three stages: 15.3 us).
+// ST = K-loop stages (conv_tile.h k_loop): 2 is the throughput form, 4 the latency mode's (hps_conv2d_bn_act_pad variant 5)
 template <int BM, int BN, int WM, int WN, int ST = 2, bool DOWN = false>
 __global__ __launch_bounds__(256) void conv_pad_kernel(const float* __restrict__ x, const float* __restrict__ wn,
                                                        const float* __restrict__ scale, const float* __restrict__ shift,
@@ -97,9 +63,7 @@ __global__ __launch_bounds__(256) void conv_pad_kernel(const float* __restrict__
                                                        const std::conditional_t<DOWN, DownArgs, NoDown> d) {
     constexpr int WAVES_N = BN / WN;
     constexpr int TM = WM / 32, TN = WN / 32;
-    constexpr int A_LD = BM / 32, B_LD = BN / 32;        // DMA pieces per wave per chunk
     static_assert((BM / WM) * (BN / WN) == 4, "4 waves per workgroup");
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* sA = smem;                                   // [ST][BM][32]
@@ -120,31 +84,10 @@ __global__ __launch_bounds__(256) void conv_pad_kernel(const float* __restrict__
     const int relu = down ? 0 : g.relu;
     const int tile_n = bx / g.tiles_m, tile_m = bx % g.tiles_m;
     const int m0 = tile_m * BM, n0 = tile_n * BN;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int wm0 = (wave / WAVES_N) * WM, wn0 = (wave % WAVES_N) * WN;
-    const int kl = lane >> 5, il = lane & 31;
-    // DMA role of this lane: tile row (32 r + 8 wave + lane / 8), LDS slot lane % 8 <- source quad slot ^ f(row),
-    // f(row) = (row >> 1) & 7 (conv.hip: conflict-free ds_read_b128)
-    const int drow = wave * 8 + (lane >> 3);
-    const int dquad = ((lane & 7) ^ ((drow >> 1) & 7)) * 4;
 
-    unsigned a_off[A_LD], b_off[B_LD];                  // per-lane byte offsets, constant for the whole kernel
-    {
-        const unsigned howo = (unsigned)(g.Ho * g.Wo);
-#pragma unroll
-        for (int r = 0; r < A_LD; ++r) {
-            const unsigned m = (unsigned)(m0 + drow + 32 * r);
-            unsigned o = 0;                              // tile overhang rows read pixel 0 (results discarded)
-            if (m < (unsigned)g.Mtot) {
-                const unsigned b = fastdiv(m, howo, g.magic_howo), rem = m - b * howo;
-                const unsigned ho = fastdiv(rem, (unsigned)g.Wo, g.magic_wo), wo = rem - ho * g.Wo;
-                o = b * g.img_pitch + (ho * g.stride + g.off) * g.row_pitch + (wo * g.stride + g.off) * g.pix_pitch;
-            }
-            a_off[r] = (o + dquad) * 4u;
-        }
-#pragma unroll
-        for (int r = 0; r < B_LD; ++r) b_off[r] = ((unsigned)(n0 + drow + 32 * r) * filter_kp + dquad) * 4u;
-    }
+    const auto off = lane_offsets<BM / 32, BN / 32>(g.in, g.out, filter_kp, m0, n0, lane, wave);   // constant for the whole kernel
 
     f32x16 acc[TM][TN];
 #pragma unroll
@@ -154,141 +97,45 @@ __global__ __launch_bounds__(256) void conv_pad_kernel(const float* __restrict__
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
 
-    // split-K: blockIdx.y owns the chunk range [c_begin, c_end) and writes raw partial sums (summed in slice order by
+    // split-K: blockIdx.y owns the chunk range [c_begin, c_begin + per_split) and writes raw partial sums (summed in slice order by
     // splitk_pad_epilogue_kernel: deterministic, no atomics)
     const int chunks_total = filter_kp / PBK;
     const int per_split = chunks_total / ksplit;
-    const int c_begin = down ? 0 : blockIdx.y * per_split, c_end = c_begin + per_split;
-    // scalar walk over (kh, kw, ci0): the A base pointer advances by 32 floats per chunk and jumps at tap / row ends
+    const int c_begin = down ? 0 : blockIdx.y * per_split;
+    // where the (kh, kw, ci0) walk starts
     const int cpt = g.cin_k / PBK;
-    int ci = c_begin % cpt, tap = c_begin / cpt;
+    const int ci = c_begin % cpt, tap = c_begin / cpt;
     int kw = tap % g.kw, kh = tap / g.kw;
     if constexpr (DOWN) {
         if (down) { kh = d.tap_kh; kw = d.tap_kw; }      // the one tap the 1x1 window reads; ci = 0 .. cpt - 1
     }
-    const float* a_src = x + (size_t)kh * g.row_pitch + (size_t)kw * g.pix_pitch + (size_t)ci * PBK;
-    const float* b_src = wn + (size_t)c_begin * PBK;
-    const int tap_jump = g.pix_pitch - g.cin_k + PBK;                    // from the last chunk of a tap to the next tap
-    const int row_jump = g.row_pitch - (g.kw - 1) * g.pix_pitch - g.cin_k + PBK;   // ... to the next filter row
-
-    const unsigned lds_a = (unsigned)(size_t)(lptr_t)(sA + wave * 8 * PBK);
-    const unsigned lds_b = (unsigned)(size_t)(lptr_t)(sB + wave * 8 * PBK);
-    auto advance = [&]() {                               // source pointers of the next chunk (scalar code)
-        b_src += PBK;
-        if (++ci < cpt) a_src += PBK;
-        else {
-            ci = 0;
-            if (++kw < g.kw) a_src += tap_jump;
-            else { kw = 0; a_src += row_jump; }
-        }
-    };
-    auto dma_chunk = [&](int buf) {
-        const unsigned la = __builtin_amdgcn_readfirstlane(lds_a + buf * BM * PBK * 4);
-        const unsigned lb = __builtin_amdgcn_readfirstlane(lds_b + buf * BN * PBK * 4);
-#pragma unroll
-        for (int r = 0; r < A_LD; ++r) lds_dma16_sv(a_off[r], a_src, la + r * 32 * PBK * 4);
-#pragma unroll
-        for (int r = 0; r < B_LD; ++r) lds_dma16_sv(b_off[r], b_src, lb + r * 32 * PBK * 4);
-        advance();
-    };
-    // one piece of the chunk whose sources are (pa_src, pb_src): piece p < A_LD is an A piece, the rest B pieces
-    auto dma_piece = [&](int p, const float* pa_src, const float* pb_src, unsigned la, unsigned lb) {
-        if (p < A_LD) lds_dma16_sv(a_off[p < A_LD ? p : 0], pa_src, la + p * 32 * PBK * 4);
-        else if (p < A_LD + B_LD) lds_dma16_sv(b_off[p >= A_LD && p < A_LD + B_LD ? p - A_LD : 0], pb_src, lb + (p - A_LD) * 32 * PBK * 4);
-    };
-
-    const int fsw = (il >> 1) & 7;                       // f(row) of the fragment rows this lane reads
+    TapWalk walk{x + (size_t)kh * g.in.row_pitch + (size_t)kw * g.in.pix_pitch + (size_t)ci * PBK, wn + (size_t)c_begin * PBK,
+                 ci, kw, cpt, g.kw,
+                 g.in.pix_pitch - g.cin_k + PBK, g.in.row_pitch - (g.kw - 1) * g.in.pix_pitch - g.cin_k + PBK};
 #ifdef HPS_DEV_BUILD
     if (g.ablate >= 2) {       // experiment: de-phase the workgroups that share a CU (ablate - 1 sleeps of 3.4 us for the second slot)
         if (((blockIdx.x >> 8) & 1) && blockIdx.x < 512)
             for (int i = 0; i < (g.ablate - 1) * 1; ++i) __builtin_amdgcn_s_sleep(127);
     }
-#endif
-    dma_chunk(0);
-#pragma unroll
-    for (int q = 1; q < ST - 1; ++q)
-        if (c_begin + q < c_end) dma_chunk(q);
-    for (int c = c_begin; c < c_end; ++c) {
-        const int buf = ST == 2 ? (c - c_begin) & 1 : (c - c_begin) % ST;
-        // this wave's pieces of chunk c have landed; with more than two stages the pieces of up to ST - 2 younger chunks, issued after
-        // them (A_LD + B_LD per chunk), may still be in flight
-        {
-            const int younger = min(ST - 2, c_end - 1 - c);
-            if (ST >= 4 && younger >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (A_LD + B_LD)) : "memory");
-            else if (ST >= 3 && younger >= 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(A_LD + B_LD) : "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        __syncthreads();                                     // ... everyone's have, and the buffer refilled below is no longer being read
-        // The next chunk's DMA pieces are issued ONE PER FOUR MFMAs, not in a burst after the barrier: every 1 KiB piece costs the
-        // SIMD 36-57 cycles that no other wave's MFMAs cover (tools/mfma_dma_overlap.hip: the loop skeleton runs at 139.4 TF/s with
-        // the burst and 143.0 spread); on the stem 0.906 -> 0.888 ms (tests/dev/stem_ablate.py, mode 3 = burst).
-        static_assert(A_LD + B_LD <= (PBK / 8) * TM * TN, "one DMA piece per accumulator block of a chunk at most");
-#ifdef HPS_DEV_BUILD
-        const bool spread = g.ablate != 3 || ST != 2;    // hps_dev_conv_pad_ablate(3): the earlier burst (two-stage form only)
+    const bool spread = g.ablate != 3 || ST != 2;        // hps_dev_conv_pad_ablate(3): the earlier burst (two-stage form only)
 #else
-        constexpr bool spread = true;
+    constexpr bool spread = true;
 #endif
-        const bool more = c + (ST - 1) < c_end;          // the chunk fetched during this one: c + 1 (two stages), c + 2, c + 3
-        const float* na_src = a_src;
-        const float* nb_src = b_src;
-        const int nbuf = ST == 2 ? buf ^ 1 : (c - c_begin + ST - 1) % ST;
-        const unsigned nla = __builtin_amdgcn_readfirstlane(lds_a + nbuf * BM * PBK * 4);
-        const unsigned nlb = __builtin_amdgcn_readfirstlane(lds_b + nbuf * BN * PBK * 4);
-        if (more) {
-            if (spread) advance();
-            else dma_chunk(buf ^ 1);
-        }
-        const float* pa = sA + (size_t)buf * BM * PBK + (wm0 + il) * PBK;
-        const float* pb = sB + (size_t)buf * BN * PBK + (wn0 + il) * PBK;
-        // Fragments are double-buffered by hand: group gq + 1 is requested before the MFMAs of group gq are issued (the
-        // sched_barriers keep hipcc from sinking the reads to their uses -- left alone it reloads the same 16 registers after
-        // the group's last MFMA and waits out the LDS round trip in front of the next group).
-        float4 a4[2][TM], b4[2][TN];
-        auto load_frags = [&](int gq, int s) {
-            const int slot = ((2 * gq + kl) ^ fsw) * 4;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) a4[s][i] = *reinterpret_cast<const float4*>(pa + i * 32 * PBK + slot);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) b4[s][j] = *reinterpret_cast<const float4*>(pb + j * 32 * PBK + slot);
-        };
-        load_frags(0, 0);
-#pragma unroll
-        for (int gq = 0; gq < PBK / 8; ++gq) {
-            if (gq + 1 < PBK / 8) load_frags(gq + 1, (gq + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-            // k order inside the group is x, y, z, w for every accumulator (same summation order as conv.hip)
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4[gq & 1][j].x, a4[gq & 1][i].x, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4[gq & 1][j].y, a4[gq & 1][i].y, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4[gq & 1][j].z, a4[gq & 1][i].z, acc[i][j], 0, 0, 0);
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(b4[gq & 1][j].w, a4[gq & 1][i].w, acc[i][j], 0, 0, 0);
-                    if (spread && more) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        dma_piece((gq * TM + i) * TN + j, na_src, nb_src, nla, nlb);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
+    k_loop<BM, BN, WM, WN, ST>(acc, off, walk, per_split, sA, sB, spread);
 
-    // The filter fragment is the MFMA's row operand and the pixel fragment its column operand (products commute, the
-    // k order is unchanged), so a lane ends up with ONE pixel (column = lane & 31) and, per register quad q, four
-    // consecutive output channels: row = (r & 3) + 8 q + 4 (lane >> 5)  ->  128-bit accesses along Cout.
+    // a lane holds ONE pixel (column = lane & 31) and, per register quad q, four consecutive output channels (conv_tile.h)
     if (ksplit > 1) {
-        float* dst = partial + (size_t)blockIdx.y * g.Mtot * g.Cout;
+        const int kl = lane >> 5, il = lane & 31;
+        float* dst = partial + (size_t)blockIdx.y * g.out.Mtot * g.out.Cout;
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const int m = m0 + wm0 + i * 32 + il;
-            if (m >= g.Mtot) continue;
+            if (m >= g.out.Mtot) continue;
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
-                    *reinterpret_cast<float4*>(dst + (size_t)m * g.Cout + n0 + wn0 + j * 32 + 8 * q + 4 * kl) =
+                    *reinterpret_cast<float4*>(dst + (size_t)m * g.out.Cout + n0 + wn0 + j * 32 + 8 * q + 4 * kl) =
                         make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
         }
         return;
@@ -306,78 +153,63 @@ __global__ __launch_bounds__(256) void conv_pad_kernel(const float* __restrict__
         return;
     }
 
-    // Epilogue: BatchNorm (scale, shift), residual, ReLU, stored as whole pixel rows.  Each wave transposes its 32-pixel
-    // sub-tiles through a private LDS patch [32][WN + 4] (the +4 keeps both the 128-bit writes -- 16 lanes = 16 pixels,
-    // bank step 4 -- and the row reads conflict free), then WN/4 consecutive lanes own one pixel's WN channels: residual
-    // loads and output stores are 16 bytes per lane, WN*4 contiguous bytes per pixel (64 stores -> 16 per wave).
-    constexpr int EP = WN + 4;                 // patch pitch (floats)
-    constexpr int LPP = WN / 4;                // lanes per pixel
-    constexpr int PPI = 64 / LPP;              // pixels per wave instruction
-    static_assert(4 * 32 * EP <= ST * (BM + BN) * PBK, "the epilogue patches fit in the K-loop buffers");
+    // Epilogue: BatchNorm (scale, shift), residual, ReLU, stored as whole pixel rows through the wave's patch (conv_tile.h)
+    typedef PatchShape<WN> P;
+    static_assert(4 * 32 * P::EP <= ST * (BM + BN) * PBK, "the epilogue patches fit in the K-loop buffers");
     __syncthreads();                           // every wave is done with the K-loop buffers
-    float* patch = smem + wave * 32 * EP;
-    const int c4 = (lane % LPP) * 4;
+    float* patch = wave_patch<WN>(smem, wave);
+    const int c4 = patch_channel<WN>(lane);
     const int co = n0 + wn0 + c4;
     const float4 sc = *reinterpret_cast<const float4*>(scale + co), sh = *reinterpret_cast<const float4*>(shift + co);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-                *reinterpret_cast<float4*>(patch + il * EP + j * 32 + 8 * q + 4 * kl) =
-                    make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-        // wave-private patch: no barrier, the LDS queue is in order per wave
-        constexpr int U = 32 / PPI;
-        if (m0 + BM <= g.Mtot) {
+        to_patch<WN>(patch, acc[i], lane);
+        if (m0 + BM <= g.out.Mtot) {
             // Full tile (every tile of the benchmark shapes): no per-pixel guards, so this is straight-line code -- all patch rows
             // are requested before the first is used and the stores follow back to back.  (With the guards hipcc put every
             // row's read, wait and store into a block of its own: 16 exposed LDS round trips per sub-tile.)
-            unsigned po[U];
-            float4 a[U];
+            unsigned po[P::U];
+            float4 a[P::U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                po[u] = out_pixel_offset((unsigned)(m0 + wm0 + i * 32 + u * PPI + lane / LPP), g) + (unsigned)co;
-                a[u] = *reinterpret_cast<const float4*>(patch + (u * PPI + lane / LPP) * EP + c4);
+            for (int u = 0; u < P::U; ++u) {
+                po[u] = out_pixel_offset((unsigned)(m0 + wm0 + i * 32 + u * P::PPI + lane / P::LPP), g.out) + (unsigned)co;
+                a[u] = *reinterpret_cast<const float4*>(patch + (u * P::PPI + lane / P::LPP) * P::EP + c4);
             }
             if (residual) {
-                float4 res[U];
+                float4 res[P::U];
 #pragma unroll
-                for (int u = 0; u < U; ++u) res[u] = *reinterpret_cast<const float4*>(residual + po[u]);
+                for (int u = 0; u < P::U; ++u) res[u] = *reinterpret_cast<const float4*>(residual + po[u]);
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    float4 v = make_float4(a[u].x * sc.x + sh.x + res[u].x, a[u].y * sc.y + sh.y + res[u].y,
-                                           a[u].z * sc.z + sh.z + res[u].z, a[u].w * sc.w + sh.w + res[u].w);
+                for (int u = 0; u < P::U; ++u) {
+                    float4 v = make_float4(a[u].x * sc.x + sh.x + res[u].x, a[u].y * sc.y + sh.y + res[u].y, a[u].z * sc.z + sh.z + res[u].z, a[u].w * sc.w + sh.w + res[u].w);
                     if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     *reinterpret_cast<float4*>(y + po[u]) = v;
                 }
             } else {
 #pragma unroll
-                for (int u = 0; u < U; ++u) {
+                for (int u = 0; u < P::U; ++u) {
                     // "+ 0" as in the guarded path (residual absent = zero addend): the same bits
-                    float4 v = make_float4(a[u].x * sc.x + sh.x + 0.f, a[u].y * sc.y + sh.y + 0.f, a[u].z * sc.z + sh.z + 0.f,
-                                           a[u].w * sc.w + sh.w + 0.f);
+                    float4 v = make_float4(a[u].x * sc.x + sh.x + 0.f, a[u].y * sc.y + sh.y + 0.f, a[u].z * sc.z + sh.z + 0.f, a[u].w * sc.w + sh.w + 0.f);
                     if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
                     *reinterpret_cast<float4*>(y + po[u]) = v;
                 }
             }
             continue;
         }
-        unsigned po[U];
-        bool live[U];
-        float4 res[U];
+        unsigned po[P::U];
+        bool live[P::U];
+        float4 res[P::U];
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const int m = m0 + wm0 + i * 32 + u * PPI + lane / LPP;
-            live[u] = m < g.Mtot;
-            po[u] = live[u] ? out_pixel_offset((unsigned)m, g) + (unsigned)co : 0u;
+        for (int u = 0; u < P::U; ++u) {
+            const int m = m0 + wm0 + i * 32 + u * P::PPI + lane / P::LPP;
+            live[u] = m < g.out.Mtot;
+            po[u] = live[u] ? out_pixel_offset((unsigned)m, g.out) + (unsigned)co : 0u;
             res[u] = (residual && live[u]) ? *reinterpret_cast<const float4*>(residual + po[u]) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const float4 a = *reinterpret_cast<const float4*>(patch + (u * PPI + lane / LPP) * EP + c4);
-            float4 v = make_float4(a.x * sc.x + sh.x + res[u].x, a.y * sc.y + sh.y + res[u].y, a.z * sc.z + sh.z + res[u].z,
-                                   a.w * sc.w + sh.w + res[u].w);
+        for (int u = 0; u < P::U; ++u) {
+            const float4 a = *reinterpret_cast<const float4*>(patch + (u * P::PPI + lane / P::LPP) * P::EP + c4);
+            float4 v = make_float4(a.x * sc.x + sh.x + res[u].x, a.y * sc.y + sh.y + res[u].y, a.z * sc.z + sh.z + res[u].z, a.w * sc.w + sh.w + res[u].w);
             if (relu) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
             if (live[u]) *reinterpret_cast<float4*>(y + po[u]) = v;
         }
@@ -410,8 +242,8 @@ __global__ __launch_bounds__(256) void splitk_pad_epilogue_kernel(const float* _
         acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
     }
     const unsigned e = (unsigned)(i * 4);
-    const unsigned m = e / (unsigned)g.Cout, co = e - m * g.Cout;
-    const size_t o = (size_t)out_pixel_offset(m, g) + co;
+    const unsigned m = e / (unsigned)g.out.Cout, co = e - m * g.out.Cout;
+    const size_t o = (size_t)out_pixel_offset(m, g.out) + co;
     const float4 sc = *reinterpret_cast<const float4*>(scale + co), sh = *reinterpret_cast<const float4*>(shift + co);
     float4 v = make_float4(acc.x * sc.x + sh.x, acc.y * sc.y + sh.y, acc.z * sc.z + sh.z, acc.w * sc.w + sh.w);
     if (residual) {
@@ -533,8 +365,8 @@ __global__ __launch_bounds__(256) void avgpool_pad_kernel(const float* __restric
 template <int BM, int BN, int WM, int WN, int ST = 2>
 static int launch_conv_pad(const float* x, const float* wn, const float* scale, const float* shift, const float* residual,
                            float* y, float* partial, PadGeom g, hipStream_t s, const DownArgs* down = nullptr) {
-    g.tiles_m = ceil_div(g.Mtot, BM);
-    const int tiles_n = g.Cout / BN;
+    g.tiles_m = ceil_div(g.out.Mtot, BM);
+    const int tiles_n = g.out.Cout / BN;
     const size_t lds = (size_t)ST * (BM + BN) * PBK * sizeof(float);
     if (down) {                 // the block's 1x1 down-sample rides in the same launch: as many workgroups again, one K slice
         DownArgs d = *down;
@@ -550,7 +382,7 @@ static int launch_conv_pad(const float* x, const float* wn, const float* scale, 
                            shift, residual, y, partial, g, NoDown());
     }
     if (g.ksplit > 1) {
-        const long total4 = (long)g.Mtot * g.Cout / 4;
+        const long total4 = (long)g.out.Mtot * g.out.Cout / 4;
         hipLaunchKernelGGL(splitk_pad_epilogue_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, partial, scale,
                            shift, residual, y, total4, g);
     }
@@ -571,25 +403,21 @@ static int conv_pad_entry(const float* x, const float* wn, const float* scale, c
     if (B <= 0) return HPS_OK;
     PadGeom g;
     const int Hp = H + 2 * ipad, Wp = W + 2 * ipad;
-    g.pix_pitch = Cin;
-    g.row_pitch = Wp * Cin;
-    g.img_pitch = Hp * g.row_pitch;
-    g.stride = stride;
-    g.off = ipad - pad;
-    g.Ho = (H + 2 * pad - KH) / stride + 1;
-    g.Wo = (W + 2 * pad - KW) / stride + 1;
-    g.Mtot = B * g.Ho * g.Wo;
-    g.Cout = Cout;
-    g.opad = opad;
+    g.in.pix_pitch = Cin;
+    g.in.row_pitch = Wp * Cin;
+    g.in.img_pitch = Hp * g.in.row_pitch;
+    g.in.stride = stride;
+    g.in.off = ipad - pad;
+    set_out_geom(g.out, B, (H + 2 * pad - KH) / stride + 1, (W + 2 * pad - KW) / stride + 1, Cout, opad);
     g.relu = relu;
     g.ksplit = ksplit < 1 ? 1 : ksplit;
     if (row_mode) {
         // a filter row = KW * Cin contiguous floats, rounded up to the chunk; the DMA needs 16-byte aligned windows
         g.cin_k = ceil_div(KW * Cin, PBK) * PBK;
         g.kw = 1;
-        if ((stride * Cin) % 4 != 0 || g.row_pitch % 4 != 0 || (g.off * Cin) % 4 != 0)
+        if ((stride * Cin) % 4 != 0 || g.in.row_pitch % 4 != 0 || (g.in.off * Cin) % 4 != 0)
             return bad_arg("hps_conv2d_bn_act_pad: row mode needs 16-byte aligned window starts");
-        if (((g.Wo - 1) * stride + g.off) * Cin + g.cin_k > g.row_pitch)
+        if (((g.out.Wo - 1) * stride + g.in.off) * Cin + g.cin_k > g.in.row_pitch)
             return bad_arg("hps_conv2d_bn_act_pad: row mode window overruns the padded row");
     } else {
         if (Cin % PBK != 0) return bad_arg("hps_conv2d_bn_act_pad: Cin % 32 == 0 required (or row mode)");
@@ -597,24 +425,16 @@ static int conv_pad_entry(const float* x, const float* wn, const float* scale, c
         g.kw = KW;
     }
     g.Kp = KH * g.kw * g.cin_k;
-    if ((size_t)B * g.img_pitch * 4 >= 0xffffffffull || (size_t)Cout * g.Kp * 4 >= 0xffffffffull)
+    if (!fits_lane_offsets((size_t)B * g.in.img_pitch) || !fits_lane_offsets((size_t)Cout * g.Kp))
         return bad_arg("hps_conv2d_bn_act_pad: tensor exceeds the 32-bit lane offsets");
     if ((g.Kp / PBK) % g.ksplit != 0 || (g.ksplit > 1 && !splitk_ws)) return bad_arg("hps_conv2d_bn_act_pad: ksplit");
-    g.magic_howo = div_magic((unsigned)(g.Ho * g.Wo));
-    g.magic_wo = div_magic((unsigned)g.Wo);
     g.ablate = g_pad_ablate;
     hipStream_t s = (hipStream_t)stream;
     // split-K runs on the 128-row tiles unless the caller asks for the 64 x 64 ones (variants 3 / 5: the latency mode, where a
     // single image's 8 x 8 ... 32 x 32 maps leave half of a 128-row tile empty and a quarter as many workgroups on the chip);
     // the summation order of an output does not depend on the tile shape: the same bits
     if (g.ksplit > 1 && variant != 3 && variant != 5) variant = Cout % 128 == 0 ? 1 : 2;
-    if (variant == 0) {
-        // same rule as hps_conv2d_bn_act_v3 (measured per layer): largest tile that still gives every CU a workgroup
-        if (Cout % 128 == 0 && ((long)g.Mtot / 128) * (Cout / 128) >= 256) variant = 1;
-        else if (Cout == 64 && g.Mtot / 256 >= 512) variant = 4;
-        else variant = 3;
-    }
-    if (variant == 1 && Cout % 128 != 0) variant = 2;
+    variant = resolve_tile_variant(variant, g.out.Mtot, Cout);
     if (down) {
         // the tile shapes a residual block's entry convolution takes (Cout >= 128): 128 x 128, 128 x 64, 64 x 64 (two- and four-stage)
         switch (variant) {

@@ -101,7 +101,8 @@ def _frame(t_nhwc, pad):
     # B, H, Cin, Cout, k, stride, pad, ipad -- every layer type of ResNet-18, ragged tiles, Wo % 4 != 0, split-K, the row-mode stem
     (2, 64, 64, 64, 3, 1, 1, 1), (2, 64, 64, 128, 3, 2, 1, 1), (2, 64, 64, 128, 1, 2, 0, 1), (64, 8, 512, 512, 3, 1, 1, 1),
     (3, 16, 256, 256, 3, 1, 1, 1), (1, 8, 512, 512, 3, 1, 1, 1), (2, 9, 128, 256, 3, 2, 1, 1), (3, 14, 64, 64, 3, 1, 1, 2),
-    (2, 30, 18, 64, 7, 2, 3, 3), (1, 256, 18, 64, 7, 2, 3, 3), (2, 12, 4, 64, 7, 2, 3, 3)])
+    (2, 30, 18, 64, 7, 2, 3, 3), (1, 256, 18, 64, 7, 2, 3, 3), (2, 12, 4, 64, 7, 2, 3, 3),
+    (1, 5, 32, 64, 1, 1, 0, 1)])      # a K loop of ONE chunk on a partial tile: the stage prologue and the vmcnt ladder have nothing to prefetch
 def test_padded_conv_kernel(cfg, dev):
     """csrc/conv_pad.hip against torch's convolution and, bit for bit, against the conv.hip kernel it replaces
     (same K order and summation order; the row-mode stem has its own K order and is held to the tolerance only)."""
