@@ -142,6 +142,10 @@ _PROTOTYPES = {
     "hps_png_bound": [_I, _I, _I],
     "hps_png_segment_rows": [_I, _I, _I],
     "hps_png_encode": [_P, _P],
+    "hps_sizeof_jpeg_header": [],
+    "hps_sizeof_jpeg_decode_args": [],
+    "hps_jpeg_parse": [_P, _c.c_int64, _P],
+    "hps_jpeg_decode": [_P, _P],
     "hps_sizeof_c16_problem": [],
     "hps_conv2d_bn_act_c16": [_P, _I, _P],
     "hps_hrnet_pack_input": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -276,6 +280,34 @@ class PngImage(_c.Structure):
 class PngEncodeArgs(_c.Structure):
     """include/hps.h: hps_png_encode_args (struct_bytes = ctypes.sizeof(PngEncodeArgs); the library rejects any other value)."""
     _fields_ = [("struct_bytes", _I), ("num_images", _I), ("image", PngImage * PNG_MAX_IMAGES)]
+
+
+class JpegHuff(_c.Structure):
+    """include/hps.h: hps_jpeg_huff."""
+    _fields_ = [("bits", _c.c_uint8 * 16), ("vals", _c.c_uint8 * 256)]
+
+
+class JpegHeader(_c.Structure):
+    """include/hps.h: hps_jpeg_header (struct_bytes = ctypes.sizeof(JpegHeader); written by hps_jpeg_parse)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "width", "height", "ncomp", "hs", "vs", "restart_interval", "scan_offset", "scan_length",
+                                  "num_blocks", "num_intervals", "file_bytes")] + [
+        ("quant", (_c.c_uint8 * 64) * 3), ("dc", JpegHuff * 3), ("ac", JpegHuff * 3)]
+
+
+class JpegImage(_c.Structure):
+    """include/hps.h: hps_jpeg_image."""
+    _fields_ = [(n, _P) for n in ("data", "header", "header_dev", "out", "workspace")]
+
+
+class JpegDecodeArgs(_c.Structure):
+    """include/hps.h: hps_jpeg_decode_args (struct_bytes = ctypes.sizeof(JpegDecodeArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "num_images", "mode", "subseq_bits")] + [("status", _P), ("rounds", _P),
+                                                                                         ("image", JpegImage * 64)]
+
+
+JPEG_MAX_DIM, JPEG_MAX_SCAN_BYTES, JPEG_NOT_FOR_DEVICE = 8192, 1 << 22, 1
+JPEG_RGB, JPEG_NATIVE, JPEG_GREY = 0, 1, 2
+JPEG_ST_MARKERS, JPEG_ST_CODE, JPEG_ST_OVERRUN, JPEG_ST_SHORT = 1, 2, 4, 8
 
 
 class C16Problem(_c.Structure):
@@ -577,6 +609,13 @@ WS_RENDER = 14
 WS_SILHOUETTE = 15
 WS_TRAIN_METRICS = 16
 WS_PNG = 17
+WS_JPEG = 18
+
+
+def jpeg_ws_dims(h):
+    """include/hps.h: HPS_WS_JPEG_D1 / _D2 -- hps_query_workspace's three dimensions for a parsed header."""
+    return (int(h.scan_length), int(h.width) + (int(h.height) << 32),
+            int(h.ncomp) + (int(h.hs) << 8) + (int(h.vs) << 16) + (int(h.restart_interval) << 32))
 
 
 def silhouette_d2(num_faces, W):

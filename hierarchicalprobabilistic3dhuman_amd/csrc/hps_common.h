@@ -32,6 +32,8 @@ int64_t silhouette_ws_bytes(int64_t M, int64_t Nd, int64_t F, int64_t W);
 int64_t train_metrics_ws_bytes(int64_t B);
 // bytes of one picture's hps_png_encode workspace, -1 outside the supported range (csrc/png.hip; HPS_WS_PNG)
 int64_t png_ws_bytes(int64_t H, int64_t W, int64_t C);
+// bytes of one file's hps_jpeg_decode workspace, -1 outside the supported range (csrc/jpeg.hip; HPS_WS_JPEG)
+int64_t jpeg_ws_bytes(int64_t scan_length, int64_t d1, int64_t d2);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

@@ -14,6 +14,10 @@ dataset inside a ``Subset``; the training and evaluation loops use both.  The fu
 Images are decoded with PIL (OpenCV is not a dependency).  PNG decoding is exact; a JPEG may differ from ``cv2.imread`` in the last bit
 of some pixels (different IDCT / upsampling defaults of the two libjpeg builds).  The resize and the warp restate OpenCV's integer
 arithmetic from its sources and have not been run against OpenCV itself.
+
+With ``decode="device"`` a dataset leaves baseline JPEG files undecoded in ``__getitem__`` (``encode_or_decode_rgb``: the file's bytes
+and parsed header) and ``prepare_batch`` decodes them in one call on the device (jpeg.DeviceJpegDecoder, ``DeviceImages``), to the
+bytes PIL gives; every other file is decoded by PIL as before.
 """
 import ctypes
 
@@ -51,11 +55,71 @@ def preparer(dataset):
     return None
 
 
+def check_decoded(dataset):
+    """``dataset.check_decoded()``, looking through ``torch.utils.data.Subset``: raises HpsError naming every JPEG file that a
+    decode="device" dataset found corrupt or truncated since the last check.  It waits for the batches prepared so far, so the loops
+    call it where the host waits anyway (the epoch's read-back, the end of an evaluation); a dataset without it is left alone."""
+    while dataset is not None:
+        fn = getattr(dataset, "check_decoded", None)
+        if fn is not None:
+            return fn()
+        dataset = getattr(dataset, "dataset", None)
+
+
 def decode_rgb(path):
     """(H, W, 3) uint8 tensor, what cv2.cvtColor(cv2.imread(path), cv2.COLOR_BGR2RGB) holds (module docstring: JPEG)."""
     from PIL import Image
     with Image.open(path) as im:
         return torch.from_numpy(np.array(im.convert("RGB"), dtype=np.uint8))
+
+
+def check_decode_arg(decode):
+    """The datasets' ``decode`` argument: "host" (PIL, in ``__getitem__``) or "device" (jpeg.DeviceJpegDecoder, in ``prepare_batch``)."""
+    if decode not in ("host", "device"):
+        raise ValueError("decode is 'host' or 'device', not %r" % (decode,))
+    return decode
+
+
+def encode_or_decode_rgb(path):
+    """What ``__getitem__`` returns for an image under decode="device": the file as a jpeg.EncodedJpeg (bytes and parsed header, no
+    pixels) when it is a JPEG the device decodes, else ``decode_rgb(path)`` as before (PNG, progressive, CMYK, ...).  Host only."""
+    from . import jpeg
+    encoded = jpeg.encode_file(path, "rgb")
+    return encoded if encoded is not None else decode_rgb(path)
+
+
+class DeviceImages:
+    """The images of a batch under decode="device": the decoded ones are staged with the batch's other host data as before, the
+    encoded ones go up as file bytes and are decoded in ONE DeviceJpegDecoder call.  ``host_arrays(images)`` is what to add to the
+    batch's staging upload, ``resolve(images, staged)`` the (H,W,3) uint8 device tensor of every image, in order; the decoder's status
+    words of earlier batches are looked at on the way, without waiting (``check`` waits)."""
+
+    def __init__(self):
+        self.decoder = None
+
+    @staticmethod
+    def is_encoded(image):
+        from . import jpeg
+        return isinstance(image, jpeg.EncodedJpeg)
+
+    def host_arrays(self, images):
+        return [as_numpy(im) for im in images if not self.is_encoded(im)]
+
+    def resolve(self, images, staged):
+        encoded = [im for im in images if self.is_encoded(im)]
+        decoded = []
+        if encoded:
+            if self.decoder is None:
+                from . import jpeg
+                self.decoder = jpeg.DeviceJpegDecoder()
+            self.decoder.check(wait=False)
+            decoded = self.decoder.decode(encoded, mode="rgb")
+        staged, decoded = iter(staged), iter(decoded)
+        return [next(decoded) if self.is_encoded(im) else next(staged) for im in images]
+
+    def check(self):
+        if self.decoder is not None:
+            self.decoder.check()
 
 
 def decode_grey(path):

@@ -154,7 +154,7 @@ def flipped_target_rotmats(target_pose, flip=None):
 
 def _evaluate_loop(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male, smpl_model_female, edge_detect_model, device,
                    loader, staged, tracker, metrics, want_samples, N, flip, fnames, poses, shapes, cams, sample_on_cpu, run_seed, frame0,
-                   reduce_across_ranks, save_per_frame_metrics, save_path, silhouette_renderer, prepare=None, **_unused):
+                   reduce_across_ranks, save_per_frame_metrics, save_path, silhouette_renderer, prepare=None, eval_dataset=None, **_unused):
     frame = frame0
     want_joints2d, want_silhouettes = any("joints2D" in m for m in metrics), any("silhouette" in m for m in metrics)
     wh = pose_shape_cfg.DATA.PROXY_REP_SIZE
@@ -274,6 +274,7 @@ def _evaluate_loop(pose_shape_model, pose_shape_cfg, smpl_model, smpl_model_male
                 cams.append(cam.cpu().numpy())
             frame += B
     check_sampling()              # every launch since the last check is recorded (sampling_utils._pending): no batch is missed
+    data_layer.check_decoded(eval_dataset)          # decode="device": corrupt or truncated JPEG files, by name
     if reduce_across_ranks:
         tracker.reduce_across_ranks()
     final = tracker.compute_final_metrics(verbose=sharding.world_info()[0] == 0)

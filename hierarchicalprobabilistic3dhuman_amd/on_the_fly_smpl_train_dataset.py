@@ -6,6 +6,8 @@ reference.  ``__getitem__`` makes the reference's random draws in the reference'
 for the texture, one for the background -- after the same torch.manual_seed the choices are the reference's) and decodes the background;
 it converts nothing to float.  ``prepare_batch`` turns a list of items into the reference's batch on the device: textures gathered from
 uint8 banks that are uploaded once, backgrounds resized by cv2.resize's arithmetic, both as float32 in [0, 1].
+``decode="device"`` (default "host": nothing changes) leaves the JPEG decoding to ``prepare_batch`` too: ``__getitem__`` returns the
+file's bytes (data_layer.encode_or_decode_rgb) and the batch's files are decoded in one call on the device, to the same bytes.
 """
 import os
 
@@ -17,7 +19,7 @@ from . import data_layer
 
 
 class OnTheFlySMPLTrainDataset(Dataset):
-    def __init__(self, poses_path, textures_path, backgrounds_dir_path, params_from='all', grey_tex_prob=0.05, img_wh=256):
+    def __init__(self, poses_path, textures_path, backgrounds_dir_path, params_from='all', grey_tex_prob=0.05, img_wh=256, decode="host"):
         assert params_from in ['all', 'h36m', 'up3d', '3dpw', 'amass', 'not_amass']
         data = np.load(poses_path)
         fnames, poses = data['fnames'], data['poses']
@@ -44,18 +46,20 @@ class OnTheFlySMPLTrainDataset(Dataset):
         self.backgrounds_paths = sorted([os.path.join(backgrounds_dir_path, f) for f in os.listdir(backgrounds_dir_path)
                                          if f.endswith('.jpg')])
         self.img_wh = img_wh
-        self._banks = self._staging = None
+        self.decode = data_layer.check_decode_arg(decode)
+        self._banks = self._staging = self._images = None
 
     def __getstate__(self):                      # a worker process gets the host data only
         state = dict(self.__dict__)
-        state['_banks'] = state['_staging'] = None
+        state['_banks'] = state['_staging'] = state['_images'] = None
         return state
 
     def __len__(self):
         return len(self.poses)
 
     def __getitem__(self, index):
-        """{'pose': (72,) float32, 'texture_choice': (is_grey, tex_idx), 'background': (H, W, 3) uint8 of the file's own size}."""
+        """{'pose': (72,) float32, 'texture_choice': (is_grey, tex_idx), 'background': (H, W, 3) uint8 of the file's own size}; under
+        decode="device" the background is a jpeg.EncodedJpeg where the device can decode the file."""
         if torch.is_tensor(index):
             index = index.tolist()
         if isinstance(index, (list, tuple)):
@@ -66,7 +70,14 @@ class OnTheFlySMPLTrainDataset(Dataset):
         tex_idx = torch.randint(low=0, high=len(bank), size=(1,)).item()
         bg_idx = torch.randint(low=0, high=len(self.backgrounds_paths), size=(1,)).item()
         return {'pose': pose, 'texture_choice': (bool(is_grey), int(tex_idx)),
-                'background': data_layer.decode_rgb(self.backgrounds_paths[bg_idx])}
+                'background': (data_layer.decode_rgb if self.decode == "host" else data_layer.encode_or_decode_rgb)(self.backgrounds_paths[bg_idx])}
+
+    def check_decoded(self):
+        """decode="device": raise HpsError naming the files of the batches prepared so far whose JPEG stream was corrupt or truncated
+        (their pixels are unspecified).  ``prepare_batch`` only looks at batches that have already finished; this waits for all of
+        them, so call it where the host waits anyway -- the training and evaluation loops do, at the epoch's read-back and at the end."""
+        if self._images is not None:
+            self._images.check()
 
     def prepare_batch(self, items):
         """-> {'pose': (B,72), 'texture': (B,1200,800,3), 'background': (B,3,img_wh,img_wh)}, float32 on the current device."""
@@ -76,9 +87,11 @@ class OnTheFlySMPLTrainDataset(Dataset):
             self._banks = (torch.from_numpy(np.ascontiguousarray(self.grey_textures)).to(dev),
                            torch.from_numpy(np.ascontiguousarray(self.nongrey_textures)).to(dev))
             self._staging = data_layer.BatchStaging()
-        B = len(items)
+        if self._images is None:
+            self._images = data_layer.DeviceImages()
         poses = np.stack([data_layer.as_numpy(it['pose']) for it in items]).astype(np.float32, copy=False)
-        staged = self._staging.upload([poses] + [data_layer.as_numpy(it['background']) for it in items])
+        backgrounds = [it['background'] for it in items]
+        staged = self._staging.upload([poses] + self._images.host_arrays(backgrounds))
         texture = data_layer.texture_gather(self._banks[0], self._banks[1], [it['texture_choice'] for it in items])
-        background = data_layer.resize_bilinear_u8(staged[1:1 + B], (self.img_wh, self.img_wh))
+        background = data_layer.resize_bilinear_u8(self._images.resolve(backgrounds, staged[1:]), (self.img_wh, self.img_wh))
         return {'pose': staged[0].clone(), 'texture': texture, 'background': background}

@@ -648,7 +648,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                                      edge_detect_model, device, image_dir, save_dir, object_detect_model=None,
                                      joints2Dvisib_threshold=0.75, visualise_wh=512, visualise_uncropped=True,
                                      visualise_samples=False, proxy_rep_fn=None, num_samples=50, batch_size=1,
-                                     result_fn=None, vis_renderer=None, batched_front_end=None, png_encoder="pil"):
+                                     result_fn=None, vis_renderer=None, batched_front_end=None, png_encoder="pil",
+                                     image_decoder="pil"):
     """Signature of predict/predict_poseMF_shapeGaussian_net.py:19-32 plus keyword extensions.
 
     Called exactly like the reference (run_predict.py:77-89) it runs the reference's front end (:61-100) on the injected
@@ -679,7 +680,15 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     can -- no ``proxy_rep_fn``, a GPU device, ``hrnet_model`` a pose2D_hrnet.PoseHighResolutionNet and an ``edge_detect_model`` with
     ``edge_map_into`` -- and the per-image route of predict_hrnet / image_utils otherwise; True demands it (HpsError when it cannot be
     used), False forbids it.
+
+    ``image_decoder``: "pil" (the default) reads every photograph on the host (``load_rgb_image``); "device" hands the batched front
+    end the files themselves: the JPEG files of a group that are in the device profile (include/hps.h: baseline, 4:4:4 / 4:2:2 / 4:2:0
+    or greyscale) go up as file bytes and are decoded in one call (jpeg.DeviceJpegDecoder) to the bytes PIL gives, straight into the
+    uint8 tensors the front end and the uncropped picture read; every other file takes the host route as before.  It needs the batched
+    front end (HpsError where the per-image route is taken); anything else is a ValueError.
     """
+    if image_decoder not in ("pil", "device"):
+        raise ValueError("image_decoder is 'pil' or 'device', not %r" % (image_decoder,))
     if png_encoder not in ("pil", "device", "device-dynamic"):
         raise ValueError("png_encoder is 'pil', 'device' or 'device-dynamic', not %r" % (png_encoder,))
     on_device = png_encoder != "pil"
@@ -693,6 +702,16 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                                         joints2Dvisib_threshold, device)
     if device.type == "cuda":
         torch.cuda.set_device(device)              # libhps launches on the current device's current stream
+    jpeg_decoder = None
+    if image_decoder == "device":
+        if batched is None:
+            raise _capi.HpsError("image_decoder='device' decodes a group's photographs for the batched front end, but the per-image "
+                                 "route is taken here (%s); use image_decoder='pil'"
+                                 % ("a proxy_rep_fn replaces the whole front end" if proxy_rep_fn is not None else
+                                    "batched_front_end=False" if batched_front_end is False else
+                                    "it needs a GPU, a pose2D_hrnet.PoseHighResolutionNet and an edge detector with edge_map_into"))
+        from .jpeg import DeviceJpegDecoder, encode_file
+        jpeg_decoder = DeviceJpegDecoder()
     pose_shape_model.eval()
     image_fnames = sorted(f for f in os.listdir(image_dir) if f.lower().endswith((".png", ".jpg", ".jpeg", ".npy")))
     if proxy_rep_fn is None and batched is None:
@@ -721,7 +740,17 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
 
     def front_batch(names):
         """The batched front end on one group: its (B,18,D,D) proxy representations; per-image views for the pictures are kept."""
-        out = batched([load_rgb_image(os.path.join(image_dir, n)) for n in names], with_image=vis is not None and visualise_uncropped)
+        paths = [os.path.join(image_dir, n) for n in names]
+        if jpeg_decoder is None:
+            images = [load_rgb_image(p) for p in paths]
+        else:                                            # the group's device-profile JPEGs in one decode call, the rest on the host
+            images = [encode_file(p) if p.lower().endswith((".jpg", ".jpeg")) else None for p in paths]
+            picks = [i for i, im in enumerate(images) if im is not None]
+            jpeg_decoder.check(wait=False)               # earlier groups, as far as they have finished
+            for i, t in zip(picks, jpeg_decoder.decode([images[i] for i in picks]) if picks else []):
+                images[i] = t
+            images = [im if im is not None else load_rgb_image(p) for im, p in zip(images, paths)]
+        out = batched(images, with_image=vis is not None and visualise_uncropped)
         if vis is not None:
             for b, n in enumerate(names):
                 extras[n] = {"proxy_rep": out["proxy_rep"][b:b + 1], "cropped_rgb": out["cropped_rgb"][b:b + 1],
@@ -808,6 +837,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         finish_pending(pending)
         graphed.check_sampling()
         check_sampling()
+        if jpeg_decoder is not None:
+            jpeg_decoder.check()
         if writer is not None:
             writer.close()
         return
@@ -844,6 +875,8 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                 check_sampling()                         # synchronises; with a result_fn the check is deferred (below) so the loop stays pipelined
             deliver(names, res)
         check_sampling()
+        if jpeg_decoder is not None:
+            jpeg_decoder.check()
     torch.cuda.current_stream().wait_stream(pipe.caller_stream(batch_size))
     if writer is not None:
         writer.close()

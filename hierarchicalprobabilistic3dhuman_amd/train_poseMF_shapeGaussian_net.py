@@ -247,6 +247,8 @@ def train_poseMF_shapeGaussian_net(pose_shape_model,
 
             metrics_tracker.update_per_epoch()                  # the epoch's one read-back; raises for an image that had no body pixel
             sampling_utils.check_sampling()
+            for checked in (train_dataset, val_dataset):        # decode="device": corrupt or truncated JPEG files of the epoch, by name
+                data_layer.check_decoded(checked)
 
             if metrics_tracker.determine_save_model_weights_this_epoch(save_val_metrics, best_epoch_val_metrics):
                 for metric in save_val_metrics:

@@ -109,11 +109,16 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_SILHOUETTE  (d0 = M, d1 = DensePose vertices, d2 = HPS_WS_SILHOUETTE_D2(faces, W))  workspace of hps_silhouette_iou
  *   HPS_WS_TRAIN_METRICS (d0 = B)                               workspace of hps_train_metrics_update
  *   HPS_WS_PNG         (d0 = H, d1 = W, d2 = C)                 a picture's workspace of hps_png_encode (-1 outside the supported range)
+ *   HPS_WS_JPEG        (d0 = scan_length, d1 = HPS_WS_JPEG_D1(width, height), d2 = HPS_WS_JPEG_D2(ncomp, hs, vs, restart_interval))
+ *                                                               a file's workspace of hps_jpeg_decode, good for every subseq_bits
+ *                                                               (-1 outside the supported range)
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
        HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
        HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13, HPS_WS_RENDER = 14,
-       HPS_WS_SILHOUETTE = 15, HPS_WS_TRAIN_METRICS = 16, HPS_WS_PNG = 17 };
+       HPS_WS_SILHOUETTE = 15, HPS_WS_TRAIN_METRICS = 16, HPS_WS_PNG = 17, HPS_WS_JPEG = 18 };
+#define HPS_WS_JPEG_D1(width, height) ((int64_t)(width) + ((int64_t)(height) << 32))
+#define HPS_WS_JPEG_D2(ncomp, hs, vs, restart_interval) ((int64_t)(ncomp) + ((int64_t)(hs) << 8) + ((int64_t)(vs) << 16) + ((int64_t)(restart_interval) << 32))
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -1470,6 +1475,123 @@ int hps_sizeof_png_encode_args(void);
 int64_t hps_png_bound(int H, int W, int C);
 int hps_png_segment_rows(int H, int W, int C);
 int hps_png_encode(const hps_png_encode_args* args, hps_stream_t stream);
+
+/* hps_jpeg_parse / hps_jpeg_decode  (no reference counterpart: the reference reads its images with cv2.imread on the host;
+ * csrc/jpeg.hip, csrc/jpeg_decode.h)  the bytes of baseline JPEG files to the pixels PIL (libjpeg's defaults: islow IDCT, fancy
+ * upsampling) gives, byte for byte, so that only the compressed file crosses to the device.
+ *
+ * hps_jpeg_parse is a HOST function: it walks the markers of data[0 .. length) and returns
+ *   HPS_OK             *header is filled; the file is in the device profile;
+ *   HPS_JPEG_NOT_FOR_DEVICE  a well-formed file outside the profile (hps_last_error says which rule); decode it on the host;
+ *   HPS_E_BADARG       null pointer, or a MALFORMED file (hps_last_error names the place): no SOI, a segment length running past the
+ *                      file, the file ending before a scan, a scan selecting a Huffman or quantisation table that was never
+ *                      defined or a component the frame does not have, a Huffman table whose counts overflow its code space or whose
+ *                      symbols run past its segment, a DC symbol above 15, table slots above 3, sampling factors outside 1..4.
+ * The device profile: SOF0, or SOF1 with 8-bit samples (Huffman coded); one component, or three treated as YCbCr as libjpeg would
+ * (JFIF; else Adobe transform 1; else component ids other than 'R','G','B'); luma sampling 1x1, 2x1 or 2x2 with both chroma
+ * components 1x1 (4:4:4, 4:2:2, 4:2:0; a single component counts as 1x1 whatever it declares); ONE scan over all components in
+ * frame order with Ss = 0, Se = 63, Ah = Al = 0, followed by EOI or the end of the file (a truncated file parses, and decodes with
+ * a non-zero status); 8-bit quantisation tables; any DHT and DRI; width and height in [1, HPS_JPEG_MAX_DIM]; a file below 2^28
+ * bytes with at most HPS_JPEG_MAX_SCAN_BYTES (4 MiB) of entropy-coded data (larger scans go to the host: see the worst case below).  APPn (EXIF orientation included, as Image.open ignores it), COM and unknown segments are skipped.  Outside it: progressive,
+ * lossless, arithmetic, differential (SOF2..SOF15), 12-bit, two or four components (CMYK / YCCK), Adobe transform 0 or RGB ids,
+ * other sampling factors, several scans, 16-bit tables, FF fill bytes inside the scan.
+ * The header resolves the table slots: quant / dc / ac are indexed by COMPONENT; quant is in natural (row-major) order.
+ * scan_offset / scan_length delimit the entropy-coded bytes inside the file.
+ *
+ * hps_jpeg_decode decodes 1 .. HPS_FRONTEND_MAX_IMAGES files of different sizes, samplings and tables in FIVE launches, whatever the
+ * files hold; no host synchronisation, no atomics, nothing allocated, bitwise repeatable, and a file's pixels do not depend on what
+ * else is in the call.  Per file: data (DEVICE) the whole file's bytes, at least header->file_bytes of them; header (HOST) what
+ * hps_jpeg_parse wrote; header_dev (DEVICE, 4-byte aligned) a copy of *header, of which the kernels read the TABLES only (the sizes
+ * travel by value from the host copy, so a bad device copy cannot move an address); out (DEVICE) the pixels; workspace (DEVICE,
+ * 16-byte aligned) hps_query_workspace(HPS_WS_JPEG, scan_length, HPS_WS_JPEG_D1(width, height), HPS_WS_JPEG_D2(ncomp, hs, vs,
+ * restart_interval)) bytes; buffers of different files do not overlap.  status (DEVICE, num_images int32) receives per file 0 or a
+ * mask of HPS_JPEG_ST_*; rounds (DEVICE, num_images int32, or NULL) the rounds its synchronisation loop took.
+ * mode HPS_JPEG_RGB: out is (H, W, 3) RGB, a one-component file's value repeated (PIL's convert("RGB")); HPS_JPEG_NATIVE: (H, W) for
+ * a one-component file, (H, W, 3) for a three-component one; HPS_JPEG_GREY: (H, W), one-component files only.
+ *
+ * Entropy decoding is parallel INSIDE a file, restart markers or not (the self-synchronising scheme of Klein and Wiseman, as
+ * Weissenberger and Schmidt run it on GPUs, with the fixed-point loop inside one launch):
+ *   1. one workgroup per file removes the FF 00 stuffing and the RSTn markers and records where each restart interval starts;
+ *   2. each interval's bits are cut into subsequences of subseq_bits (0: the default 512; else a power of two in [128, 4096]).  Lane s
+ *      starts at its subsequence's first bit in the state (start of an MCU, block 0, coefficient 0), decodes symbols until the first
+ *      symbol boundary at or behind its end and records (bit, block of the MCU, coefficient, blocks completed).  Every later round
+ *      restarts each lane from its predecessor's record; a lane whose entry did not change keeps its record.  The loop ends with the
+ *      first round that changes no record, or after as many rounds as the file has subsequences -- then lane k's entry is the
+ *      sequential decoder's by induction.  One workgroup of 1024 lanes per file strides over its subsequences, so the loop needs no
+ *      synchronisation between workgroups and the launch count does not depend on the content;
+ *   3. in the same launch a segmented prefix sum of the blocks completed gives every lane its first block -- the first lane of
+ *      interval i owns block i * restart_interval * blocks per MCU -- and a last pass writes the coefficients, DC as differences;
+ *   4. a segmented prefix sum per component and restart interval makes the DC values absolute.
+ * Every bit read is bounded by the interval's end: bits behind it read as zero; every coefficient write is bounded by the interval's
+ * block range.  A corrupt or truncated stream gives a non-zero status and unspecified pixels, and touches nothing outside that
+ * file's out and workspace.
+ * WORST CASE.  Files from an encoder synchronise within tens of rounds (profiles/jpeg_decode_time.txt: 5 to 21).  The loop's bound is
+ * the subsequence count n = 8 scan_length / subseq_bits, and a stream CRAFTED never to synchronise makes every round decode every
+ * subsequence again: n^2 subseq_bits / 2 symbol steps at most, on one workgroup -- at the 4 MiB limit and 512 bits about 10^12, a launch
+ * of minutes.  HPS_JPEG_MAX_SCAN_BYTES keeps it there; hand files of unknown origin to the host decoder.
+ *
+ * The arithmetic (libjpeg's defaults).  Dequantise with the table in natural order.  IDCT jidctint.c "islow", CONST_BITS 13,
+ * PASS1_BITS 2, columns then rows: even part z1 = (c2 + c6) 4433, t2 = z1 - c6 15137, t3 = z1 + c2 6270, t0 = (c0 + c4) << 13,
+ * t1 = (c0 - c4) << 13, t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2; odd part on (c7, c5, c3, c1): z1 = c7 + c1,
+ * z2 = c5 + c3, z3 = c7 + c3, z4 = c5 + c1, z5 = (z3 + z4) 9633, the four times 2446, 16819, 25172, 12299, z1..z4 times -7373,
+ * -20995, -16069, -3196, z3 += z5, z4 += z5, o0 = c7' + z1 + z3, o1 = c5' + z2 + z4, o2 = c3' + z2 + z3, o3 = c1' + z1 + z4;
+ * outputs (t10 +- o3, t11 +- o2, t12 +- o1, t13 +- o0).  Column pass: (x + 2^10) >> 11; row pass: (x + 2^17) >> 18, + 128, clamped to
+ * 0..255; arithmetic shifts of signed 32-bit values.  Chroma of ceil(W / hs) x ceil(H / vs) real samples, "fancy" upsampling with
+ * the last real row and column standing in for anything beyond them and row -1 equal to row 0: h2v1 out[2i] = (3 s[i] + s[i-1] +
+ * 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2; h2v2 with t[i] = 3 near[i] + far[i] (the upper output row takes the row above as
+ * far, the lower the row below): out[2i] = (3 t[i] + t[i-1] + 8) >> 4, out[2i+1] = (3 t[i] + t[i+1] + 7) >> 4.  Colour, each clamped:
+ * R = Y + ((91881 (Cr - 128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16),
+ * G = Y + ((-22554 (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16).
+ *
+ * HPS_E_BADARG before any launch: null pointers, a wrong struct_bytes (of the arguments or of a header), num_images outside
+ * [1, HPS_FRONTEND_MAX_IMAGES], a subseq_bits that is neither 0 nor a power of two in [128, 4096], an unknown mode, a header whose
+ * fields are outside the profile above or inconsistent (num_blocks, num_intervals, scan_offset + scan_length > file_bytes), a
+ * misaligned workspace or header_dev.  HPS_E_UNSUPPORTED: HPS_JPEG_GREY asked of a three-component file. */
+#define HPS_JPEG_MAX_DIM 8192
+#define HPS_JPEG_MAX_SCAN_BYTES (1 << 22)
+#define HPS_JPEG_NOT_FOR_DEVICE 1
+#define HPS_JPEG_RGB 0
+#define HPS_JPEG_NATIVE 1
+#define HPS_JPEG_GREY 2
+#define HPS_JPEG_ST_MARKERS 1    /* more RSTn markers than restart intervals, or one out of sequence */
+#define HPS_JPEG_ST_CODE 2       /* a bit pattern that is no code of its table, or a zero run past coefficient 63 */
+#define HPS_JPEG_ST_OVERRUN 4    /* a symbol reached behind the end of its restart interval (zero bits were read) */
+#define HPS_JPEG_ST_SHORT 8      /* a restart interval ended before its blocks were complete */
+typedef struct hps_jpeg_huff {
+    uint8_t bits[16];                                          /* codes of length 1..16 */
+    uint8_t vals[256];                                         /* the symbols in code order */
+} hps_jpeg_huff;
+typedef struct hps_jpeg_header {
+    int struct_bytes;
+    int width, height, ncomp;                                  /* ncomp 1 or 3 */
+    int hs, vs;                                                /* luma sampling: 1x1, 2x1 or 2x2 (chroma is 1x1) */
+    int restart_interval;                                      /* MCUs, 0: none */
+    int scan_offset, scan_length;                              /* the entropy-coded bytes inside the file */
+    int num_blocks, num_intervals;                             /* 8x8 blocks in the scan; restart intervals (>= 1) */
+    int file_bytes;
+    uint8_t quant[3][64];                                      /* per component, natural order */
+    hps_jpeg_huff dc[3], ac[3];                                /* per component */
+} hps_jpeg_header;
+typedef struct hps_jpeg_image {
+    const uint8_t* data;                                       /* DEVICE (file_bytes) */
+    const hps_jpeg_header* header;                             /* HOST */
+    const hps_jpeg_header* header_dev;                         /* DEVICE copy of *header */
+    uint8_t* out;                                              /* DEVICE (H, W) or (H, W, 3) */
+    void* workspace;                                           /* DEVICE */
+} hps_jpeg_image;
+typedef struct hps_jpeg_decode_args {
+    int struct_bytes;
+    int num_images;
+    int mode;                                                  /* HPS_JPEG_RGB / _NATIVE / _GREY */
+    int subseq_bits;
+    int32_t* status;                                           /* DEVICE (num_images) */
+    int32_t* rounds;                                           /* DEVICE (num_images) or NULL */
+    hps_jpeg_image image[64];                                  /* HPS_FRONTEND_MAX_IMAGES */
+} hps_jpeg_decode_args;
+int hps_sizeof_jpeg_header(void);
+int hps_sizeof_jpeg_decode_args(void);
+int hps_jpeg_parse(const uint8_t* data /* HOST */, int64_t length, hps_jpeg_header* header /* HOST */);
+int hps_jpeg_decode(const hps_jpeg_decode_args* args /* HOST */, hps_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * HRNet 2D keypoint detector, inference forward  (models/pose2D_hrnet.py:426-461)
