@@ -146,6 +146,9 @@ _PROTOTYPES = {
     "hps_sizeof_jpeg_decode_args": [],
     "hps_jpeg_parse": [_P, _c.c_int64, _P],
     "hps_jpeg_decode": [_P, _P],
+    "hps_sizeof_jpeg_encode_args": [],
+    "hps_jpeg_encode_bound": [_I, _I, _I, _I],
+    "hps_jpeg_encode": [_P, _P],
     "hps_sizeof_c16_problem": [],
     "hps_conv2d_bn_act_c16": [_P, _I, _P],
     "hps_hrnet_pack_input": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -174,7 +177,7 @@ _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
              "hps_conv_wgrad_workspace": _c.c_size_t, "hps_conv1x1_wgrad_workspace": _c.c_size_t, "hps_relu_gate_workspace": _c.c_size_t,
              "hps_bn_batch_stats_workspace": _c.c_size_t, "hps_bn_train_backward_sums_workspace": _c.c_size_t,
-             "hps_png_bound": _c.c_int64}
+             "hps_png_bound": _c.c_int64, "hps_jpeg_encode_bound": _c.c_int64}
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)
 
@@ -306,6 +309,20 @@ class JpegDecodeArgs(_c.Structure):
 
 
 JPEG_MAX_DIM, JPEG_MAX_SCAN_BYTES, JPEG_NOT_FOR_DEVICE = 8192, 1 << 22, 1
+JPEG_ENC_MAX_IMAGES = 8
+
+
+class JpegEncImage(_c.Structure):
+    """include/hps.h: hps_jpeg_enc_image."""
+    _fields_ = [("pixels", _P), ("H", _I), ("W", _I), ("C", _I), ("quality", _I), ("sampling", _I), ("reserved", _I), ("out", _P),
+                ("capacity", _c.c_int64), ("length", _P), ("workspace", _P)]
+
+
+class JpegEncodeArgs(_c.Structure):
+    """include/hps.h: hps_jpeg_encode_args (struct_bytes = ctypes.sizeof(JpegEncodeArgs); the library rejects any other value)."""
+    _fields_ = [("struct_bytes", _I), ("num_images", _I), ("image", JpegEncImage * JPEG_ENC_MAX_IMAGES)]
+
+
 JPEG_RGB, JPEG_NATIVE, JPEG_GREY = 0, 1, 2
 JPEG_ST_MARKERS, JPEG_ST_CODE, JPEG_ST_OVERRUN, JPEG_ST_SHORT = 1, 2, 4, 8
 
@@ -610,12 +627,18 @@ WS_SILHOUETTE = 15
 WS_TRAIN_METRICS = 16
 WS_PNG = 17
 WS_JPEG = 18
+WS_JPEG_ENC = 19
 
 
 def jpeg_ws_dims(h):
     """include/hps.h: HPS_WS_JPEG_D1 / _D2 -- hps_query_workspace's three dimensions for a parsed header."""
     return (int(h.scan_length), int(h.width) + (int(h.height) << 32),
             int(h.ncomp) + (int(h.hs) << 8) + (int(h.vs) << 16) + (int(h.restart_interval) << 32))
+
+
+def jpeg_enc_d2(C, sampling):
+    """include/hps.h: HPS_WS_JPEG_ENC_D2 -- channels and sampling in hps_query_workspace's third dimension."""
+    return int(C) + (int(sampling) << 8)
 
 
 def silhouette_d2(num_faces, W):

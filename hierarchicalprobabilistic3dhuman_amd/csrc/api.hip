@@ -54,6 +54,11 @@ extern "C" int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t
             if (n < 0) hps::set_error("hps_query_workspace: HPS_WS_JPEG takes d0 = scan_length <= HPS_JPEG_MAX_SCAN_BYTES, d1 = HPS_WS_JPEG_D1(width, height) with both in [1, %d], d2 = HPS_WS_JPEG_D2(ncomp, hs, vs, restart_interval) of the device profile", HPS_JPEG_MAX_DIM);
             return n;
         }
+        case HPS_WS_JPEG_ENC: {
+            const int64_t n = hps::jpeg_enc_ws_bytes(d0, d1, d2);
+            if (n < 0) hps::set_error("hps_query_workspace: HPS_WS_JPEG_ENC takes d0 = H, d1 = W, both in [1, %d], d2 = HPS_WS_JPEG_ENC_D2(C, sampling) with C in {1, 3} and sampling in 0..2", HPS_JPEG_MAX_DIM);
+            return n;
+        }
         default: hps::set_error("hps_query_workspace: unknown item %d", what); return -1;
     }
 }

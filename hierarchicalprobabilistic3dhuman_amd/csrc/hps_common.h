@@ -34,6 +34,8 @@ int64_t train_metrics_ws_bytes(int64_t B);
 int64_t png_ws_bytes(int64_t H, int64_t W, int64_t C);
 // bytes of one file's hps_jpeg_decode workspace, -1 outside the supported range (csrc/jpeg.hip; HPS_WS_JPEG)
 int64_t jpeg_ws_bytes(int64_t scan_length, int64_t d1, int64_t d2);
+// bytes of one picture's hps_jpeg_encode workspace, -1 outside the supported range (csrc/jpeg_encode.hip; HPS_WS_JPEG_ENC)
+int64_t jpeg_enc_ws_bytes(int64_t H, int64_t W, int64_t d2);
 
 inline int check_launch(const char* what) {
     hipError_t e = hipGetLastError();

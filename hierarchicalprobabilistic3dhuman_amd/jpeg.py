@@ -8,6 +8,13 @@
                               synchronisation; ``check()`` reads the status words where the host waits anyway
 
 Opt-in: the datasets take ``decode="device"``, the predict loop ``image_decoder="device"``.  There is no CPU fallback behind ``decode``.
+
+The other direction (csrc/jpeg_encode.hip, include/hps.h: hps_jpeg_encode): finished pictures to the bytes PIL would save.
+
+    encode_bound(H, W, C, s)  host: a capacity no file exceeds
+    DeviceJpegEncoder.encode  device tensors in, (out, length) device tensors back; four launches per eight pictures, no host
+                              synchronisation (visualise.DeviceJpegWriter goes on to files; the predict loop takes
+                              ``picture_format="jpeg"``)
 """
 import ctypes
 
@@ -223,3 +230,71 @@ class DeviceJpegDecoder:
             raise
         finally:
             self._pending = pending + self._pending
+
+
+SAMPLINGS = {"444": 0, "422": 1, "420": 2}
+
+
+def encode_bound(H, W, C, sampling=2):
+    """include/hps.h: hps_jpeg_encode_bound -- a capacity no JPEG file of an (H, W, C) picture exceeds (a host call).  ``sampling``:
+    0 / "444", 1 / "422", 2 / "420"; ignored for C = 1."""
+    sampling = SAMPLINGS.get(sampling, sampling)
+    n = _capi.load(dev=_capi._use_dev).hps_jpeg_encode_bound(int(H), int(W), int(C), int(sampling))
+    if n < 0:
+        raise _capi.HpsError("hps_jpeg_encode_bound(%d, %d, %d, %d): %s" % (H, W, C, sampling, _last_error()))
+    return int(n)
+
+
+class DeviceJpegEncoder:
+    """Baseline JPEG files made on the current device (include/hps.h: hps_jpeg_encode), for callers who want the bytes there:
+    ``encode`` takes (H, W), (H, W, 1) or (H, W, 3) uint8 device tensors and returns one ``(out, length)`` pair per picture -- ``out``
+    a uint8 tensor of ``encode_bound`` bytes whose first ``length[0]`` (a device int64) are the file, equal to PIL's
+    ``save(format="JPEG", quality=quality, subsampling=...)`` byte for byte.  Only enqueues: four launches per
+    _capi.JPEG_ENC_MAX_IMAGES pictures, no host synchronisation.  The pairs are views of the encoder's own buffers, valid until the
+    next ``encode``; buffers are kept per picture shape.  (visualise.DeviceJpegWriter is the route from pictures to files.)"""
+
+    def __init__(self, quality=95, subsampling="420"):
+        require_gpu("DeviceJpegEncoder")
+        if subsampling not in SAMPLINGS:
+            raise ValueError("subsampling is '444', '422' or '420', not %r" % (subsampling,))
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("quality is 1 .. 100, not %r" % (quality,))
+        self.quality, self.sampling = int(quality), SAMPLINGS[subsampling]
+        self._buffers = {}
+
+    def _buffer(self, key, index):
+        bufs = self._buffers.setdefault(key, [])
+        while len(bufs) <= index:
+            H, W, C = key
+            dev = current_device()
+            ws = _capi.query_workspace(_capi.WS_JPEG_ENC, H, W, _capi.jpeg_enc_d2(C, self.sampling))
+            bufs.append((torch.empty(encode_bound(H, W, C, self.sampling), dtype=torch.uint8, device=dev),
+                         torch.zeros(1, dtype=torch.int64, device=dev), torch.empty(max(16, ws), dtype=torch.uint8, device=dev)))
+        return bufs[index]
+
+    def encode(self, images):
+        images = list(images)
+        results, keep, used = [], [], {}
+        for b0 in range(0, len(images), _capi.JPEG_ENC_MAX_IMAGES):
+            group = images[b0:b0 + _capi.JPEG_ENC_MAX_IMAGES]
+            a = _capi.JpegEncodeArgs()
+            a.struct_bytes, a.num_images = ctypes.sizeof(_capi.JpegEncodeArgs), len(group)
+            for i, image in enumerate(group):
+                _capi.require_device(image, "image")
+                if image.dtype != torch.uint8 or image.dim() not in (2, 3) or (image.dim() == 3 and image.shape[2] not in (1, 3)):
+                    raise _capi.HpsError("a picture is (H, W), (H, W, 1) or (H, W, 3) uint8")
+                image = image.contiguous()
+                if image.data_ptr() % 16:
+                    image = image.clone()
+                keep.append(image)
+                key = (int(image.shape[0]), int(image.shape[1]), int(image.shape[2]) if image.dim() == 3 else 1)
+                used[key] = used.get(key, -1) + 1
+                out, length, ws = self._buffer(key, used[key])
+                im = a.image[i]
+                im.pixels, (im.H, im.W, im.C) = _capi.ptr(image, torch.uint8, "image"), key
+                im.quality, im.sampling = self.quality, self.sampling
+                im.out, im.capacity = _capi.ptr(out, torch.uint8), out.numel()
+                im.length, im.workspace = _capi.ptr(length, torch.int64), _capi.ptr(ws, torch.uint8)
+                results.append((out, length))
+            _capi.call("hps_jpeg_encode", ctypes.addressof(a), _capi.stream())
+        return results

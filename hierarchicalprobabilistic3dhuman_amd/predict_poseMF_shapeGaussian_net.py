@@ -9,8 +9,9 @@ HRNet forward per group); with any other injected
 ``hrnet_model`` / ``object_detect_model`` (the person detector itself is out of scope), the torch crop
 glue of image_utils / predict_hrnet and the Canny / heat-map kernels of SURVEY 8(f)1; ``proxy_rep_fn`` may replace it.  Results go to ``result_fn`` or to .pt files;
 with ``vis_renderer=`` the reference's three pictures per image (:149-333: the eight-panel figure, the body over the original
-photograph, the sample sheet) are written beside them as PNG files by visualise.PredictVisualiser (DESIGN.md section 8 row (f)16;
-section 9 for what stays out: the text labels of the proxy panel, JPEG output).
+photograph, the sample sheet) are written beside them as PNG files -- or, with ``picture_format="jpeg"``, as baseline JPEG files made on the device (row (f)25) --
+by visualise.PredictVisualiser (section 9 for what stays out: the text labels of the proxy panel, the
+reference's reuse of the input's own file name).
 """
 import os
 import weakref
@@ -649,7 +650,7 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
                                      joints2Dvisib_threshold=0.75, visualise_wh=512, visualise_uncropped=True,
                                      visualise_samples=False, proxy_rep_fn=None, num_samples=50, batch_size=1,
                                      result_fn=None, vis_renderer=None, batched_front_end=None, png_encoder="pil",
-                                     image_decoder="pil"):
+                                     image_decoder="pil", picture_format="png", picture_quality=95):
     """Signature of predict/predict_poseMF_shapeGaussian_net.py:19-32 plus keyword extensions.
 
     Called exactly like the reference (run_predict.py:77-89) it runs the reference's front end (:61-100) on the injected
@@ -664,8 +665,10 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     img_wh=visualise_wh (the DensePose asset is not shipped, so the caller brings the renderer, as the evaluation's
     ``silhouette_renderer=``).  With it the reference's pictures (:149-333) are written for every image, beside the .pt / result_fn
     delivery, which does not change: <save_dir>/<stem>.png (the eight-panel figure), <stem>_uncrop.png if ``visualise_uncropped``
-    and <stem>_samples.png if ``visualise_samples``.  Always PNG: the reference reuses the input's file name, which makes a lossy
-    JPEG of a .jpg input.  Without it ``visualise_wh`` / ``visualise_uncropped`` / ``visualise_samples`` have no effect.
+    and <stem>_samples.png if ``visualise_samples``.  PNG by default; ``picture_format="jpeg"`` writes <stem>.jpg, <stem>_uncrop.jpg
+    and <stem>_samples.jpg instead (below).  The reference reuses the input's file name, which makes a lossy JPEG of a .jpg input and
+    a PNG of a .png one; here the format is the caller's choice whatever the input was.  Without ``vis_renderer``, ``visualise_wh`` /
+    ``visualise_uncropped`` / ``visualise_samples`` / ``picture_format`` have no effect.
     A custom ``proxy_rep_fn`` may return a dict with ``proxy_rep`` and, for the pictures, ``cropped_rgb`` (1,3,D,D), ``joints2D``
     (1,K,2) in crop pixels, ``image`` (3,H,W) float in [0,1], ``bbox_centre`` (2,) and ``bbox_wh`` (max(h, w) BBOX_SCALE_FACTOR),
     all on the device; a bare tensor gives black crop panels, no joint discs and no uncropped picture (one warning).
@@ -674,6 +677,12 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     cross to the host); "device-dynamic" is the same route with DevicePngWriter(strategy="dynamic"): a dynamic Huffman code per segment
     and all five filters, for smaller files.  The decoded pixels are the same; the files are not (another compressor).  Anything else is
     a ValueError.
+    ``picture_format``: "png" (the default) as above; "jpeg" makes baseline JPEG files on the device (visualise.DeviceJpegWriter,
+    hps_jpeg_encode: an image's three pictures in one library call) at ``picture_quality`` (1 .. 100, default 95) and 4:2:0 -- libjpeg's
+    settings as cv2.imwrite leaves them, so the files are what the reference writes for a .jpg input as far as the encoder goes; they
+    equal PIL's ``save(quality=picture_quality)`` of the same pixels byte for byte, and have not been run against OpenCV itself.
+    ``png_encoder`` must be left at its default with it (a ValueError naming both otherwise); any other ``picture_format`` is a
+    ValueError.
 
     ``batched_front_end``: None runs the front end of a whole group of ``batch_size`` images on the device with ONE HRNet forward
     (predict_frontend.DevicePredictFrontEnd: box, crops and key points are libhps kernels, no host synchronisation of its own) when it
@@ -691,7 +700,14 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         raise ValueError("image_decoder is 'pil' or 'device', not %r" % (image_decoder,))
     if png_encoder not in ("pil", "device", "device-dynamic"):
         raise ValueError("png_encoder is 'pil', 'device' or 'device-dynamic', not %r" % (png_encoder,))
-    on_device = png_encoder != "pil"
+    if picture_format not in ("png", "jpeg"):
+        raise ValueError("picture_format is 'png' or 'jpeg', not %r" % (picture_format,))
+    if picture_format == "jpeg" and png_encoder != "pil":
+        raise ValueError("picture_format='jpeg' writes no PNG files: leave png_encoder at its default, not %r" % (png_encoder,))
+    if picture_format == "jpeg" and not 1 <= int(picture_quality) <= 100:
+        raise ValueError("picture_quality is 1 .. 100, not %r" % (picture_quality,))
+    on_device = png_encoder != "pil" or picture_format == "jpeg"
+    suffix = ".jpg" if picture_format == "jpeg" else ".png"
     device = torch.device(device)
     batched = None
     if use_batched_front_end(batched_front_end, proxy_rep_fn, device, hrnet_model, edge_detect_model):
@@ -721,9 +737,12 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
     vis = writer = None
     extras = {}                                          # image name -> what the front end kept for the pictures
     if vis_renderer is not None:
-        from .visualise import DevicePngWriter, PngWriter, predict_visualiser
+        from .visualise import DeviceJpegWriter, DevicePngWriter, PngWriter, predict_visualiser
         vis = predict_visualiser(vis_renderer, pose_shape_cfg, visualise_wh)
-        writer = DevicePngWriter(strategy="dynamic" if png_encoder == "device-dynamic" else "fixed") if on_device else PngWriter()
+        if picture_format == "jpeg":
+            writer = DeviceJpegWriter(quality=int(picture_quality), subsampling="420")
+        else:
+            writer = DevicePngWriter(strategy="dynamic" if png_encoder == "device-dynamic" else "fixed") if on_device else PngWriter()
     warned = []
 
     def get_proxy(name):
@@ -767,16 +786,16 @@ def predict_poseMF_shapeGaussian_net(pose_shape_model, pose_shape_cfg, smpl_mode
         crop, joints = ex.get("cropped_rgb"), ex.get("joints2D")
         pictures = []                                    # the device encoder takes an image's pictures in one call
         write = (lambda image, path: pictures.append((image, path))) if on_device else writer.write
-        write(vis.figure(item, crop, proxy.float(), joints), stem + ".png")
+        write(vis.figure(item, crop, proxy.float(), joints), stem + suffix)
         if visualise_uncropped:
             if all(ex.get(k) is not None for k in ("image", "bbox_centre", "bbox_wh")):
-                write(vis.uncropped(ex["image"], ex["bbox_centre"], ex["bbox_wh"]), stem + "_uncrop.png")
+                write(vis.uncropped(ex["image"], ex["bbox_centre"], ex["bbox_wh"]), stem + "_uncrop" + suffix)
             elif not warned:
                 import warnings
                 warned.append(True)
                 warnings.warn("predict: proxy_rep_fn gave no image / bbox_centre / bbox_wh; the uncropped pictures are skipped")
         if visualise_samples:
-            write(vis.samples_figure(item, crop, proxy.float()), stem + "_samples.png")
+            write(vis.samples_figure(item, crop, proxy.float()), stem + "_samples" + suffix)
         if pictures:
             writer.write_many([image for image, _ in pictures], [path for _, path in pictures])
     # The loop is software-pipelined (InferencePipeline): while batch k's head, sampling and meshes run, batch k+1's proxy

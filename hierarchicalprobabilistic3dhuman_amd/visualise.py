@@ -5,14 +5,16 @@ the body projected back onto the original photograph, and the sheet of the eight
 csrc/visualise.hip around ONE hps_render call over all of the picture's views (include/hps.h: hps_vis_views, hps_vis_compose,
 hps_vis_uncrop).  The kernels write finished uint8 RGB images, so only bytes cross to the host; ``PngWriter`` copies them into
 page-locked buffers without blocking and encodes them with PIL on a small thread pool.  ``DevicePngWriter`` is the opt-in beside it:
-the PNG file itself is made on the device (hps_png_encode) and only the compressed bytes cross.
+the PNG file itself is made on the device (hps_png_encode) and only the compressed bytes cross; ``DeviceJpegWriter`` does the same with
+baseline JPEG files (hps_jpeg_encode), byte for byte what PIL would save.
 
 Differences from the reference, all deliberate:
   * the joint numbers and confidences it prints into the proxy-representation panel with cv2.putText (:256-263) are NOT drawn: the
     Hershey font lives in OpenCV, which this package does not depend on.  The red joint discs are;
   * the two T-pose views and the sample sheet take a constant per-vertex colour where the reference uses a constant UV texture (all
     views of a picture share one render call; the routes differ by rounding in the interpolation of a constant only);
-  * pictures are always written as PNG (the reference reuses the input's file name, which makes a lossy JPEG of a ``.jpg`` input);
+  * pictures are written as PNG unless the caller asks for JPEG (the reference reuses the input's file name, which makes a lossy JPEG
+    of a ``.jpg`` input and a PNG of a ``.png`` one; here the format is the caller's choice and the name is <stem>.png / <stem>.jpg);
   * the warp onto the photograph restates cv2.warpAffine's fixed-point arithmetic and has not been run against OpenCV itself.
 There is no matplotlib behind this module: ``jet_lut`` builds the colour map's table from jet's published segments.
 """
@@ -282,15 +284,16 @@ class PngWriter:
         self._pool.shutdown(wait=True)
 
 
-class _PngSlot:
-    """What one picture of DevicePngWriter holds while it is in flight: the file's device buffer (hps_png_bound bytes), the library's
+
+
+class _FileSlot:
+    """What one picture of a device writer holds while it is in flight: the file's device buffer (``bound`` bytes), the library's
     workspace, the device length, and page-locked mirrors of file and length.  Reused by picture shape."""
 
-    def __init__(self, key, device):
-        H, W, C = key
-        self.key, self.bound = key, png_bound(H, W, C)
+    def __init__(self, key, device, bound, workspace_bytes):
+        self.key, self.bound = key, bound
         self.out = torch.empty(self.bound, dtype=torch.uint8, device=device)
-        self.workspace = torch.empty(max(16, _capi.query_workspace(_capi.WS_PNG, H, W, C)), dtype=torch.uint8, device=device)
+        self.workspace = torch.empty(max(16, workspace_bytes), dtype=torch.uint8, device=device)
         self.length = torch.zeros(1, dtype=torch.int64, device=device)
         self.host = torch.empty(self.bound, dtype=torch.uint8).pin_memory()
         self.host_length = torch.zeros(1, dtype=torch.int64).pin_memory()
@@ -312,61 +315,66 @@ def png_segment_rows(H, W, C):
     return int(n)
 
 
-class DevicePngWriter:
-    """PngWriter's interface with the encoder on the device (include/hps.h: hps_png_encode): ``write`` / ``write_many`` launch the
-    library's two kernels on the current stream into reused device buffers and never block the caller; a worker thread waits for the
+class _DeviceFileWriter:
+    """What the device writers share: PngWriter's interface with the encoder on the device.  ``write`` / ``write_many`` launch the
+    library's kernels on the current stream into reused device buffers and never block the caller; a worker thread waits for the
     file's length, copies exactly that many bytes through a reused page-locked buffer on a copy stream of its own, writes
-    ``path + ".part"`` and renames it.  No host thread compresses anything.  ``write_many`` puts up to _capi.PNG_MAX_IMAGES pictures
-    -- one predicted image's three -- into one library call.  At most 2 x workers pictures are in flight; ``drain`` waits for every
-    file and re-raises the first error.  Pictures are (H, W), (H, W, 1) or (H, W, 3) uint8 device tensors.  ``strategy``: "fixed" (the
-    default: deflate's fixed Huffman code, filters Sub and Up) or "dynamic" (one dynamic Huffman code per segment, all five filters:
-    smaller files for more device time) -- hps_png_image.strategy 0 and 1."""
+    ``path + ".part"`` and renames it.  No host thread compresses anything.  At most 2 x workers pictures are in flight; ``drain``
+    waits for every file and re-raises the first error.  Pictures are (H, W), (H, W, 1) or (H, W, 3) uint8 device tensors.
+    A subclass names the library call (ENTRY, ARGS, MAX_IMAGES) and gives a picture's bound, workspace and arguments."""
 
-    STRATEGIES = {"fixed": 0, "dynamic": 1}
+    ENTRY = ARGS = MAX_IMAGES = None
 
-    def __init__(self, workers=4, strategy="fixed"):
-        if strategy not in self.STRATEGIES:
-            raise ValueError("strategy is 'fixed' or 'dynamic', not %r" % (strategy,))
-        self.strategy = strategy
+    def __init__(self, workers=4):
         self.workers = max(1, min(4, int(workers)))
         self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.workers)
         self._free = {}
         self._pending = []
         self._copy_streams = {}
 
+    def _bound(self, H, W, C):
+        raise NotImplementedError
+
+    def _workspace_bytes(self, H, W, C):
+        raise NotImplementedError
+
+    def _describe(self, im):
+        """The entry's own fields of one picture's arguments (strategy; quality and sampling)."""
+        raise NotImplementedError
+
     def _slot(self, key, device):
         free = self._free.setdefault((key, device), [])
-        return free.pop() if free else _PngSlot(key, device)
+        return free.pop() if free else _FileSlot(key, device, self._bound(*key), self._workspace_bytes(*key))
 
     def write(self, image, path):
         self.write_many([image], [path])
 
     def write_many(self, images, paths):
-        if len(images) != len(paths) or not 1 <= len(images) <= _capi.PNG_MAX_IMAGES:
-            raise _capi.HpsError("write_many takes 1 .. %d pictures and as many paths" % _capi.PNG_MAX_IMAGES)
+        if len(images) != len(paths) or not 1 <= len(images) <= self.MAX_IMAGES:
+            raise _capi.HpsError("write_many takes 1 .. %d pictures and as many paths" % self.MAX_IMAGES)
         while len(self._pending) + len(images) > 2 * self.workers and self._pending:
             self._pending.pop(0).result()
-        a = _capi.PngEncodeArgs()
-        a.struct_bytes, a.num_images = ctypes.sizeof(_capi.PngEncodeArgs), len(images)
+        a = self.ARGS()
+        a.struct_bytes, a.num_images = ctypes.sizeof(self.ARGS), len(images)
         slots, keep = [], []
-        for i, image in enumerate(images):
-            _capi.require_device(image, "image")
-            if image.dtype != torch.uint8 or image.dim() not in (2, 3) or (image.dim() == 3 and image.shape[2] not in (1, 3)):
-                raise _capi.HpsError("a picture is (H, W), (H, W, 1) or (H, W, 3) uint8")
-            image = image.contiguous()
-            if image.data_ptr() % 16:
-                image = image.clone()
-            keep.append(image)
-            key = (int(image.shape[0]), int(image.shape[1]), int(image.shape[2]) if image.dim() == 3 else 1)
-            slot = self._slot(key, image.device)
-            slots.append(slot)
-            im = a.image[i]
-            im.pixels, (im.H, im.W, im.C) = _capi.ptr(image, torch.uint8, "image"), key
-            im.strategy = self.STRATEGIES[self.strategy]
-            im.out, im.capacity = _capi.ptr(slot.out, torch.uint8), slot.bound
-            im.length, im.workspace = _capi.ptr(slot.length, torch.int64), _capi.ptr(slot.workspace, torch.uint8)
         try:
-            _capi.call("hps_png_encode", ctypes.addressof(a), _capi.stream())
+            for i, image in enumerate(images):
+                _capi.require_device(image, "image")
+                if image.dtype != torch.uint8 or image.dim() not in (2, 3) or (image.dim() == 3 and image.shape[2] not in (1, 3)):
+                    raise _capi.HpsError("a picture is (H, W), (H, W, 1) or (H, W, 3) uint8")
+                image = image.contiguous()
+                if image.data_ptr() % 16:
+                    image = image.clone()
+                keep.append(image)
+                key = (int(image.shape[0]), int(image.shape[1]), int(image.shape[2]) if image.dim() == 3 else 1)
+                slot = self._slot(key, image.device)
+                slots.append(slot)
+                im = a.image[i]
+                im.pixels, (im.H, im.W, im.C) = _capi.ptr(image, torch.uint8, "image"), key
+                self._describe(im)
+                im.out, im.capacity = _capi.ptr(slot.out, torch.uint8), slot.bound
+                im.length, im.workspace = _capi.ptr(slot.length, torch.int64), _capi.ptr(slot.workspace, torch.uint8)
+            _capi.call(self.ENTRY, ctypes.addressof(a), _capi.stream())
         except Exception:
             for slot in slots:
                 self._free[(slot.key, slot.out.device)].append(slot)
@@ -383,7 +391,7 @@ class DevicePngWriter:
             encoded.synchronize()
             n = int(slot.host_length[0])
             if not 0 < n <= slot.bound:
-                raise _capi.HpsError("hps_png_encode reported a file of %d bytes, the bound is %d" % (n, slot.bound))
+                raise _capi.HpsError("%s reported a file of %d bytes, the bound is %d" % (self.ENTRY, n, slot.bound))
             device = slot.out.device
             with torch.cuda.device(device):
                 stream = self._copy_streams.get(device)
@@ -415,3 +423,57 @@ class DevicePngWriter:
     def close(self):
         self.drain()
         self._pool.shutdown(wait=True)
+
+
+class DevicePngWriter(_DeviceFileWriter):
+    """PngWriter's interface with the encoder on the device (include/hps.h: hps_png_encode; _DeviceFileWriter holds the route): two
+    kernels per call, only the compressed bytes cross.  ``write_many`` puts up to _capi.PNG_MAX_IMAGES pictures -- one predicted
+    image's three -- into one library call.  ``strategy``: "fixed" (the default: deflate's fixed Huffman code, filters Sub and Up) or
+    "dynamic" (one dynamic Huffman code per segment, all five filters: smaller files for more device time) -- hps_png_image.strategy
+    0 and 1."""
+
+    STRATEGIES = {"fixed": 0, "dynamic": 1}
+    ENTRY, ARGS, MAX_IMAGES = "hps_png_encode", _capi.PngEncodeArgs, _capi.PNG_MAX_IMAGES
+
+    def __init__(self, workers=4, strategy="fixed"):
+        if strategy not in self.STRATEGIES:
+            raise ValueError("strategy is 'fixed' or 'dynamic', not %r" % (strategy,))
+        self.strategy = strategy
+        super().__init__(workers)
+
+    def _bound(self, H, W, C):
+        return png_bound(H, W, C)
+
+    def _workspace_bytes(self, H, W, C):
+        return _capi.query_workspace(_capi.WS_PNG, H, W, C)
+
+    def _describe(self, im):
+        im.strategy = self.STRATEGIES[self.strategy]
+
+
+class DeviceJpegWriter(_DeviceFileWriter):
+    """PngWriter's interface writing baseline JPEG files made on the device (include/hps.h: hps_jpeg_encode; _DeviceFileWriter holds
+    the route): four kernels per call, only the compressed bytes cross.  The files equal PIL's ``save(format="JPEG", quality=quality,
+    subsampling=...)`` byte for byte.  ``subsampling``: "444", "422" or "420" (ignored for greyscale pictures); quality 95 and "420"
+    are what cv2.imwrite leaves libjpeg at, but nothing here has been run against OpenCV itself."""
+
+    SUBSAMPLINGS = {"444": 0, "422": 1, "420": 2}
+    ENTRY, ARGS, MAX_IMAGES = "hps_jpeg_encode", _capi.JpegEncodeArgs, _capi.JPEG_ENC_MAX_IMAGES
+
+    def __init__(self, workers=4, quality=95, subsampling="420"):
+        if subsampling not in self.SUBSAMPLINGS:
+            raise ValueError("subsampling is '444', '422' or '420', not %r" % (subsampling,))
+        if not 1 <= int(quality) <= 100:
+            raise ValueError("quality is 1 .. 100, not %r" % (quality,))
+        self.quality, self.subsampling = int(quality), subsampling
+        super().__init__(workers)
+
+    def _bound(self, H, W, C):
+        from .jpeg import encode_bound
+        return encode_bound(H, W, C, self.SUBSAMPLINGS[self.subsampling])
+
+    def _workspace_bytes(self, H, W, C):
+        return _capi.query_workspace(_capi.WS_JPEG_ENC, H, W, _capi.jpeg_enc_d2(C, self.SUBSAMPLINGS[self.subsampling]))
+
+    def _describe(self, im):
+        im.quality, im.sampling = self.quality, self.SUBSAMPLINGS[self.subsampling]

@@ -112,13 +112,16 @@ int hps_stream_destroy(hps_stream_t stream);
  *   HPS_WS_JPEG        (d0 = scan_length, d1 = HPS_WS_JPEG_D1(width, height), d2 = HPS_WS_JPEG_D2(ncomp, hs, vs, restart_interval))
  *                                                               a file's workspace of hps_jpeg_decode, good for every subseq_bits
  *                                                               (-1 outside the supported range)
+ *   HPS_WS_JPEG_ENC    (d0 = H, d1 = W, d2 = HPS_WS_JPEG_ENC_D2(C, sampling))  a picture's workspace of hps_jpeg_encode (-1 outside the
+ *                                                               supported range)
  * Unused dims are ignored.  Returns -1 (and sets hps_last_error) for an unknown `what` or negative dims. */
 enum { HPS_WS_CONV_SPLITK = 0, HPS_WS_SMPL_MP = 1, HPS_WS_SMPL_XT = 2, HPS_WS_SMPL_A = 3, HPS_WS_SMPL_VPOSED = 4,
        HPS_WS_HEAD_F = 5, HPS_WS_HEAD_USV = 6, HPS_WS_MF_LOSS = 8, HPS_WS_SMPL_LBS_BWD = 9, HPS_WS_SMPL_BLEND_BWD = 10,
        HPS_WS_HEAD_LEVELS_BWD = 11, HPS_WS_HEAD_TRUNK_BWD = 12, HPS_WS_SEG_BBOX = 13, HPS_WS_RENDER = 14,
-       HPS_WS_SILHOUETTE = 15, HPS_WS_TRAIN_METRICS = 16, HPS_WS_PNG = 17, HPS_WS_JPEG = 18 };
+       HPS_WS_SILHOUETTE = 15, HPS_WS_TRAIN_METRICS = 16, HPS_WS_PNG = 17, HPS_WS_JPEG = 18, HPS_WS_JPEG_ENC = 19 };
 #define HPS_WS_JPEG_D1(width, height) ((int64_t)(width) + ((int64_t)(height) << 32))
 #define HPS_WS_JPEG_D2(ncomp, hs, vs, restart_interval) ((int64_t)(ncomp) + ((int64_t)(hs) << 8) + ((int64_t)(vs) << 16) + ((int64_t)(restart_interval) << 32))
+#define HPS_WS_JPEG_ENC_D2(C, sampling) ((int64_t)(C) + ((int64_t)(sampling) << 8))
 int64_t hps_query_workspace(int what, int64_t d0, int64_t d1, int64_t d2);
 
 /* ------------------------------------------------------------------------------------------
@@ -1592,6 +1595,83 @@ int hps_sizeof_jpeg_header(void);
 int hps_sizeof_jpeg_decode_args(void);
 int hps_jpeg_parse(const uint8_t* data /* HOST */, int64_t length, hps_jpeg_header* header /* HOST */);
 int hps_jpeg_decode(const hps_jpeg_decode_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_jpeg_encode  (no reference counterpart: the reference hands its pictures to cv2.imwrite, which writes a JPEG for a .jpg name;
+ * csrc/jpeg_encode.hip, csrc/jpeg_encode.h)  finished uint8 pictures to the bytes of complete baseline JPEG files, equal byte for
+ * byte, whole file, to what libjpeg / libjpeg-turbo (PIL's Image.save(format="JPEG", quality=q, subsampling=s)) writes, so that only
+ * the compressed file crosses to the host.  Up to HPS_JPEG_ENC_MAX_IMAGES pictures per call share FOUR launches, whatever their number
+ * and sizes; no atomics on global memory (integer OR and ADD in LDS, on disjoint bits and order-independent sums), nothing allocated,
+ * no host synchronisation, bitwise repeatable, and the bytes of a picture do not depend on what else is in the call.  Picture i:
+ * pixels (H, W, C) contiguous uint8, C = 1 (greyscale) or 3 (RGB); quality in [1, 100]; sampling 0 (4:4:4), 1 (4:2:2) or 2 (4:2:0),
+ * ignored for C = 1; out receives the file and *length (device int64) its length in bytes; capacity, the bytes behind out, must be at
+ * least hps_jpeg_encode_bound(H, W, C, sampling); workspace is hps_query_workspace(HPS_WS_JPEG_ENC, H, W, HPS_WS_JPEG_ENC_D2(C,
+ * sampling)) bytes.  pixels, out and workspace are 16-byte aligned, length 8-byte aligned; the buffers of different pictures do not
+ * overlap.  Nothing is written at or behind out + *length: the file is stored byte by byte and no zeroing reaches past it.
+ *
+ * The file.  Markers in this order: SOI; APP0 "JFIF\0", version 1.01, units 0, density 1 x 1, no thumbnail; one DQT segment per
+ * table (8-bit entries in zig-zag order): luminance (table 0), then chrominance (table 1) when C = 3; SOF0: precision 8, height,
+ * width, components 1..C with sampling factors (luminance hmax x vmax = 1x1, 2x1 or 2x2; chrominance 1x1) and quantisation table
+ * 0 / 1 / 1; one DHT segment each for DC 0, AC 0 and, when C = 3, DC 1, AC 1 -- the tables of T.81 Annex K, K.3 to K.6; SOS over all
+ * components with table selectors 00, 11, 11, then 00 3F 00; the scan; EOI.  No DRI, no restart markers.
+ *   Quantisation tables: Annex K's K.1 and K.2; scale = 5000 / q (integer) for q < 50, else 200 - 2 q; an entry is
+ *     (base scale + 50) / 100 (integer), clamped to 1..255.
+ *   Colour, 16.16 fixed point, arithmetic shifts: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ *     Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16, Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16.
+ *   Planes: a component with factors (h, v) under (hmax, vmax) has ceil(W h / hmax) x ceil(H v / vmax) samples in ceil(. / 8) blocks
+ *     each way.  The full-resolution plane repeats its last column to the right as far as the blocks reach and its last row down to a
+ *     multiple of vmax rows; 2 x 2 down-sampling is (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ... by output column, 2 x 1 is
+ *     (a + b + bias) >> 1 with bias 0, 1, 0, 1, ...; then the DOWN-SAMPLED plane repeats its last row to fill its last block row.
+ *   MCUs in raster order, ceil(W / 8 hmax) x ceil(H / 8 vmax) of them; in an MCU luminance's hmax x vmax blocks row by row, then Cb,
+ *     then Cr.  A luminance block beyond the component's block grid (last MCU column or row under 4:2:2 / 4:2:0) is a DUMMY: every AC
+ *     coefficient zero, DC equal to the DC of the block before it in the MCU.
+ *   DCT: libjpeg's accurate integer forward DCT (jfdctint.c: 13-bit constants, 2 pass-1 bits, rows then columns) on samples - 128;
+ *     its output is the coefficient times 8.  Per 1-D pass over (d0 .. d7): t0 = d0 + d7, t7 = d0 - d7, t1 = d1 + d6, t6 = d1 - d6,
+ *     t2 = d2 + d5, t5 = d2 - d5, t3 = d3 + d4, t4 = d3 - d4, t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2; rows:
+ *     o0 = (t10 + t11) << 2, o4 = (t10 - t11) << 2, the others (x + 2^10) >> 11; columns: o0 = (t10 + t11 + 2) >> 2, o4 likewise, the
+ *     others (x + 2^14) >> 15; z1 = (t12 + t13) 4433, o2 = z1 + t13 6270, o6 = z1 - t12 15137; z1 = t4 + t7, z2 = t5 + t6,
+ *     z3 = t4 + t6, z4 = t5 + t7, z5 = (z3 + z4) 9633, t4..t7 times 2446, 16819, 25172, 12299, z1..z4 times -7373, -20995, -16069,
+ *     -3196, z3 += z5, z4 += z5, o7 = t4 + z1 + z3, o5 = t5 + z2 + z4, o3 = t6 + z2 + z3, o1 = t7 + z1 + z4.
+ *   Quantisation with table entry Q: sign(c) ((|c| + (8 Q >> 1)) / (8 Q)), integer division.
+ *   Entropy code (T.81 F.1.2): DC as the difference to the component's previous block in scan order (dummies included; 0 before the
+ *     first): the code of its size, then size bits (the value, or value - 1 for a negative one, low bits).  AC in zig-zag order:
+ *     run/size symbols with the value's bits, ZRL (F0) for each 16 zeros before a non-zero coefficient, EOB (00) when the block ends in
+ *     zeros.  The last byte is padded with 1 bits; every FF of the scan -- a padded one too -- is followed by 00.
+ * Out of scope: optimised Huffman tables, progressive, restart markers, arithmetic coding, 12-bit, CMYK, EXIF / ICC.
+ *
+ * On the device (csrc/jpeg_encode.hip): workgroups of 192 lanes take 192 consecutive blocks of the scan in every launch.  1. blocks:
+ * one lane per block, samples to quantised zig-zag coefficients, the AC part's bit count; 2. bit counts: the DC difference, the
+ * block's bits, the workgroup's sum; 3. bits: the workgroup's offset is the sum of the sums before it; the blocks' bits go into an LDS
+ * buffer by atomic OR on zeroed words (the bits are disjoint, so the result is exact), the two blocks before the workgroup's first
+ * are coded again so that the byte shared with the neighbour is complete, and the workgroup stores the bytes whose last bit is its
+ * own into the unstuffed stream and counts its FF bytes; 4. file: header, every workgroup's bytes at header + index + FF bytes before,
+ * with the stuffing, EOI and *length.
+ *
+ * HPS_E_BADARG before any launch: null pointers, a wrong struct_bytes, num_images outside [1, HPS_JPEG_ENC_MAX_IMAGES], C other than
+ * 1 and 3, H or W outside [1, 8192] (the decoder's HPS_JPEG_MAX_DIM), quality outside [1, 100], sampling outside 0..2 (C = 3), a
+ * capacity below the bound, pixels / out / workspace not 16-byte aligned, length not 8-byte aligned.
+ * hps_jpeg_encode_bound is a host function; -1 (and hps_last_error) outside the supported range.  It is the header (328 bytes for
+ * C = 1, 623 for C = 3) + 2 ceil(1660 blocks / 8) + 2: a block is at most 22 + 63 * 26 = 1660 bits before stuffing, stuffing at most
+ * doubles a byte (derivation: csrc/jpeg_encode.hip). */
+#define HPS_JPEG_ENC_MAX_IMAGES 8
+typedef struct hps_jpeg_enc_image {
+    const uint8_t* pixels;                                     /* (H, W, C) */
+    int H, W, C;
+    int quality;                                               /* 1 .. 100 */
+    int sampling;                                              /* 0: 4:4:4, 1: 4:2:2, 2: 4:2:0; ignored for C = 1 */
+    int reserved;                                              /* 0 */
+    uint8_t* out;                                              /* (capacity) */
+    int64_t capacity;
+    int64_t* length;                                           /* (1) */
+    void* workspace;
+} hps_jpeg_enc_image;
+typedef struct hps_jpeg_encode_args {
+    int struct_bytes;
+    int num_images;
+    hps_jpeg_enc_image image[HPS_JPEG_ENC_MAX_IMAGES];
+} hps_jpeg_encode_args;
+int hps_sizeof_jpeg_encode_args(void);
+int64_t hps_jpeg_encode_bound(int H, int W, int C, int sampling);
+int hps_jpeg_encode(const hps_jpeg_encode_args* args, hps_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * HRNet 2D keypoint detector, inference forward  (models/pose2D_hrnet.py:426-461)
