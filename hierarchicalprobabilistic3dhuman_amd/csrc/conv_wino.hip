@@ -31,6 +31,10 @@
 // Accuracy: the transforms use only +-1 and +-1/2 -- exact scalings; the result differs from the direct convolution by
 // fp32 rounding of a different summation order (<= 1e-5 of the output scale, tests/test_gpu_net.py).
 // The summation order depends on the layer only, never on the batch size (sharding invariance).
+// The one-run rule: an fp32 VALU instruction and an fp32 MFMA of one SIMD exclude each other and every change between a run of one and
+// a run of the other costs about 40 cycles, so the product's chunk loop issues ONE run of VALU instructions between a chunk's first and
+// last MFMA -- the input transform with the next chunk's address steps inside it -- and its item epilogue branches on what is
+// wave-uniform instead of selecting per value (LEAN at the kernel; docs/wino_item_cost.md; tools/wino_isa_counts.py counts the runs).
 #include <type_traits>
 
 #include "hps_common.h"
@@ -90,6 +94,16 @@ __device__ __forceinline__ unsigned wino_div(unsigned n, unsigned d, unsigned ma
 // as 16-byte vectors (8 + 8 memory instructions per lane instead of 32 + 32 of four bytes).  Every product and every sum is the same:
 // identical bits -- but 2-6 % SLOWER per layer (tests/dev/wino8_check.py): a 16-byte store of 64 lanes touches 32 lines of 128 bytes where
 // a 4-byte store of a lane-per-channel wave writes two whole lines.
+// LEAN (the product: eight waves, lane = channel, AB = 0): the item loop written around the rule that stem_wino.hip keeps -- on gfx950 an fp32 VALU
+// instruction and an fp32 MFMA of one SIMD exclude each other and every change between a run of one and a run of the other costs about 40
+// cycles (tools/mfma_valu_ops.hip), so between the first and the last MFMA of a chunk a wave issues MFMAs, LDS reads and writes, DMA pieces,
+// scalar instructions, waits and ONE run of VALU instructions: the input transform, with every LDS address step of the next chunk inside it
+// (tools/wino_isa_counts.py counts the runs in the compiled code).  The chunk guards are fixed per loop (a steady state that always fetches,
+// a drain that never does), the peeled first chunk starts the accumulators from the MFMA's zero C operand (no zeroing per item), and the
+// epilogue chooses by wave-uniform branches what the earlier one selected per value; residual loads and stores take a scalar 64-bit row
+// address and a 32-bit lane offset.  Every product and every sum is the earlier loop's, in its order: identical bits (tests/test_gpu_wino_item.py).
+// The earlier loop and epilogue stay below for every other AB -- AB = 50 is that form without any ablation (dev library: the reference of the
+// test and the other arm of tests/dev/wino_item_time.py); the profiling ablations are ablations of it.
 template <int AB, bool QUAD, bool W8 = false, bool TR = false>
 __global__ __launch_bounds__(W8 ? 512 : 256, 1) void conv_wino_kernel(const float* __restrict__ x, const float* __restrict__ u,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
@@ -101,8 +115,9 @@ __global__ __launch_bounds__(W8 ? 512 : 256, 1) void conv_wino_kernel(const floa
     float* sB = smem + 2 * W_OPER;
     float* sR = smem + 4 * W_OPER;
     constexpr int ab = AB;
+    constexpr bool LEAN = W8 && !TR && AB == 0;                   // the product's item loop; every other AB keeps the earlier one (see above)
 
-    constexpr int NW = W8 ? 8 : 4;                                // waves per workgroup
+    constexpr int NW = W8 ? 8 : 4;                               // waves per workgroup
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int kl = lane >> 5, il = lane & 31;
     const int pg = W8 ? wave >> 2 : 0;                            // W8: the wave's column pair of positions (j = 2 pg, 2 pg + 1)
@@ -317,6 +332,255 @@ __global__ __launch_bounds__(W8 ? 512 : 256, 1) void conv_wino_kernel(const floa
     size_t out_base;
     locate(item, ct, out_base);
     prologue_dma();
+
+    if constexpr (LEAN) {
+        // ---- the product's item loop (see LEAN at the kernel): the same item, LDS plan, DMA order and sums as the loop below ----
+        typedef __attribute__((address_space(3))) float* lds_f;
+        typedef float f32x4 __attribute__((ext_vector_type(4)));
+        typedef __attribute__((address_space(3))) const f32x4* lds_c4;
+        auto ld1 = [](unsigned addr, int byte_off) { return *(lds_f)(size_t)(addr + (unsigned)byte_off); };       // base register + immediate offset
+        auto ld4 = [](unsigned addr, int byte_off) { return *(lds_c4)(size_t)(addr + (unsigned)byte_off); };
+        const unsigned lds_a0 = (unsigned)(size_t)(lptr_t)(sA);
+        const unsigned fa0 = lds_a0 + (unsigned)(((kl * 64 + wm * 32 + il) * 4 + pg * 2 * 512) * 4);     // fragment slot of the wave's first position, buffer 0
+        const unsigned fb0 = lds_b0 + (unsigned)(((kl * 64 + wn * 32 + il) * 4 + pg * 2 * 512) * 4);
+        const unsigned dst0 = lds_a0 + (unsigned)(a_slot * 4);
+        // LDS addresses of the patch pixels in the ring slot that is read next.  They are carried from chunk to chunk and moved by a
+        // scalar step INSIDE the transform's VALU run (src_pos = the slot offset they hold), so that no address is formed between MFMAs.
+        // 16 x 16 blocks: two row-pair bases, the pixels at immediate offsets; quad: sixteen addresses (halo pixels point at the zero pixel).
+        constexpr int NSRC = QUAD ? 16 : 2;
+        unsigned src[NSRC];
+#pragma unroll
+        for (int n = 0; n < NSRC; ++n)
+            src[n] = lds_r0 + (QUAD ? ((pk_off[n >> 1] >> (16 * (n & 1))) & 0xffffu) * 4u : (unsigned)((w_slot + n * 2 * 18 * WK) * 4));
+        int src_pos = 0;
+        auto step_src = [&](int step) {                       // step: wave-uniform bytes
+#pragma unroll
+            for (int n = 0; n < NSRC; ++n) {
+                src[n] += (unsigned)step;
+                asm volatile("" : "+v"(src[n]));
+            }
+            src_pos += step;
+        };
+        float d1[16];
+        auto read_row = [&](int i) {                          // patch row i (four pixels, the thread's one channel)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                d1[i * 4 + j] = QUAD ? ld1(src[i * 4 + j], 0) : ld1(src[i >> 1], (((i & 1) * 18 + j) * WK) * 4);
+        };
+        auto transform_write = [&](int buf) {                 // V = B^T d B in t_write's order, the 16 positions to sA[buf]
+            unsigned dst = dst0 + (unsigned)(buf * W_OPER * 4);
+            asm volatile("" : "+v"(dst));
+            float t1[16];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                t1[0 * 4 + j] = d1[0 * 4 + j] - d1[2 * 4 + j];
+                t1[1 * 4 + j] = d1[1 * 4 + j] + d1[2 * 4 + j];
+                t1[2 * 4 + j] = d1[2 * 4 + j] - d1[1 * 4 + j];
+                t1[3 * 4 + j] = d1[1 * 4 + j] - d1[3 * 4 + j];
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                ((lds_f)(size_t)dst)[(i * 4 + 0) * 512] = t1[i * 4 + 0] - t1[i * 4 + 2];
+                ((lds_f)(size_t)dst)[(i * 4 + 1) * 512] = t1[i * 4 + 1] + t1[i * 4 + 2];
+                ((lds_f)(size_t)dst)[(i * 4 + 2) * 512] = t1[i * 4 + 2] - t1[i * 4 + 1];
+                ((lds_f)(size_t)dst)[(i * 4 + 3) * 512] = t1[i * 4 + 1] - t1[i * 4 + 3];
+            }
+        };
+        const unsigned f_voff = (unsigned)(lane * 16);
+        typedef std::integral_constant<bool, true> Yes;
+        typedef std::integral_constant<bool, false> No;
+        auto with_flag = [](bool f, auto&& fn) {
+            if (f) fn(Yes());
+            else fn(No());
+        };
+
+        for (;;) {
+            f32x16 acc[8];                                   // acc[2 i + jj] is position 4 i + 2 pg + jj; the first chunk writes it (C operand 0)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's pieces of windows 0..2 and filters 0 (and the last stores)
+            __syncthreads();                                 // ... everyone's
+            step_src(-src_pos);                              // back to ring slot 0
+#pragma unroll
+            for (int i = 0; i < 4; ++i) read_row(i);
+            transform_write(0);
+            step_src(W_RAW * 4);
+            __syncthreads();                                 // operand chunk 0 complete
+            // One chunk.  FIRST (the peeled chunk 0): the accumulators start from the MFMA's zero C operand.  more: chunk c + 1 exists (its
+            // filters are fetched, its patches read and transformed); fetch: so does window c + 3.  The item runs three loops with these
+            // guards fixed at compile time -- the steady state that always fetches, two chunks that only finish chunk c + 1, the last chunk
+            // -- so only the peeled chunk tests them (by scalar branches).  Between the first and the last MFMA the wave issues LDS reads,
+            // DMAs, scalar work -- and ONE run of VALU instructions, the transform in position 5 with every address step in it.
+            auto chunk = [&](auto FIRST_, auto MORE_, auto FETCH_, int c) {
+                constexpr bool FIRST = decltype(FIRST_)::value;
+                const bool more = FIRST ? c + 1 < nchunks : decltype(MORE_)::value, fetch = FIRST ? c + 3 < nchunks : decltype(FETCH_)::value;
+                const int buf = c & 1;
+                unsigned pa = fa0 + (unsigned)(buf * W_OPER * 4), pb = fb0 + (unsigned)(buf * W_OPER * 4);
+                asm volatile("" : "+v"(pa), "+v"(pb));
+                f32x4 a4[2], b4[2];
+                a4[0] = ld4(pa, 0);
+                b4[0] = ld4(pb, 0);
+                const float* u_next = u_item + (size_t)(c + 1) * g.n_ct * W_OPER + wave * FP * 256;
+                const unsigned lds_f_next = lds_b0 + (unsigned)(((c + 1) & 1) * W_OPER * 4 + wave * FP * 1024);
+                const float* x_next = x_item + (c + 3) * WK;
+                const unsigned lds_r_next = lds_r0 + (unsigned)((c % 3) * W_RAW * 4 + wave * 1024);          // window c + 3 takes the slot of chunk c
+#pragma unroll
+                for (int pp = 0; pp < 8; ++pp) {             // pp = 2 i + jj: position 4 i + 2 pg + jj (pa / pb start at position 2 pg)
+                    const int pnext = (4 * ((pp + 1) >> 1) + ((pp + 1) & 1)) * 512;
+                    if (pp < FP) {                           // filters first, then the window: the waits below count on that order
+                        if (more) lds_dma16(f_voff, u_next + pp * 256, lds_f_next + (unsigned)(pp * 1024));
+                    } else if (pp == 5) {
+                        if (fetch) lds_dma16(r_cur[0], x_next, lds_r_next);
+                    } else if (!QUAD && pp == 6) {
+                        if (fetch && r_ok[1]) lds_dma16(r_cur[1], x_next, lds_r_next + (unsigned)(NW * 1024));
+                    }
+                    if (pp < 7) {
+                        a4[(pp + 1) & 1] = ld4(pa, pnext * 4);
+                        b4[(pp + 1) & 1] = ld4(pb, pnext * 4);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    const f32x4 a = a4[pp & 1], b = b4[pp & 1];
+                    if (FIRST) {
+                        const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                        acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, zero, 0, 0, 0);
+                    } else {
+                        acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc[pp], 0, 0, 0);
+                    }
+                    acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc[pp], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (pp < 4) {
+                        if (more) read_row(pp);              // requested in the MIDDLE of a position's MFMAs (see the four-wave loop below)
+                    } else if (pp == 5) {
+                        if (more) {
+                            transform_write((c + 1) & 1);
+                            step_src((c + 2) % 3 == 0 ? -2 * W_RAW * 4 : W_RAW * 4);      // to the slot of chunk c + 2
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc[pp], 0, 0, 0);
+                    acc[pp] = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc[pp], 0, 0, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                if (!more) return;
+                // filters of chunk c + 1 were issued BEFORE window c + 3: with in-order returns, all but the wave's own pieces of that
+                // window (needed one chunk later) must have landed.  Eleven window pieces over eight waves: waves 0-2 move two, the
+                // others one (quad: eight pieces, one each).
+                if (fetch) {
+                    if (!QUAD && wave < 3) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+                    else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+                } else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                __syncthreads();                             // operand chunk c + 1 complete; sA / sB [buf] and ring slot (c + 1) % 3 are free
+            };
+            chunk(Yes(), No(), No(), 0);
+            int c = 1;
+            for (; c + 3 < nchunks; ++c) chunk(No(), Yes(), Yes(), c);
+            for (; c + 1 < nchunks; ++c) chunk(No(), Yes(), No(), c);
+            if (c < nchunks) chunk(No(), No(), No(), c);
+
+            // ---- the next item's first DMAs go out before this item's epilogue (which touches no LDS but the exchange in sA) ----
+            const int cur_ct = ct, cur_nimg = nimg;
+            const size_t cur_out = out_base;
+            const int next = item + gridDim.x;
+            __syncthreads();                                 // everyone is done with this item's LDS
+            if (next < g.items) {
+                locate(next, ct, out_base);
+                prologue_dma();
+            }
+
+            // ---- output transform, BatchNorm, residual, ReLU: the sums of the eight-wave epilogue below, one by one.  Addresses: a
+            //      wave-uniform 64-bit base per output row and four 32-bit lane offsets (one per tile column) ----
+            const int co_w = cur_ct * WC + wn * 32;
+            const size_t wave_base = (QUAD ? cur_out + (size_t)(2 * wm) * g.out_img : cur_out + (size_t)(8 * wm) * g.out_row) + co_w + (size_t)pg * g.Cout;
+            unsigned col_off[4];                             // bytes: the lane's channel (and tile-column half kl; quad: image kl) + tile column
+#pragma unroll
+            for (int j = 0; j < 4; ++j) col_off[j] = (unsigned)(((QUAD ? kl * g.out_img : kl * 8 * g.Cout) + il + 2 * j * g.Cout) * 4);
+            const size_t row_bytes = (size_t)g.out_row * 4;
+            const bool store_ok = !QUAD || 2 * wm + kl < cur_nimg;
+            float2* xch = reinterpret_cast<float2*>(sA);
+            float k0[2][16], k1[2][16];                      // s_0[jj], s_1[jj] of the wave's columns, per tile register r
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+#pragma unroll
+                for (int jj = 0; jj < 2; ++jj) {
+                    k0[jj][r] = acc[0 + jj][r] + acc[2 + jj][r] + acc[4 + jj][r];
+                    k1[jj][r] = acc[2 + jj][r] - acc[4 + jj][r] - acc[6 + jj][r];
+                }
+            const int w4 = wave & 3;
+            typedef __attribute__((address_space(1))) char gchar;          // global address space, stated: it does not survive the pin below otherwise
+            typedef __attribute__((address_space(1))) float gfloat;
+            auto lane_ptr = [&](gchar* row, int j) {         // row + the lane's 32-bit offset, extended HERE: scalar base + 32-bit lane offset
+                asm volatile("" : "+v"(col_off[j]));         // is an addressing mode only when the extension is in sight of the access
+                return (gfloat*)(row + (size_t)col_off[j]);
+            };
+            auto row_ptr = [&](const float* base, int row) { // wave-uniform address of the wave's output row `row`, pinned in scalar registers
+                gchar* p = (gchar*)(base + wave_base) + (size_t)row * row_bytes;
+                asm volatile("" : "+s"(p));
+                return p;
+            };
+            // Everything that depends on the wave's column pair, the residual or the ReLU is wave-uniform: chosen by branches into
+            // specialised code, never by a select per value (each arm has its own s_barrier for the exchange; every wave passes one).
+            with_flag(pg != 0, [&](auto PG1) {
+                constexpr bool P1 = decltype(PG1)::value;
+                constexpr int jx = P1 ? 0 : 1;               // columns 0-1 export column 1, columns 2-3 export column 2 (their jj = 0)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) xch[(((P1 ? 1 : 0) * 16 + r) * 4 + w4) * 64 + lane] = make_float2(k0[jx][r], k1[jx][r]);
+                float sc = 0.f, sh = 0.f;
+                float res[16][2];
+                if (!QUAD) {
+                    sc = scale[co_w + il];
+                    sh = shift[co_w + il];
+                    if (residual) {
+#pragma unroll
+                        for (int row = 0; row < 8; ++row) {
+                            gchar* rp = row_ptr(residual, row);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) res[4 * (row >> 1) + j][row & 1] = *lane_ptr(rp, j);
+                        }
+                    }
+                }
+                __syncthreads();
+                auto finish = [&](auto RES_, auto RELU_) {
+                    constexpr bool RES = decltype(RES_)::value, RELU = decltype(RELU_)::value;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {            // tile row i of the wave's four: registers r = 4 i + j, output rows 2 i + a
+                        float out[4][2];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const int r = 4 * i + j;
+                            const float2 o = xch[(((P1 ? 0 : 1) * 16 + r) * 4 + w4) * 64 + lane];
+                            if (!P1) {                       // y(a, 0) = (s_a[0] + s_a[1]) + s_a[2]
+                                out[j][0] = k0[0][r] + k0[1][r] + o.x;
+                                out[j][1] = k1[0][r] + k1[1][r] + o.y;
+                            } else {                         // y(a, 1) = (s_a[1] - s_a[2]) - s_a[3]
+                                out[j][0] = o.x - k0[0][r] - k0[1][r];
+                                out[j][1] = o.y - k1[0][r] - k1[1][r];
+                            }
+#pragma unroll
+                            for (int a = 0; a < 2; ++a) {
+                                float v = out[j][a];
+                                if (!QUAD) {                 // (the quad geometry writes raw partial sums: wino_launch sets g.raw)
+                                    v = v * sc + sh;
+                                    if (RES) v += res[r][a];
+                                    if (RELU) v = fmaxf(v, 0.0f);
+                                }
+                                out[j][a] = v;
+                            }
+                        }
+#pragma unroll
+                        for (int a = 0; a < 2; ++a) {
+                            gchar* yp = row_ptr(y, 2 * i + a);
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) *lane_ptr(yp, j) = out[j][a];
+                        }
+                    }
+                };
+                if (store_ok) {
+                    if constexpr (QUAD) finish(No(), No());
+                    else with_flag(residual != nullptr, [&](auto RES_) { with_flag(g.relu != 0, [&](auto RELU_) { finish(RES_, RELU_); }); });
+                }
+            });
+            if (next >= g.items) return;
+            item = next;
+        }
+    }
 
     for (;;) {
         constexpr int NP = W8 ? 8 : 16;                      // positions per wave (W8: acc[2 i + jj] is position 4 i + 2 pg + jj)
@@ -944,7 +1208,7 @@ extern "C" size_t hps_conv3x3_winograd_workspace(int B, int H, int W, int Cin, i
 
 static int wino_launch(const float* x, const float* u, const float* scale, const float* shift, const float* residual,
                        float* y, int B, int H, int W, int ipad, int Cin, int Cout, int opad, int relu, float* splitk_ws, int ablate,
-                       hps_stream_t stream) {
+                       hps_stream_t stream, int grid_cap = 0) {          // grid_cap (dev entry only): workgroups of the persistent grid, 0 = one per CU
     if (!x || !u || !scale || !shift || !y) return bad_arg("hps_conv3x3_winograd: null pointer");
     if (B <= 0) return HPS_OK;
     const bool quad = H == 8 && W == 8;
@@ -979,7 +1243,8 @@ static int wino_launch(const float* x, const float* u, const float* scale, const
     g.magic_ks = wino_magic((unsigned)g.ksplit);
     const size_t lds = (size_t)(4 * W_OPER + 3 * W_RAW) * sizeof(float);           // 162 176 bytes
     // persistent grid: one workgroup per CU (256 on MI355X), items strided over the workgroups
-    const dim3 grid((unsigned)(g.items < 256 ? g.items : 256));
+    const int max_wgs = grid_cap > 0 && grid_cap < 256 ? grid_cap : 256;
+    const dim3 grid((unsigned)(g.items < max_wgs ? g.items : max_wgs));
     int grant_rc = HPS_OK;
     auto launch = [&](auto AB, auto Q) {
         constexpr int ab = decltype(AB)::value;
@@ -999,9 +1264,10 @@ static int wino_launch(const float* x, const float* u, const float* scale, const
     typedef std::integral_constant<bool, false> F;
     typedef std::integral_constant<bool, true> T;
     if (quad) {
-        if (ablate != 0 && ablate != 21 && ablate != 23) return bad_arg("hps_conv3x3_winograd: ablations exist for the 16 x 16-block geometry only");
+        if (ablate != 0 && ablate != 21 && ablate != 23 && ablate != 50) return bad_arg("hps_conv3x3_winograd: ablations exist for the 16 x 16-block geometry only");
 #ifdef HPS_DEV_BUILD
         if (ablate == 21) launch(std::integral_constant<int, 0>(), T());      // the four-wave form
+        else if (ablate == 50) launch8(T(), F(), std::integral_constant<int, 50>());      // eight waves, the earlier item loop (identical bits)
         else if (ablate == 23) launch8(T(), T(), Z());                        // eight waves, a lane owns a tile (16-byte stores: slower)
         else
 #endif
@@ -1028,6 +1294,7 @@ static int wino_launch(const float* x, const float* u, const float* scale, const
         case 43: launch8(F(), F(), std::integral_constant<int, 13>()); break;   // timing only: the MFMAs as bf16x3 piece products (3 bf16 MFMAs per position and 8 k)
         case 44: launch8(F(), F(), std::integral_constant<int, 14>()); break;   // ... + the VALU work of splitting the transformed input into three bf16 pieces
         case 11: launch8(F(), F(), std::integral_constant<int, 11>()); break;   // profiling: lane = channel form with clock stamps (hps_dev_wino_stamps)
+        case 50: launch8(F(), F(), std::integral_constant<int, 50>()); break;   // eight waves, the earlier item loop (identical bits; the reference of tests/test_gpu_wino_item.py)
         case 21: launch(std::integral_constant<int, 0>(), F()); break;          // the four-wave form (identical bits; the ablations below are its)
         case 1: launch(std::integral_constant<int, 1>(), F()); break;
         case 2: launch(std::integral_constant<int, 2>(), F()); break;
@@ -1102,6 +1369,8 @@ extern "C" int hps_dev_wino_quad_ksplit(int ks) {       // experiment: K slices 
 extern "C" int hps_dev_conv3x3_winograd(const float* x, const float* u, const float* scale, const float* shift, const float* residual,
                                         float* y, int B, int H, int W, int ipad, int Cin, int Cout, int opad, int relu,
                                         float* splitk_ws, int ablate, hps_stream_t stream) {
-    return wino_launch(x, u, scale, shift, residual, y, B, H, W, ipad, Cin, Cout, opad, relu, splitk_ws, ablate, stream);
+    // ablate = 1000 * cap + ablation: at most `cap` workgroups walk the items (0 = one per CU), so that a small problem has item hand-overs
+    if (ablate < 0) return bad_arg("hps_dev_conv3x3_winograd: ablate");
+    return wino_launch(x, u, scale, shift, residual, y, B, H, W, ipad, Cin, Cout, opad, relu, splitk_ws, ablate % 1000, stream, ablate / 1000);
 }
 #endif

@@ -149,7 +149,11 @@ int hps_dev_mesh_fused(const float* xt, const float* bmat_p, const float* v_temp
  * reads the first window, 9 = DMAs issued in one burst per chunk, 10 = no barrier per chunk (races; results are garbage except for 9); 0 = the product
  * kernel.  16 x 16-block geometry only.  The eight-wave product form has its own set (21-44, csrc/conv_wino.hip), among them the two that
  * price a bf16x3 arithmetic for these layers, timing only: 43 = every position's four fp32 MFMAs per 8 k as three v_mfma_f32_32x32x16_bf16,
- * 44 = 43 + the VALU work of splitting the transformed input into three bf16 pieces (tests/dev/wino_bf16x3_price.py). */
+ * 44 = 43 + the VALU work of splitting the transformed input into three bf16 pieces (tests/dev/wino_bf16x3_price.py).
+ * 50 = the eight-wave form with the item loop and epilogue it had before the one-VALU-run loop (both geometries; identical bits): the
+ * reference of tests/test_gpu_wino_item.py.  The ablations 24-44 are ablations of that earlier loop.
+ * ablate = 1000 * cap + ablation (cap >= 1): the same ablation with at most `cap` workgroups in the persistent grid instead of one per CU,
+ * so that a small problem exercises the hand-over from one item to the next. */
 int hps_dev_conv3x3_winograd(const float* x, const float* u, const float* scale, const float* shift,
                              const float* residual, float* y, int B, int H, int W, int ipad, int Cin, int Cout,
                              int opad, int relu, float* splitk_ws, int ablate, hps_stream_t stream);
