@@ -144,14 +144,17 @@ int hps_dev_mesh_fused(const float* xt, const float* bmat_p, const float* v_temp
                        const int32_t* w_idx, const float* w_val, int K, int num_joints, const float* transl,
                        float* verts, int M, int V, int kp, int mp, int np, int ablate, hps_stream_t stream);
 
-/* Profiling ablations of hps_conv3x3_winograd: 1 = no patch loads / input transform, 2 = no MFMA, 3 = no filter DMA,
+/* hps_conv3x3_winograd's kernel (ablate = 0: the product's own code, csrc/conv_wino.hip) or one of its earlier forms and their profiling
+ * ablations (conv_wino_earlier_kernel, csrc/conv_wino_dev.hip, where the table of forms is).  Of the four-wave first form (21; identical
+ * bits): 1 = no patch loads / input transform, 2 = no MFMA, 3 = no filter DMA,
  * 4 = no epilogue, 5 = raw DMA but no transform, 6 = transform but no raw DMA, 7 = raw DMA from one line, 8 = every item
- * reads the first window, 9 = DMAs issued in one burst per chunk, 10 = no barrier per chunk (races; results are garbage except for 9); 0 = the product
- * kernel.  16 x 16-block geometry only.  The eight-wave product form has its own set (21-44, csrc/conv_wino.hip), among them the two that
+ * reads the first window, 9 = DMAs issued in one burst per chunk, 10 = no barrier per chunk (races; results are garbage except for 9).
+ * 16 x 16-block geometry only.  The eight-wave form has its own set (23-44), among them the two that
  * price a bf16x3 arithmetic for these layers, timing only: 43 = every position's four fp32 MFMAs per 8 k as three v_mfma_f32_32x32x16_bf16,
  * 44 = 43 + the VALU work of splitting the transformed input into three bf16 pieces (tests/dev/wino_bf16x3_price.py).
  * 50 = the eight-wave form with the item loop and epilogue it had before the one-VALU-run loop (both geometries; identical bits): the
- * reference of tests/test_gpu_wino_item.py.  The ablations 24-44 are ablations of that earlier loop.
+ * reference of tests/test_gpu_wino_item.py.  The ablations 24-44 are ablations of that earlier loop.  The 8 x 8 (quad) geometry knows 0, 21,
+ * 23 and 50.
  * ablate = 1000 * cap + ablation (cap >= 1): the same ablation with at most `cap` workgroups in the persistent grid instead of one per CU,
  * so that a small problem exercises the hand-over from one item to the next. */
 int hps_dev_conv3x3_winograd(const float* x, const float* u, const float* scale, const float* shift,

@@ -1,5 +1,6 @@
-"""The Winograd kernel's item loop (csrc/conv_wino.hip, LEAN: one VALU run per chunk, the peeled first chunk on a zero C operand, an
-epilogue of wave-uniform branches) against the loop and epilogue it replaced, which the dev library keeps as ablate = 50: the same
+"""The Winograd kernel's item loop (csrc/conv_wino.hip: one VALU run per chunk, the peeled first chunk on a zero C operand, an
+epilogue of wave-uniform branches) against the loop and epilogue it replaced, which the dev library keeps as ablate = 50
+(conv_wino_earlier_kernel, csrc/conv_wino_dev.hip): the same
 products and sums in the same order, so EQUAL bits -- halo included -- and, independently, within 1e-5 of the output scale of a float64
 direct convolution (the tolerance of test_gpu_net.py::test_winograd_conv_kernel).
 

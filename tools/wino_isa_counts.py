@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Instruction counts of the compiled conv_wino_kernel instantiations, per basic block and per region (no GPU needed).
+"""Instruction counts of the compiled Winograd layer kernels, per basic block and per region (no GPU needed).
 
-Compiles csrc/conv_wino.hip to gfx950 assembly with the build recipe's flags and prints, for every conv_wino_kernel:
+Compiles csrc/conv_wino.hip (the product's conv_wino_kernel) or, with --dev, csrc/conv_wino_dev.hip (the dev library's earlier forms,
+conv_wino_earlier_kernel) to gfx950 assembly with the build recipe's flags and prints, for every instantiation:
   * the kernel metadata (VGPRs, SGPR spills, scratch bytes);
   * per basic block: loop depth and instructions per class (MFMA, VALU, SALU, LDS, DMA, VMEM, branch, wait / barrier / nop);
   * per chunk body -- every depth-2 loop, and every piece of the depth-1 code between two s_barrier that holds MFMAs (a peeled chunk;
@@ -11,7 +12,8 @@ Compiles csrc/conv_wino.hip to gfx950 assembly with the build recipe's flags and
 A block that a wave-uniform branch skips is still counted: the sums are those of a steady-state chunk / of an item that takes every path,
 so an epilogue specialised by branches counts once per variant (--blocks shows the blocks).
 
-usage: wino_isa_counts.py [--dev] [--blocks] [--asm FILE] [extra hipcc flags, e.g. -fno-slp-vectorize]
+usage: wino_isa_counts.py [--dev] [--source FILE.hip] [--blocks] [--asm FILE] [extra hipcc flags, e.g. -fno-slp-vectorize]
+  --dev: the dev library's flags and, unless --source says otherwise, conv_wino_dev.hip; --source: a file under csrc/
 """
 import collections
 import os
@@ -26,12 +28,15 @@ sys.path.insert(0, REPO)
 CLASSES = ("mfma", "valu", "salu", "lds", "dma", "vmem", "branch", "wait")
 
 
-def compile_asm(dev=False, extra=()):
+def compile_asm(dev=False, extra=(), source=None):
+    """dev: the dev library's flags.  source: a file under csrc/ (default: conv_wino.hip, the product kernel; with dev, conv_wino_dev.hip, the
+    earlier forms -- conv_wino.hip itself is part of both libraries, so it can be asked for with dev=True as well)."""
     from hierarchicalprobabilistic3dhuman_amd import build as B
-    flags = B.FLAGS + (["-DHPS_DEV_BUILD"] if dev else []) + B.FILE_FLAGS.get("conv_wino.hip", []) + list(extra)
+    source = source or ("conv_wino_dev.hip" if dev else "conv_wino.hip")
+    flags = B.FLAGS + (["-DHPS_DEV_BUILD"] if dev else []) + B.FILE_FLAGS.get(source, []) + list(extra)
     with tempfile.TemporaryDirectory() as tmp:
         out = os.path.join(tmp, "conv_wino.s")
-        cmd = [B._hipcc()] + flags + ["-I", B.INCLUDE, "-I", B.CSRC, "-S", "--cuda-device-only", os.path.join(B.CSRC, "conv_wino.hip"), "-o", out]
+        cmd = [B._hipcc()] + flags + ["-I", B.INCLUDE, "-I", B.CSRC, "-S", "--cuda-device-only", os.path.join(B.CSRC, source), "-o", out]
         subprocess.run(cmd, check=True, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         with open(out) as f:
             return f.read()
@@ -62,7 +67,7 @@ def kernels(asm):
     out = collections.OrderedDict()
     cur = None
     for line in asm.splitlines():
-        m = re.match(r"^(_Z\w*conv_wino_kernel\w*):", line)
+        m = re.match(r"^(_Z\w*conv_wino_(?:earlier_)?kernel\w*):", line)
         if m:
             cur = out[m.group(1)] = [["entry", 0, [], "entry"]]
             continue
@@ -161,10 +166,13 @@ if __name__ == "__main__":
     args = sys.argv[1:]
     dev = "--dev" in args
     show = "--blocks" in args
-    src = None
+    src = source = None
     if "--asm" in args:
         src = args[args.index("--asm") + 1]
         args.remove(src)
-    extra = [a for a in args if a not in ("--dev", "--blocks", "--asm")]
-    text = open(src).read() if src else compile_asm(dev, extra)
+    if "--source" in args:
+        source = args[args.index("--source") + 1]
+        args.remove(source)
+    extra = [a for a in args if a not in ("--dev", "--blocks", "--asm", "--source")]
+    text = open(src).read() if src else compile_asm(dev, extra, source)
     report(text, show)
