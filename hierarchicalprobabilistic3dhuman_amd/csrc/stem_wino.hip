@@ -41,119 +41,17 @@
 // the workgroup, two filter rows (5 positions x 4.5 KiB, double buffered) -- 154 KiB, one workgroup per CU, persistent.
 // The input comes from hps_stem_phase_split: the four phase images of every input image as separate NHWC frames, so that a
 // window row is one contiguous run and the channels of a pixel sit in the order the lanes read them.
-#include <type_traits>
-
-#include "hps_common.h"
+//
+// This file is the kernel that ships, alone.  Its sizes, row table and geometry are in stem_wino.h; the profiling forms
+// that price its parts (hps_dev_stem_winograd and its kin) are a copy of it in stem_wino_dev.hip, dev library only.
+#include "stem_wino.h"
 
 namespace hps {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-constexpr int SW_C = 18;                         // input channels
-constexpr int SW_CO = 64;                        // output channels
-constexpr int SW_PAIR = 38;                      // floats per pixel PAIR: 2 x 18 channels + 2 floats of padding (see stem_phase_split_kernel)
-constexpr int SW_SLOTS = 90;                     // 16-byte slots per window row: 19 pixels = 9.5 pairs x 152 bytes = 1440
-constexpr int SW_ROWF = SW_SLOTS * 4;            // floats per window row in LDS
-constexpr int SW_RAW_PIECES = 27;                // 1 KiB DMA pieces per window: 19 rows x 90 slots = 1710 slots (the tail over-reads row 19)
-constexpr int SW_RAW_F = SW_RAW_PIECES * 256;    // floats per window buffer
-constexpr int SW_POS_F = 1152;                   // floats of one position's filters: [co half][k 0-7 | k 8-15 | k 16-17] x 32 co
-constexpr int SW_U_PIECES = 23;                  // a row of five positions = 22.5 KiB
-constexpr int SW_U_F = SW_U_PIECES * 256;
-constexpr int SW_ROWS = 18;
-constexpr int SW_LDS_F = 4 * SW_RAW_F + 2 * SW_U_F;      // 157 696 bytes
-
-// one row of positions: phase, number of x points, the vertical combination, the output fold
-struct StemRow {
-    int phase, first, nxp, ne;
-    int upos;                   // index of the row's first position in the filter array
-    int aoff[4];                // window rows of the vertical combination, as float offsets (a * SW_ROWF)
-    float coef[4];
-    float e0, e1;               // A_y^T[0][i], A_y^T[1][i]
-};
-// F(2, 4), points 0, 1, -1, 2, inf:  B^T = [2 -1 -2 1 0; 0 -2 -1 1 0; 0 2 -3 1 0; 0 -1 0 1 0; 0 2 -1 -2 1],  A^T = [1 1 1 1 0; 0 1 -1 2 1]
-// F(2, 3), points 0, 1, -1, inf:     B^T = [1 0 -1 0; 0 1 1 0; 0 -1 1 0; 0 -1 0 1],                          A^T = [1 1 1 0; 0 1 -1 1]
-// Phases in the order (even rows, even columns), (even, odd), (odd, even), (odd, odd); ne = taps of the row's vertical combination
-// (unused entries repeat tap 0 with coefficient 0).
-__constant__ StemRow c_stem_rows[SW_ROWS] = {
-    {0, 1, 5, 4,  0, {0 * SW_ROWF, 1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF}, {2.0f, -1.0f, -2.0f, 1.0f}, 1.0f, 0.0f},
-    {0, 0, 5, 3,  5, {1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF}, {-2.0f, -1.0f, 1.0f, 0.0f}, 1.0f, 1.0f},
-    {0, 0, 5, 3, 10, {1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF}, {2.0f, -3.0f, 1.0f, 0.0f}, 1.0f, -1.0f},
-    {0, 0, 5, 2, 15, {1 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {-1.0f, 1.0f, 0.0f, 0.0f}, 1.0f, 2.0f},
-    {0, 0, 5, 4, 20, {1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF, 4 * SW_ROWF}, {2.0f, -1.0f, -2.0f, 1.0f}, 0.0f, 1.0f},
-    {1, 1, 4, 4, 25, {0 * SW_ROWF, 1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF}, {2.0f, -1.0f, -2.0f, 1.0f}, 1.0f, 0.0f},
-    {1, 0, 4, 3, 29, {1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF}, {-2.0f, -1.0f, 1.0f, 0.0f}, 1.0f, 1.0f},
-    {1, 0, 4, 3, 33, {1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF}, {2.0f, -3.0f, 1.0f, 0.0f}, 1.0f, -1.0f},
-    {1, 0, 4, 2, 37, {1 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {-1.0f, 1.0f, 0.0f, 0.0f}, 1.0f, 2.0f},
-    {1, 0, 4, 4, 41, {1 * SW_ROWF, 2 * SW_ROWF, 3 * SW_ROWF, 4 * SW_ROWF}, {2.0f, -1.0f, -2.0f, 1.0f}, 0.0f, 1.0f},
-    {2, 1, 5, 2, 45, {0 * SW_ROWF, 2 * SW_ROWF, 0 * SW_ROWF, 0 * SW_ROWF}, {1.0f, -1.0f, 0.0f, 0.0f}, 1.0f, 0.0f},
-    {2, 0, 5, 2, 50, {1 * SW_ROWF, 2 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {1.0f, 1.0f, 0.0f, 0.0f}, 1.0f, 1.0f},
-    {2, 0, 5, 2, 55, {1 * SW_ROWF, 2 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {-1.0f, 1.0f, 0.0f, 0.0f}, 1.0f, -1.0f},
-    {2, 0, 5, 2, 60, {1 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {-1.0f, 1.0f, 0.0f, 0.0f}, 0.0f, 1.0f},
-    {3, 1, 4, 2, 65, {0 * SW_ROWF, 2 * SW_ROWF, 0 * SW_ROWF, 0 * SW_ROWF}, {1.0f, -1.0f, 0.0f, 0.0f}, 1.0f, 0.0f},
-    {3, 0, 4, 2, 69, {1 * SW_ROWF, 2 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {1.0f, 1.0f, 0.0f, 0.0f}, 1.0f, 1.0f},
-    {3, 0, 4, 2, 73, {1 * SW_ROWF, 2 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {-1.0f, 1.0f, 0.0f, 0.0f}, 1.0f, -1.0f},
-    {3, 0, 4, 2, 77, {1 * SW_ROWF, 3 * SW_ROWF, 1 * SW_ROWF, 1 * SW_ROWF}, {-1.0f, 1.0f, 0.0f, 0.0f}, 0.0f, 1.0f}};
-
-struct StemGeom {
-    int fr_rowf, fr_phasef, fr_imgf;      // phase frame pitches in floats: row, phase frame, image (4 phase frames)
-    int blocks_x, blocks_img, n_items;
-    int out_row, out_img, opad, relu;     // output frame (B, Ho + 2 opad, Wo + 2 opad, 64)
-    unsigned magic_img, magic_x;
-    int in_h, in_w;                       // NCHW-fed form: the input image (B, 18, in_h, in_w)
-};
-
-__device__ __forceinline__ unsigned sw_div(unsigned n, unsigned d, unsigned magic) {
-    unsigned q = __umulhi(n, magic);
-    if (n - q * d >= d) ++q;
-    return q;
-}
-static unsigned sw_magic(unsigned d) { return d <= 1 ? 0xffffffffu : (unsigned)(0x100000000ull / d); }
-
-// B_x^T applied to the vertical combinations c[0..NXP): position j of the row
-template <int NXP, typename T>
-__device__ __forceinline__ T sw_horiz(int j, const T (&c)[5]) {
-    if (NXP == 5) {
-        switch (j) {
-            case 0: return 2.0f * (c[0] - c[2]) + (c[3] - c[1]);
-            case 1: return (c[3] - c[2]) - 2.0f * c[1];
-            case 2: return (2.0f * c[1] + c[3]) - 3.0f * c[2];
-            case 3: return c[3] - c[1];
-            default: return 2.0f * (c[1] - c[3]) + (c[4] - c[2]);
-        }
-    }
-    switch (j) {
-        case 0: return c[0] - c[2];
-        case 1: return c[1] + c[2];
-        case 2: return c[2] - c[1];
-        default: return c[3] - c[1];
-    }
-}
-
-// One 8-byte LDS read per patch pixel and channel pair, as ds_read_b64 (volatile: hipcc would pair two of them into a
-// ds_read2_b64, which the LDS serves at half the rate -- 16-lane groups, banks mod 32 -- and with the tiles' 144-byte pitch at
-// half of that again)
-__device__ __forceinline__ v2f sw_ld2(const float* p) {
-    typedef const volatile __attribute__((address_space(3))) v2f* lds_v2f_t;
-    return *(lds_v2f_t)(const __attribute__((address_space(3))) float*)p;
-}
-
-template <int AB>
-__device__ __forceinline__ f32x16 sw_mfma(float a, float b, f32x16 c) {
-    if (AB == 2) {
-        c[0] += a * b;
-        return c;
-    }
-    return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0);
-}
 
 // Input transform of one row of positions (see the header): A[j][m] = the lane's channel 2 m + kl of position j, m = 0..8.
 // rawp: this lane's patch origin in the raw window (its channel pairs), raws: the channels 16, 17 of that pixel (odd: the lane
 // keeps 17).  NXP: positions of the row, NE: window rows in its vertical combination.
-// AB: profiling ablations (dev library only; the product instantiates AB = 0): 1 = patch pixels not read (constants), 2 = no MFMAs,
-// 3 = no output transform, 4 = no barriers (races), 5 = no filter fragment reads, 6 = no stores
-// G0, G1 (profiling, AB = 12 / 13): only the channel groups [G0, G1) are transformed, the other operands stay constants
-template <int NXP, int NE, int AB, int G0 = 0, int G1 = 5>
+template <int NXP, int NE>
 __device__ __forceinline__ void sw_transform(const float* rawp, const float* raws, const StemRow& row, bool odd, float (&A)[5][9]) {
     const int o[4] = {row.aoff[0], row.aoff[1], row.aoff[2], row.aoff[3]};
     const float k[4] = {row.coef[0], row.coef[1], row.coef[2], row.coef[3]};
@@ -164,24 +62,13 @@ __device__ __forceinline__ void sw_transform(const float* rawp, const float* raw
 #pragma unroll
             for (int e = 0; e < NE; ++e) {
                 const float* p = (g < 4 ? rawp + g * 4 : raws) + (b >> 1) * SW_PAIR + (b & 1) * SW_C + o[e];
-                if (AB == 7) {       // profiling: the channel pair as two 4-byte reads (what a planar, NCHW-fed window would need)
-                    typedef const volatile __attribute__((address_space(3))) float* lds_f_t;
-                    const lds_f_t q = (lds_f_t)(const __attribute__((address_space(3))) float*)p;
-                    ld[g & 1][b][e] = (v2f){q[0], q[1]};
-                } else
-                    ld[g & 1][b][e] = AB == 1 ? (v2f){(float)(unsigned)(size_t)p, 1.0f} : sw_ld2(p);
+                ld[g & 1][b][e] = sw_ld2(p);
             }
     };
-    if (G0 > 0 || G1 < 5) {
+    issue(0);
 #pragma unroll
-        for (int j = 0; j < 5; ++j)
-#pragma unroll
-            for (int m = 0; m < 9; ++m) A[j][m] = (float)(j + m);
-    }
-    issue(G0);
-#pragma unroll
-    for (int g = G0; g < G1; ++g) {
-        if (g + 1 < G1) issue(g + 1);
+    for (int g = 0; g < 5; ++g) {
+        if (g + 1 < 5) issue(g + 1);
         v2f c[5];
 #pragma unroll
         for (int b = 0; b < NXP; ++b) {
@@ -205,32 +92,32 @@ __device__ __forceinline__ void sw_transform(const float* rawp, const float* raw
 
 // The MFMAs of one row (nine per position, filters of the position read from LDS one position ahead) and its output transform
 // t = M A_x, Y[a][.] += A_y^T[a][i] t.  ub / ub1: this lane's filter fragment slots of position 0 of the row (k 0-15, k 16-17).
-template <int NXP, int AB, typename Spread>
+template <int NXP, typename Spread>
 __device__ __forceinline__ void sw_gemm(const float* ub, const float* ub1, const StemRow& row, const float (&A)[5][9], f32x16 (&Y)[2][2],
                                         Spread spread) {
     f32x16 M[5];
     const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    float4 u0 = AB == 5 ? make_float4(1.f, 2.f, 3.f, 4.f) : *reinterpret_cast<const float4*>(ub);
-    float4 u1 = AB == 5 ? make_float4(1.f, 2.f, 3.f, 4.f) : *reinterpret_cast<const float4*>(ub + 256);
-    float u2 = AB == 5 ? 1.0f : ub1[0];
+    float4 u0 = *reinterpret_cast<const float4*>(ub);
+    float4 u1 = *reinterpret_cast<const float4*>(ub + 256);
+    float u2 = ub1[0];
 #pragma unroll
     for (int j = 0; j < NXP; ++j) {
         float4 n0 = u0, n1 = u1;
         float n2 = u2;
-        if (j + 1 < NXP && AB != 5) {
+        if (j + 1 < NXP) {
             n0 = *reinterpret_cast<const float4*>(ub + (j + 1) * SW_POS_F);
             n1 = *reinterpret_cast<const float4*>(ub + (j + 1) * SW_POS_F + 256);
             n2 = ub1[(j + 1) * SW_POS_F];
         }
-        M[j] = sw_mfma<AB>(u0.x, A[j][0], z);
-        M[j] = sw_mfma<AB>(u0.y, A[j][1], M[j]);
-        M[j] = sw_mfma<AB>(u0.z, A[j][2], M[j]);
-        M[j] = sw_mfma<AB>(u0.w, A[j][3], M[j]);
-        M[j] = sw_mfma<AB>(u1.x, A[j][4], M[j]);
-        M[j] = sw_mfma<AB>(u1.y, A[j][5], M[j]);
-        M[j] = sw_mfma<AB>(u1.z, A[j][6], M[j]);
-        M[j] = sw_mfma<AB>(u1.w, A[j][7], M[j]);
-        M[j] = sw_mfma<AB>(u2, A[j][8], M[j]);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u0.x, A[j][0], z, 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u0.y, A[j][1], M[j], 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u0.z, A[j][2], M[j], 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u0.w, A[j][3], M[j], 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u1.x, A[j][4], M[j], 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u1.y, A[j][5], M[j], 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u1.z, A[j][6], M[j], 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u1.w, A[j][7], M[j], 0, 0, 0);
+        M[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(u2, A[j][8], M[j], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int sl = 2 * j; sl < (j + 1 < NXP ? 2 * j + 2 : 10); ++sl) spread(sl);       // DMA pieces of the next row / phase (see the caller)
@@ -238,11 +125,6 @@ __device__ __forceinline__ void sw_gemm(const float* ub, const float* ub1, const
         u0 = n0;
         u1 = n1;
         u2 = n2;
-    }
-    if (AB == 3) {
-#pragma unroll
-        for (int j = 0; j < NXP; ++j) Y[j & 1][(j >> 1) & 1][j] += M[j][j];
-        return;
     }
     f32x16 t0, t1;
     if (NXP == 5) {
@@ -274,7 +156,7 @@ __device__ __forceinline__ void sw_gemm(const float* ub, const float* ub1, const
 // floats: global loads (exec-masked where the pixel lies outside the image: it stays zero) in one row's MFMA run, the 8-byte LDS stores at the
 // top of the next row.  Window p + 1 is stored during the first four rows of phase p (its first chunk is loaded in the last row of phase
 // p - 1, when the buffer's previous window has been read for the last time); xf is then the NCHW tensor.
-template <int AB, bool POOL = false, bool NCHW = false>
+template <bool POOL, bool NCHW>
 __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict__ xf, const float* __restrict__ u,
                                                            const float* __restrict__ scale, const float* __restrict__ shift,
                                                            float* __restrict__ y, float* __restrict__ side, const StemGeom g) {
@@ -302,9 +184,8 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
     const unsigned lds_u = lds0 + (unsigned)(4 * SW_RAW_F * 4);
 
     auto window_src = [&](int item, int phase) -> const float* {
-        const unsigned b = sw_div((unsigned)item, (unsigned)g.blocks_img, g.magic_img), rem = item - b * g.blocks_img;
-        const unsigned by = sw_div(rem, (unsigned)g.blocks_x, g.magic_x), bx = rem - by * g.blocks_x;
-        return xf + (size_t)b * g.fr_imgf + (size_t)phase * g.fr_phasef + (size_t)(16 * by) * g.fr_rowf + (size_t)(8 * bx) * SW_PAIR;
+        const StemItem at = sw_item(item, g);
+        return xf + (size_t)at.b * g.fr_imgf + (size_t)phase * g.fr_phasef + (size_t)(16 * at.by) * g.fr_rowf + (size_t)(8 * at.bx) * SW_PAIR;
     };
     // piece k (0..6) of the phase window whose origin is src -> the team's buffer phase & 1; this wave moves pieces w4, w4 + 4, ...
     auto dma_raw_piece = [&](const float* src, int phase, int k) {
@@ -345,11 +226,10 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
     const float* nc_origin = xf; int nc_y0 = 0, nc_x0 = 0; bool nc_border = false;        // the current item
     const float* nn_origin = xf; int nn_y0 = 0, nn_x0 = 0; bool nn_border = false;        // the next one
     auto nchw_item = [&](int it, const float*& origin, int& y0, int& x0, bool& border) {
-        const unsigned b = sw_div((unsigned)it, (unsigned)g.blocks_img, g.magic_img), rem = it - b * g.blocks_img;
-        const unsigned by = sw_div(rem, (unsigned)g.blocks_x, g.magic_x), bx = rem - by * g.blocks_x;
-        y0 = 32 * (int)by - 3; x0 = 32 * (int)bx - 3;
-        origin = xf + (long)b * SW_C * n_plane + (long)y0 * g.in_w + x0;
-        border = by == 0 || bx == 0 || y0 + 38 > g.in_h || x0 + 38 > g.in_w;
+        const StemItem at = sw_item(it, g);
+        y0 = 32 * (int)at.by - 3; x0 = 32 * (int)at.bx - 3;
+        origin = xf + (long)at.b * SW_C * n_plane + (long)y0 * g.in_w + x0;
+        border = at.by == 0 || at.bx == 0 || y0 + 38 > g.in_h || x0 + 38 > g.in_w;
     };
     const bool n_act1 = n_act && n_pj < 9;                                         // the pair's second pixel exists (19 pixels per window row)
     const float* n_base = xf;                                                      // wave-uniform: pixel 0 of pair (0, 0), first channel of the chunk
@@ -370,7 +250,7 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
         }
     };
     auto nchw_load2 = [&](int q, int sc) {                   // channel sc of the chunk aimed at, both pixels
-        if (sc < (q == 3 ? 6 : 4) && AB != 8) {             // (8: profiling, no gather loads)
+        if (sc < (q == 3 ? 6 : 4)) {
             if (n_zero) { lr[2 * sc] = 0.0f; lr[2 * sc + 1] = 0.0f; }
             const float* p = reinterpret_cast<const float*>(reinterpret_cast<const char*>(n_base + sc * n_plane) + n_goff);
             if (n_ok0) lr[2 * sc] = p[0];
@@ -378,7 +258,6 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
         }
     };
     auto nchw_store = [&](int phase, int q) {                // the chunk in lr -> the team's window buffer phase & 1 (slots: c c+2 | c+1 c+3 per four channels)
-        if (AB == 9) return;                                 // (9: profiling, no window stores)
         float* d = smem + team * 2 * SW_RAW_F + (phase & 1) * SW_RAW_F + n_lds + 4 * q;
         if (n_act) {
             *reinterpret_cast<v2f*>(d + 0) = (v2f){lr[0], lr[4]};
@@ -448,66 +327,20 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
             const float* raws = raw_team + (phase & 1) * SW_RAW_F + patch0 + 16;
             const bool odd = kl != 0;
             float A[5][9];
-            // Profiling (dev library; results are garbage): what removing the DUPLICATE input transform could buy at most.  The waves of a
-            // channel-half pair (wn = 0 / 1) transform the same tiles.  AB = 10: the wn = 1 waves skip the transform outright (operands =
-            // constants) -- the upper bound, a hand-over that costs nothing.  AB = 11: they read their 45 operands from LDS instead (the
-            // team's window buffer as a stand-in for an exchange buffer: 45 four-byte reads per lane) behind one more barrier per row --
-            // the cheapest hand-over there could be (the wn = 0 waves' 45 stores are NOT charged).
-            // AB = 12 / 13: the SPLIT form -- each wave of the pair transforms about half of the channels (wn = 0: channel pairs 0-3 of
-            // the even / odd parity = groups 0, 1; wn = 1: groups 2, 3 and the singles) and would get the other half from its partner.
-            // 12: no exchange at all (the upper bound of the split); 13: + 23 LDS stores, 23 LDS reads per lane and row and a second barrier
-            // (stand-ins in the team's window buffer: the cheapest exchange there could be, its 2 x 23 KB of LDS not even found yet).
-            if (AB == 12 || AB == 13) {
-                if (row.nxp == 5) {
-                    if (wn == 0) { if (row.ne == 4) sw_transform<5, 4, AB, 0, 2>(rawp, raws, row, odd, A); else if (row.ne == 3) sw_transform<5, 3, AB, 0, 2>(rawp, raws, row, odd, A); else sw_transform<5, 2, AB, 0, 2>(rawp, raws, row, odd, A); }
-                    else { if (row.ne == 4) sw_transform<5, 4, AB, 2, 5>(rawp, raws, row, odd, A); else if (row.ne == 3) sw_transform<5, 3, AB, 2, 5>(rawp, raws, row, odd, A); else sw_transform<5, 2, AB, 2, 5>(rawp, raws, row, odd, A); }
-                } else {
-                    if (wn == 0) { if (row.ne == 4) sw_transform<4, 4, AB, 0, 2>(rawp, raws, row, odd, A); else if (row.ne == 3) sw_transform<4, 3, AB, 0, 2>(rawp, raws, row, odd, A); else sw_transform<4, 2, AB, 0, 2>(rawp, raws, row, odd, A); }
-                    else { if (row.ne == 4) sw_transform<4, 4, AB, 2, 5>(rawp, raws, row, odd, A); else if (row.ne == 3) sw_transform<4, 3, AB, 2, 5>(rawp, raws, row, odd, A); else sw_transform<4, 2, AB, 2, 5>(rawp, raws, row, odd, A); }
-                }
-                if (AB == 13) {
-                    float* xq = const_cast<float*>(raw_team) + (phase & 1) * SW_RAW_F + (w4 * 23) * 64 + lane;
-                    if (wn) {
-#pragma unroll
-                        for (int e = 0; e < 23; ++e) xq[e * 64] = A[e / 9 + 2][e % 9];
-                    } else {
-#pragma unroll
-                        for (int e = 0; e < 23; ++e) xq[e * 64] = A[e / 9][e % 9];
-                    }
-                }
-            } else
-            if ((AB == 10 || AB == 11) && wn == 1) {
-#pragma unroll
-                for (int j = 0; j < 5; ++j)
-#pragma unroll
-                    for (int m = 0; m < 9; ++m) A[j][m] = AB == 10 ? (float)(j + m) : raw_team[(phase & 1) * SW_RAW_F + (j * 9 + m) * 64 + lane];
-            } else
             if (row.nxp == 5) {
-                if (row.ne == 4) sw_transform<5, 4, AB>(rawp, raws, row, odd, A);
-                else if (row.ne == 3) sw_transform<5, 3, AB>(rawp, raws, row, odd, A);
-                else sw_transform<5, 2, AB>(rawp, raws, row, odd, A);
+                if (row.ne == 4) sw_transform<5, 4>(rawp, raws, row, odd, A);
+                else if (row.ne == 3) sw_transform<5, 3>(rawp, raws, row, odd, A);
+                else sw_transform<5, 2>(rawp, raws, row, odd, A);
             } else {
-                if (row.ne == 4) sw_transform<4, 4, AB>(rawp, raws, row, odd, A);
-                else if (row.ne == 3) sw_transform<4, 3, AB>(rawp, raws, row, odd, A);
-                else sw_transform<4, 2, AB>(rawp, raws, row, odd, A);
+                if (row.ne == 4) sw_transform<4, 4>(rawp, raws, row, odd, A);
+                else if (row.ne == 3) sw_transform<4, 3>(rawp, raws, row, odd, A);
+                else sw_transform<4, 2>(rawp, raws, row, odd, A);
             }
             // NCHW: the chunk loaded during the previous row's MFMA run goes to LDS here, behind the transform (its loads have had the
             // transform's time to arrive; stored at the top of the row they were waited for) and in front of the row's barrier
             if (NCHW && n_idx < 4 && (phase < 3 || has_next)) nchw_store(phase + 1, n_idx);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's pieces of row r's filters (and of the next phase window)
-            if (AB != 4) __syncthreads();                        // ... everyone's; the other filter buffer and window buffer are free
-            if (AB == 11) __syncthreads();                       // (profiling: the hand-over's second barrier)
-            if (AB == 13) {                                      // (profiling: the exchange's second half -- read the partner's 23 operands, one more barrier)
-                const float* xq = raw_team + (phase & 1) * SW_RAW_F + ((w4 ^ 1) * 23) * 64 + lane;
-                if (wn) {
-#pragma unroll
-                    for (int e = 0; e < 23; ++e) A[e / 9][e % 9] = xq[e * 64];
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 23; ++e) A[e / 9 + 2][e % 9] = xq[e * 64];
-                }
-                __syncthreads();
-            }
+            __syncthreads();                                     // ... everyone's; the other filter buffer and window buffer are free
             // The DMAs of the next row's filters (and, in the first row of a phase, of the next phase's window) are issued INSIDE the
             // MFMA run, two pieces behind each position's MFMAs: in front of the run their issue (about 50 cycles a piece, up to ten
             // pieces) held the whole SIMD back while the MFMA pipe was idle.
@@ -532,21 +365,13 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
             // ---- the row's MFMA run, then its output transform (the head of the next VALU run) ----
             const float* ub = frag0 + (r & 1) * SW_U_F;
             const float* ub1 = frag1 + (r & 1) * SW_U_F;
-            if (row.nxp == 5) sw_gemm<5, AB>(ub, ub1, row, A, Y, spread);
-            else sw_gemm<4, AB>(ub, ub1, row, A, Y, spread);
+            if (row.nxp == 5) sw_gemm<5>(ub, ub1, row, A, Y, spread);
+            else sw_gemm<4>(ub, ub1, row, A, Y, spread);
         }
 
         // ---- bn1 + relu, stores: lane = one tile (MFMA column), register quad q = channels wn 32 + 8 q + 4 kl .. + 3 ----
-        if (AB == 6) {                 // profiling: results kept alive, nothing stored
-            float t = 0.0f;
-#pragma unroll
-            for (int a = 0; a < 2; ++a)
-#pragma unroll
-                for (int bb = 0; bb < 2; ++bb)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) t += Y[a][bb][r];
-            if (t == 12345.678f) y[0] = t;
-        } else if (POOL) {
+        // (written out here and in stem_wino_dev.hip: as shared functions the two epilogues got other registers)
+        if (POOL) {
             const int co = wn * 32 + 4 * kl;
             float4 sc[4], sh[4];
 #pragma unroll
@@ -598,9 +423,8 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
             }
             if (NCHW) __syncthreads();       // the next item's first row STORES into this buffer at once (the frame-fed form's DMA into it waits for a barrier)
             if (live) {
-                const unsigned b = sw_div((unsigned)item, (unsigned)g.blocks_img, g.magic_img), rem = item - b * g.blocks_img;
-                const unsigned by = sw_div(rem, (unsigned)g.blocks_x, g.magic_x), bx = rem - by * g.blocks_x;
-                float* yp = y + (size_t)b * g.out_img + (size_t)(8 * by + ty + g.opad) * g.out_row + (size_t)(8 * bx + tx + g.opad) * SW_CO + co;
+                const StemItem at = sw_item(item, g);
+                float* yp = y + (size_t)at.b * g.out_img + (size_t)(8 * at.by + ty + g.opad) * g.out_row + (size_t)(8 * at.bx + tx + g.opad) * SW_CO + co;
 #pragma unroll
                 for (int q = 0; q < 4; ++q)
                     *reinterpret_cast<float4*>(yp + 8 * q) = make_float4(P[4 * q], P[4 * q + 1], P[4 * q + 2], P[4 * q + 3]);
@@ -621,11 +445,10 @@ __global__ __launch_bounds__(512) void stem_wino_kernel(const float* __restrict_
                 }
             }
         } else if (live) {
-            const unsigned b = sw_div((unsigned)item, (unsigned)g.blocks_img, g.magic_img), rem = item - b * g.blocks_img;
-            const unsigned by = sw_div(rem, (unsigned)g.blocks_x, g.magic_x), bx = rem - by * g.blocks_x;
+            const StemItem at = sw_item(item, g);
             const int co = wn * 32 + 4 * kl;
-            float* yp = y + (size_t)b * g.out_img + (size_t)(16 * by + 2 * ty + g.opad) * g.out_row +
-                        (size_t)(16 * bx + 2 * tx + g.opad) * SW_CO + co;
+            float* yp = y + (size_t)at.b * g.out_img + (size_t)(16 * at.by + 2 * ty + g.opad) * g.out_row +
+                        (size_t)(16 * at.bx + 2 * tx + g.opad) * SW_CO + co;
             float4 sc[4], sh[4];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -769,9 +592,9 @@ __global__ __launch_bounds__(256) void stem_pool_borders_kernel(float* __restric
     const int j = (int)(p % 15);
     const int item = (int)(p / 15);
     const int ty = j < 8 ? 0 : j - 7, tx = j < 8 ? j : 0;
-    const unsigned b = sw_div((unsigned)item, (unsigned)g.blocks_img, g.magic_img), rem = item - b * g.blocks_img;
-    const unsigned by = sw_div(rem, (unsigned)g.blocks_x, g.magic_x), bx = rem - by * g.blocks_x;
-    if (by == 0 && bx == 0) return;                                      // nothing above, nothing to the left
+    const StemItem at = sw_item(item, g);
+    const unsigned b = at.b, by = at.by, bx = at.bx;
+    if (by == 0 && bx == 0) return;                                     // nothing above, nothing to the left
     float4* yp = reinterpret_cast<float4*>(y + (size_t)b * g.out_img + (size_t)(8 * by + ty + g.opad) * g.out_row +
                                            (size_t)(8 * bx + tx + g.opad) * SW_CO + cq * 4);
     float4 v = *yp;
@@ -793,6 +616,27 @@ __global__ __launch_bounds__(256) void stem_pool_borders_kernel(float* __restric
         take(item - 1, 1, ty - 1, 1);
     }
     *yp = v;
+}
+
+int stem_pool_borders_launch(float* y, const float* side, const StemGeom& g, hps_stream_t stream) {
+    const long total = (long)g.n_items * 15 * 16;
+    hipLaunchKernelGGL(stem_pool_borders_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, side, g, total);
+    return check_launch("hps_stem_winograd_pooled (borders)");
+}
+
+int stem_wino_launch(const float* xf, const float* u, const float* scale, const float* shift, float* y, float* side, int B, int H, int W,
+                     int opad, int relu, bool pool, bool nchw, hps_stream_t stream) {
+    StemGeom g;
+    int rc = stem_geom(g, xf, u, scale, shift, y, B, H, W, opad, relu, pool);
+    if (rc != HPS_OK || g.n_items == 0) return rc;
+    if (!pool) {
+        if ((rc = stem_launch_kernel<&stem_wino_kernel<false, false>>(g, xf, u, scale, shift, y, nullptr, stream, "hps_stem_winograd")) != HPS_OK) return rc;
+        return check_launch("hps_stem_winograd");
+    }
+    rc = nchw ? stem_launch_kernel<&stem_wino_kernel<true, true>>(g, xf, u, scale, shift, y, side, stream, "hps_stem_winograd_pooled_nchw")
+              : stem_launch_kernel<&stem_wino_kernel<true, false>>(g, xf, u, scale, shift, y, side, stream, "hps_stem_winograd_pooled");
+    if (rc != HPS_OK || (rc = check_launch("hps_stem_winograd_pooled")) != HPS_OK) return rc;
+    return stem_pool_borders_launch(y, side, g, stream);
 }
 
 }  // namespace hps
@@ -831,113 +675,9 @@ extern "C" int hps_proxy_rep_phase_frames(const float* edge, const float* joints
     return check_launch("hps_proxy_rep_phase_frames");
 }
 
-static int stem_wino_launch(const float* frames, const float* u, const float* scale, const float* shift, float* y, int B, int H,
-                            int W, int opad, int relu, int ablate, hps_stream_t stream, float* side = nullptr, bool nchw = false) {
-    const bool pool = side != nullptr;
-    if (!frames || !u || !scale || !shift || !y) return bad_arg("hps_stem_winograd: null pointer");
-    if (H <= 0 || W <= 0 || (H % 32) || (W % 32)) return bad_arg("hps_stem_winograd: H and W must be multiples of 32 (8 x 8 blocks of 2 x 2-pixel tiles at stride 2)");
-    if (opad < 0) return bad_arg("hps_stem_winograd: opad");
-    if (B <= 0) return HPS_OK;
-    const int Ho = H / 2, Wo = W / 2;
-    StemGeom g;
-    g.fr_rowf = (Wo + 4) / 2 * SW_PAIR;
-    g.fr_phasef = (Ho + 4) * g.fr_rowf;
-    g.fr_imgf = 4 * g.fr_phasef;
-    g.blocks_x = Wo / 16;
-    g.blocks_img = (Ho / 16) * g.blocks_x;
-    g.n_items = B * g.blocks_img;
-    g.out_row = ((pool ? Wo / 2 : Wo) + 2 * opad) * SW_CO;       // pool: the frame of the pooled map
-    g.out_img = ((pool ? Ho / 2 : Ho) + 2 * opad) * g.out_row;
-    g.opad = opad;
-    g.relu = relu;
-    g.magic_img = sw_magic((unsigned)g.blocks_img);
-    g.magic_x = sw_magic((unsigned)g.blocks_x);
-    g.in_h = H; g.in_w = W;
-    if ((size_t)B * g.fr_imgf * 4 >= 0xffffffffull || (size_t)B * g.out_img * 4 >= 0xffffffffull)
-        return bad_arg("hps_stem_winograd: tensor exceeds the 32-bit lane offsets");
-    const size_t lds = (size_t)SW_LDS_F * sizeof(float);
-    const int pairs = (g.n_items + 1) / 2;
-    int rc = HPS_OK;
-    auto launch = [&](auto AB) {
-        constexpr int ab = decltype(AB)::value;
-        if ((rc = grant_lds<&stem_wino_kernel<ab>>((int)lds, "hps_stem_winograd")) != HPS_OK) return;
-        hipLaunchKernelGGL((stem_wino_kernel<ab>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                           frames, u, scale, shift, y, (float*)nullptr, g);
-    };
-    if (pool) {
-        if (ablate != 0 && !(nchw && ablate >= 8 && ablate <= 13)) return bad_arg("hps_stem_winograd_pooled: no ablations");
-        if (nchw) {
-#ifdef HPS_DEV_BUILD
-            if (ablate == 12 || ablate == 13) {              // profiling: the input transform SPLIT between the waves of a channel-half pair
-                if (ablate == 12) {
-                    if ((rc = grant_lds<&stem_wino_kernel<12, true, true>>((int)lds, "hps_dev_stem_winograd_pooled_nchw")) != HPS_OK) return rc;
-                    hipLaunchKernelGGL((stem_wino_kernel<12, true, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                                       frames, u, scale, shift, y, side, g);
-                } else {
-                    if ((rc = grant_lds<&stem_wino_kernel<13, true, true>>((int)lds, "hps_dev_stem_winograd_pooled_nchw")) != HPS_OK) return rc;
-                    hipLaunchKernelGGL((stem_wino_kernel<13, true, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                                       frames, u, scale, shift, y, side, g);
-                }
-                return check_launch("hps_dev_stem_winograd_pooled_nchw");
-            }
-            if (ablate == 10 || ablate == 11) {              // profiling: the duplicate input transform removed (see the kernel)
-                if (ablate == 10) {
-                    if ((rc = grant_lds<&stem_wino_kernel<10, true, true>>((int)lds, "hps_dev_stem_winograd_pooled_nchw")) != HPS_OK) return rc;
-                    hipLaunchKernelGGL((stem_wino_kernel<10, true, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                                       frames, u, scale, shift, y, side, g);
-                } else {
-                    if ((rc = grant_lds<&stem_wino_kernel<11, true, true>>((int)lds, "hps_dev_stem_winograd_pooled_nchw")) != HPS_OK) return rc;
-                    hipLaunchKernelGGL((stem_wino_kernel<11, true, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                                       frames, u, scale, shift, y, side, g);
-                }
-                return check_launch("hps_dev_stem_winograd_pooled_nchw");
-            }
-            if (ablate == 8 || ablate == 9) {                // profiling: the gather without its loads / without its LDS stores (results are garbage)
-                if (ablate == 8) {
-                    if ((rc = grant_lds<&stem_wino_kernel<8, true, true>>((int)lds, "hps_dev_stem_winograd_pooled_nchw")) != HPS_OK) return rc;
-                    hipLaunchKernelGGL((stem_wino_kernel<8, true, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                                       frames, u, scale, shift, y, side, g);
-                } else {
-                    if ((rc = grant_lds<&stem_wino_kernel<9, true, true>>((int)lds, "hps_dev_stem_winograd_pooled_nchw")) != HPS_OK) return rc;
-                    hipLaunchKernelGGL((stem_wino_kernel<9, true, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                                       frames, u, scale, shift, y, side, g);
-                }
-                return check_launch("hps_dev_stem_winograd_pooled_nchw");
-            }
-#endif
-            if ((rc = grant_lds<&stem_wino_kernel<0, true, true>>((int)lds, "hps_stem_winograd_pooled_nchw")) != HPS_OK) return rc;
-            hipLaunchKernelGGL((stem_wino_kernel<0, true, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                               frames, u, scale, shift, y, side, g);
-        } else {
-            if ((rc = grant_lds<&stem_wino_kernel<0, true>>((int)lds, "hps_stem_winograd_pooled")) != HPS_OK) return rc;
-            hipLaunchKernelGGL((stem_wino_kernel<0, true>), dim3((unsigned)(pairs < 256 ? pairs : 256)), dim3(512), lds, (hipStream_t)stream,
-                               frames, u, scale, shift, y, side, g);
-        }
-        if ((rc = check_launch("hps_stem_winograd_pooled")) != HPS_OK) return rc;
-        const long total = (long)g.n_items * 15 * 16;
-        hipLaunchKernelGGL(stem_pool_borders_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, y, side, g, total);
-        return check_launch("hps_stem_winograd_pooled (borders)");
-    }
-    switch (ablate) {
-        case 0: launch(std::integral_constant<int, 0>()); break;
-#ifdef HPS_DEV_BUILD
-        case 1: launch(std::integral_constant<int, 1>()); break;
-        case 2: launch(std::integral_constant<int, 2>()); break;
-        case 3: launch(std::integral_constant<int, 3>()); break;
-        case 4: launch(std::integral_constant<int, 4>()); break;
-        case 5: launch(std::integral_constant<int, 5>()); break;
-        case 6: launch(std::integral_constant<int, 6>()); break;
-        case 7: launch(std::integral_constant<int, 7>()); break;
-#endif
-        default: return bad_arg("hps_stem_winograd: ablate");
-    }
-    if (rc != HPS_OK) return rc;
-    return check_launch("hps_stem_winograd");
-}
-
 extern "C" int hps_stem_winograd(const float* frames, const float* u, const float* scale, const float* shift, float* y, int B, int H,
                                  int W, int opad, int relu, hps_stream_t stream) {
-    return stem_wino_launch(frames, u, scale, shift, y, B, H, W, opad, relu, 0, stream);
+    return stem_wino_launch(frames, u, scale, shift, y, nullptr, B, H, W, opad, relu, false, false, stream);
 }
 
 extern "C" size_t hps_stem_pool_side_bytes(int B, int H, int W) {
@@ -948,23 +688,12 @@ extern "C" size_t hps_stem_pool_side_bytes(int B, int H, int W) {
 extern "C" int hps_stem_winograd_pooled(const float* frames, const float* u, const float* scale, const float* shift, float* pooled, float* side,
                                         int B, int H, int W, int opad, int relu, hps_stream_t stream) {
     if (!side) return bad_arg("hps_stem_winograd_pooled: null pointer");
-    return stem_wino_launch(frames, u, scale, shift, pooled, B, H, W, opad, relu, 0, stream, side);
+    return stem_wino_launch(frames, u, scale, shift, pooled, side, B, H, W, opad, relu, true, false, stream);
 }
 
 extern "C" int hps_stem_winograd_pooled_nchw(const float* x, const float* u, const float* scale, const float* shift, float* pooled, float* side,
                                              int B, int H, int W, int opad, int relu, hps_stream_t stream) {
     if (!side) return bad_arg("hps_stem_winograd_pooled_nchw: null pointer");
     if ((size_t)B * SW_C * H * W * 4 >= 0x7fffffffull * 4) return bad_arg("hps_stem_winograd_pooled_nchw: input too large");
-    return stem_wino_launch(x, u, scale, shift, pooled, B, H, W, opad, relu, 0, stream, side, true);
+    return stem_wino_launch(x, u, scale, shift, pooled, side, B, H, W, opad, relu, true, true, stream);
 }
-
-#ifdef HPS_DEV_BUILD
-extern "C" int hps_dev_stem_winograd_pooled_nchw(const float* x, const float* u, const float* scale, const float* shift, float* pooled, float* side,
-                                                 int B, int H, int W, int opad, int relu, int ablate, hps_stream_t stream) {
-    return stem_wino_launch(x, u, scale, shift, pooled, B, H, W, opad, relu, ablate, stream, side, true);
-}
-extern "C" int hps_dev_stem_winograd(const float* frames, const float* u, const float* scale, const float* shift, float* y, int B,
-                                     int H, int W, int opad, int relu, int ablate, hps_stream_t stream) {
-    return stem_wino_launch(frames, u, scale, shift, y, B, H, W, opad, relu, ablate, stream);
-}
-#endif

@@ -119,7 +119,11 @@ int hps_dev_mesh_lds_floor(int bytes);
 /* Experiment hook: K slices of hps_conv3x3_winograd's 8 x 8 geometry (0 = the product rule: four when >= 32 chunks).  Also changes
  * hps_conv3x3_winograd_workspace's answer. */
 int hps_dev_wino_quad_ksplit(int ks);
-/* profiling: hps_stem_winograd_pooled_nchw with ablate = 8 (no gather loads) / 9 (no window stores); 0 = the product */
+/* hps_stem_winograd_pooled_nchw's kernel (ablate = 0: the product's own code, csrc/stem_wino.hip, border pass included) or one of its
+ * profiling ablations (stem_wino_ablate_kernel, csrc/stem_wino_dev.hip; timing only, results are wrong by construction, no border pass):
+ * 8 = no gather loads, 9 = no window stores, 10 = one wave of each channel-half pair skips the input transform, 11 = ... and reads its
+ * 45 operands from LDS behind a second barrier per row, 12 = the transform split between the pair's waves without an exchange,
+ * 13 = ... + 23 LDS stores, 23 LDS reads per lane and row and a second barrier.  Every other number is a bad argument. */
 int hps_dev_stem_winograd_pooled_nchw(const float* x, const float* u, const float* scale, const float* shift, float* pooled, float* side,
                                       int B, int H, int W, int opad, int relu, int ablate, hps_stream_t stream);
 /* experiment: Winograd layer on half items (4 x 8 tiles), two four-wave workgroups per CU; u4 = the half-chunk packing of the filters */
@@ -161,8 +165,10 @@ int hps_dev_conv3x3_winograd(const float* x, const float* u, const float* scale,
                              const float* residual, float* y, int B, int H, int W, int ipad, int Cin, int Cout,
                              int opad, int relu, float* splitk_ws, int ablate, hps_stream_t stream);
 
-/* hps_stem_winograd with a profiling ablation (csrc/stem_wino.hip: 1 = patch pixels not read, 2 = no MFMAs, 3 = no output
- * transform, 4 = no barriers, 5 = no filter fragment reads; results are wrong by construction). */
+/* hps_stem_winograd's kernel (ablate = 0: the product's own code, csrc/stem_wino.hip) or one of its profiling ablations
+ * (stem_wino_ablate_kernel, csrc/stem_wino_dev.hip, where the table of forms is): 1 = patch pixels not read, 2 = no MFMAs, 3 = no output
+ * transform, 4 = no barriers, 5 = no filter fragment reads, 6 = no stores -- results are wrong by construction -- and 7 = each channel
+ * pair as two 4-byte LDS reads (identical results).  Every other number is a bad argument. */
 int hps_dev_stem_winograd(const float* frames, const float* u, const float* scale, const float* shift, float* y, int B, int H,
                           int W, int opad, int relu, int ablate, hps_stream_t stream);
 

@@ -19,7 +19,7 @@ sec "tests/dev/stem_ablate.py (stem convolution alone, modes interleaved over 9 
 python $R/tests/dev/stem_ablate.py 0 1 3 5 13 2>&1 | grep "^stem"
 sec "tests/dev/stem_wino_check.py (Winograd stem against an fp64 convolution and the direct kernel; both alone, B = 64 and 16)"
 PYTHONPATH=$R python $R/tests/dev/stem_wino_check.py 2>&1 | grep -E "^B=|median"
-sec "tests/dev/stem_wino_ablate.py (Winograd stem, modes interleaved over 9 rounds: 0 = product, 1 = window pixels not read, 2 = no MFMAs, 3 = no output transform, 4 = no barriers, 5 = no filter fragment reads)"
+sec "tests/dev/stem_wino_ablate.py (Winograd stem, modes interleaved over 9 rounds; csrc/stem_wino_dev.hip: 0 = product, 1 = window pixels not read, 2 = no MFMAs, 3 = no output transform, 4 = no barriers, 5 = no filter fragment reads)"
 PYTHONPATH=$R python $R/tests/dev/stem_wino_ablate.py 2>&1 | grep "^stem"
 sec "tools/bin/mfma_valu_ops (which VALU instructions cost MFMA time, alone / same wave / other wave of the SIMD; cost of alternating MFMA and VALU runs)"
 $R/tools/bin/mfma_valu_ops 2>&1 | grep -E "^v_"

@@ -14,7 +14,7 @@ out = os.environ.get("GRAFT_REPO_ROOT", os.getcwd()) + "/gpurun_out/stempmc"
 for f in sorted(glob.glob(out + "/**/*counter_collection.csv", recursive=True)):
     acc = collections.defaultdict(list)
     for r in csv.DictReader(open(f)):
-        if "stem_wino_kernel" in r["Kernel_Name"]:
+        if "stem_wino_kernel" in r["Kernel_Name"] or "stem_wino_ablate_kernel" in r["Kernel_Name"]:      # mode 0 / a non-zero mode (csrc/stem_wino_dev.hip)
             acc[r["Counter_Name"]].append(float(r["Counter_Value"]))
     for k, v in sorted(acc.items()):
         print("%-32s n=%3d  mean %.4g" % (k, len(v), sum(v) / len(v)))
