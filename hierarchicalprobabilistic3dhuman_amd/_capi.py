@@ -172,6 +172,19 @@ _PROTOTYPES = {
     "hps_keypoints_scale_round": [_P, _P, _P, _P, _I, _I, _P],
     "hps_sizeof_eval_heatmaps_args": [],
     "hps_eval_heatmaps": [_P, _P],
+    "hps_sizeof_det_transform_args": [],
+    "hps_det_transform": [_P, _P],
+    "hps_det_subsample2": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "hps_sizeof_det_rpn_decode_args": [],
+    "hps_det_rpn_decode": [_P, _P],
+    "hps_sizeof_det_nms_args": [],
+    "hps_det_nms": [_P, _P],
+    "hps_sizeof_det_roi_align_args": [],
+    "hps_det_roi_align": [_P, _P],
+    "hps_sizeof_det_box_decode_args": [],
+    "hps_det_box_decode": [_P, _P],
+    "hps_sizeof_det_gather_args": [],
+    "hps_det_gather": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -410,6 +423,56 @@ class EvalHeatmapsArgs(_c.Structure):
     _fields_ = [(n, _I) for n in ("struct_bytes", "B", "K", "wh", "use_threshold")] + [("std", _c.c_float), ("always_visible", _c.c_uint32),
                                                                                        ("threshold", _c.c_double)] + [
         (n, _P) for n in ("positions", "keypoints", "out")]
+
+
+DET_MAX_IMAGES, DET_MAX_ANCHORS, DET_MAX_LEVELS, DET_NMS_MAX_BOXES = 64, 8, 4, 2048
+
+
+class DetImage(_c.Structure):
+    """include/hps.h: hps_det_image."""
+    _fields_ = [("src", _P), ("H", _I), ("W", _I), ("oh", _I), ("ow", _I)]
+
+
+class DetTransformArgs(_c.Structure):
+    """include/hps.h: hps_det_transform_args (struct_bytes = ctypes.sizeof(DetTransformArgs); the library rejects any other value)."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "FH", "FW", "P")] + [("mean", _c.c_float * 3), ("std", _c.c_float * 3), ("y", _P),
+                                                                            ("image", DetImage * DET_MAX_IMAGES)]
+
+
+class DetRpnDecodeArgs(_c.Structure):
+    """include/hps.h: hps_det_rpn_decode_args."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "h", "w", "A", "k", "n_out", "out_offset")] + [
+        (n, _c.c_float) for n in ("stride_h", "stride_w", "min_size")] + [("base", (_c.c_float * 4) * DET_MAX_ANCHORS)] + [
+        (n, _P) for n in ("deltas", "index", "logits", "boxes", "scores")] + [("size", (_I * 2) * DET_MAX_IMAGES)]
+
+
+class DetNmsArgs(_c.Structure):
+    """include/hps.h: hps_det_nms_args."""
+    _fields_ = [("struct_bytes", _I), ("G", _I), ("N", _I), ("thresh", _c.c_float)] + [(n, _P) for n in ("boxes", "order", "scores", "keep_scores")]
+
+
+class DetLevel(_c.Structure):
+    """include/hps.h: hps_det_level."""
+    _fields_ = [("x", _P), ("h", _I), ("w", _I), ("pad", _I), ("scale", _c.c_float)]
+
+
+class DetRoiAlignArgs(_c.Structure):
+    """include/hps.h: hps_det_roi_align_args."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "R", "C", "bins", "n_levels")] + [("level", DetLevel * DET_MAX_LEVELS)] + [
+        (n, _P) for n in ("boxes", "scores", "y")]
+
+
+class DetBoxDecodeArgs(_c.Structure):
+    """include/hps.h: hps_det_box_decode_args."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "R", "NC")] + [("score_thresh", _c.c_float), ("min_size", _c.c_float)] + [
+        (n, _P) for n in ("logits", "deltas", "proposals", "prop_scores", "boxes", "scores", "probs")] + [("size", (_I * 2) * DET_MAX_IMAGES)]
+
+
+class DetGatherArgs(_c.Structure):
+    """include/hps.h: hps_det_gather_args."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "B", "D", "R", "NC")] + [
+        (n, _P) for n in ("top_scores", "top_index", "order", "boxes", "out_boxes", "out_labels", "out_scores", "counts")] + [
+        ("size", (_I * 4) * DET_MAX_IMAGES)]
 
 
 C16_MAX_PROBLEMS, HRNET_MAX_TERMS = 4, 4

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libhps.so")
 DEV_LIB_PATH = os.path.join(PKG_DIR, "libhps_dev.so")
 
 SOURCES = ["api.hip", "smpl.hip", "blend_gemm.hip", "mesh_fused.hip", "mesh_split.hip", "mf_sample.hip", "head.hip", "conv_pad.hip", "conv_expand_down.hip", "conv_wino.hip", "stem_wino.hip", "composite.hip",
-           "host_svd.hip", "frontend.hip", "metrics.hip", "mf_loss.hip", "smpl_backward.hip", "head_backward.hip", "conv_backward.hip", "conv1x1_backward.hip", "bn_train.hip", "train_frontend.hip", "optim.hip", "render.hip", "visualise.hip", "conv_c16.hip", "hrnet.hip", "predict_frontend.hip", "data_layer.hip", "png.hip", "jpeg.hip", "jpeg_encode.hip"]
+           "host_svd.hip", "frontend.hip", "metrics.hip", "mf_loss.hip", "smpl_backward.hip", "head_backward.hip", "conv_backward.hip", "conv1x1_backward.hip", "bn_train.hip", "train_frontend.hip", "optim.hip", "render.hip", "visualise.hip", "conv_c16.hip", "hrnet.hip", "predict_frontend.hip", "data_layer.hip", "png.hip", "jpeg.hip", "jpeg_encode.hip", "detector.hip"]
 DEV_ONLY_SOURCES = ["conv.hip", "conv_wino_dev.hip", "stem_wino_dev.hip"]
 # per-file flags.  mesh_fused.hip: hipcc's SLP vectoriser turns the skinning epilogue into v_pk_fma_f32 plus one v_mov
 # per packed operand (525 moves, 2 051 instructions); unpacked it is 1 963 instructions with 109 moves, and packed fp32

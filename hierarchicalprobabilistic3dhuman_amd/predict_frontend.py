@@ -7,8 +7,8 @@ proxy-representation size, Canny edges and heat maps -- with one HRNet forward p
     out["proxy_rep"]                               # (B,18,D,D): the network's input
 
 Launches per batch: hps_predict_boxes, hps_crop_bilinear, the HRNet forward, hps_hrnet_keypoints, hps_crop_bilinear for the proxy size
-(its static box records are formed once and kept), hps_canny_edge_map and hps_proxy_rep.  The person detector stays an injected
-per-image callable (its synchronisation is its own).  The functions ``predict_boxes`` / ``crop_bilinear`` / ``hrnet_keypoints`` are
+(its static box records are formed once and kept), hps_canny_edge_map and hps_proxy_rep.  The person detector is an injected
+per-image callable (its synchronisation is its own); ``detection.maskrcnn_resnet50_fpn()`` is the device implementation.  The functions ``predict_boxes`` / ``crop_bilinear`` / ``hrnet_keypoints`` are
 the three kernels on their own.
 """
 import ctypes

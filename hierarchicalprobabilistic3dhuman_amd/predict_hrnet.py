@@ -1,7 +1,8 @@
 """2D keypoint prediction front end with the call surface of the reference's predict/predict_hrnet.py: person box ->
 crop to the HRNet input -> injected ``hrnet_model`` -> heat-map arg-max.  The detectors stay injected objects (any callables with
 the reference's interfaces); this module is the per-image torch glue between them and the proxy representation.  The device
-implementation of the keypoint detector is ``pose2D_hrnet.PoseHighResolutionNet``; the person detector (Mask R-CNN) is out of scope.
+implementation of the keypoint detector is ``pose2D_hrnet.PoseHighResolutionNet``, that of the person detector (Mask R-CNN's box path)
+``detection.maskrcnn_resnet50_fpn()``.
 The batched device form of this front end -- box selection, crop and arg-max as libhps kernels, one HRNet forward per batch -- is
 ``predict_frontend.DevicePredictFrontEnd``; ``predict_hrnet`` itself keeps the reference's one-image behaviour."""
 import torch

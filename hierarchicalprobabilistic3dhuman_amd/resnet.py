@@ -788,6 +788,39 @@ class ResNet(DeviceStateModule):
         # frame (hps_nchw_to_padded_nhwc_generic) in front of the row-mode / direct stem
         return self._forward_padded(prep, _capi.f32c(x), gate=_gate)
 
+    def stage_taps(self, shape, device, x=None, fill=None):
+        """The outputs of layer1..4 (C2..C5 of a feature pyramid, strides 4, 8, 16, 32) for a (B, C, H, W) input: the existing launch
+        plan of ``forward`` without its closing average pool, handed back as the four block-output frames themselves -- halo-padded NHWC
+        (B, h + 2, w + 2, c), zero halo -- which belong to the module: read them, never write them, and copy what must outlive the
+        next forward of this shape on this stream.  Read-only: no launch is added for any other caller and ``forward`` keeps its bits.
+        ``x``: the NCHW input; or ``fill(frame)``, a callable that writes the interior of the direct stem's input frame
+        (B, H + 6, W + 6, row channels; channels past C and the halo stay zero) in the input relayout's place -- for shapes whose stem
+        reads such a frame (not the Winograd stem of the 18-channel model).  Eval-mode BatchNorm, no autograd."""
+        if self._train_flags() is not None:
+            raise RuntimeError("stage_taps runs eval-mode BatchNorm only")
+        B, C, H, W = shape
+        prep = self._current_prep()
+        fs = self._frame_set(prep, B, C, H, W, device)
+        ops = fs["ops"]
+        n = len(ops) - 1                                   # the average pool closes the list: not run
+        if x is not None:
+            _capi.require_device(x, "encoder input")
+            xc = _capi.f32c(x.detach())
+            if tuple(xc.shape) != tuple(shape):
+                raise _capi.HpsError("stage_taps: the input is %s, not %s" % (tuple(xc.shape), tuple(shape)))
+            ops[0].x = xc.data_ptr()
+            _capi.run_enc_ops(ops, 0, n, self.composite)
+        else:
+            if fill is None or fs["stem_wino"] or fs.get("in") is None:
+                raise _capi.HpsError("stage_taps: give the input, or fill() for a shape whose stem reads a padded NHWC frame")
+            fill(fs["in"])
+            _capi.run_enc_ops(ops, 1, n - 1, self.composite)
+        last, taps = -1, []
+        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+            last += len(layer)
+            taps.append(fs["blocks"][last]["out"])
+        return taps
+
     # ---- training-mode BatchNorm (csrc/bn_train.hip) ----
     def _train_flags(self):
         """None when every BatchNorm runs on running statistics, else {layer name: its BatchNorm is training} over _enc_layers().

@@ -1940,6 +1940,152 @@ typedef struct hps_eval_heatmaps_args {
 int hps_sizeof_eval_heatmaps_args(void);
 int hps_eval_heatmaps(const hps_eval_heatmaps_args* args /* HOST */, hps_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Person detector: the box path of Mask R-CNN (ResNet-50-FPN)  (csrc/detector.hip; run_predict.py:43, predict/predict_hrnet.py:52-57)
+ * ---------------------------------------------------------------------------------------- */
+
+/* The detection-specific launches of detection.MaskRCNNBoxDetector; the convolutions and FC layers are hps_conv2d_bn_act_pad /
+ * hps_conv3x3_winograd (backbone), hps_conv2d_bn_act_c16 (FPN, RPN head, box head) and hps_hrnet_fuse (FPN's top-down sum).  The
+ * semantics restate torchvision 0.7.0's detection code as we understand it; they have NOT been run against torchvision.  fp32, no
+ * atomics, nothing allocated, no host synchronisation: capacities are the caller's, an ABSENT row is marked by a score of -infinity
+ * (its box is zero) and is skipped by every later launch.  Per-image sizes go by value (HOST structs), at most HPS_DET_MAX_IMAGES
+ * images per launch.  An image's values depend on its own descriptor only: same bits alone and in a batch. */
+#define HPS_DET_MAX_IMAGES 64
+#define HPS_DET_MAX_ANCHORS 8
+#define HPS_DET_MAX_LEVELS 4
+#define HPS_DET_NMS_MAX_BOXES 2048
+
+/* hps_det_transform  (GeneralizedRCNNTransform: normalise, resize, batch): image b, (3, H, W) float32 CHW, -> the interior of the
+ * stem's zero-haloed NHWC frame y (B, FH + 2 P, FW + 2 P, 4): channels (x - mean[c]) / std[c] resampled bilinearly (align_corners =
+ * False) to (oh, ow) at the frame's top-left corner, channel 3 and every interior pixel outside (oh, ow) zero, one 16-byte store per
+ * pixel.  Source coordinate of output row i: max((i + 1/2) (H / oh) - 1/2, 0) with the quotient in fp32, y0 = min(int(.), H - 1),
+ * y1 = min(y0 + 1, H - 1), l = coordinate - y0; value (1 - ly) ((1 - lx) a + lx b) + ly ((1 - lx) c + lx d).  oh <= FH, ow <= FW. */
+typedef struct hps_det_image {
+    const float* src;                                          /* (3, H, W) */
+    int H, W, oh, ow;
+} hps_det_image;
+typedef struct hps_det_transform_args {
+    int struct_bytes;
+    int B, FH, FW, P;
+    float mean[3], std[3];
+    float* y;
+    hps_det_image image[HPS_DET_MAX_IMAGES];
+} hps_det_transform_args;
+int hps_sizeof_det_transform_args(void);
+int hps_det_transform(const hps_det_transform_args* args /* HOST */, hps_stream_t stream);
+
+/* LastLevelMaxPool (a max pool with kernel 1 and stride 2): y's interior (B, (H + 1) / 2, (W + 1) / 2, C) = x's interior at (2 i, 2 j);
+ * frames with ipad / opad halos, C % 4 == 0. */
+int hps_det_subsample2(const float* x, float* y, int B, int H, int W, int C, int ipad, int opad, hps_stream_t stream);
+
+/* hps_det_rpn_decode  (AnchorGenerator, BoxCoder.decode with weights (1, 1, 1, 1), clip_boxes_to_image, remove_small_boxes) for one
+ * level's k candidates per image: index (B, k) int64 into the level's (h, w, A) logits in the frame's own order, logits (B, k) their
+ * values.  Candidate j: a = index % A, x = (index / A) % w, y = index / (A w); anchor = base[a] + (x stride_w, y stride_h, x stride_w,
+ * y stride_h); deltas (B, h, w, 4 A) at channel 4 a + (dx, dy, dw, dh), dw and dh held to <= log(1000 / 16);
+ * cx = dx w + ctr_x, pw = exp(dw) w, box = cx -+ pw / 2 (likewise y), clipped to [0, rw] x [0, rh] of ITS image's resized size.
+ * Row out_offset + j of boxes (B, n_out, 4) / scores (B, n_out): the box and its logit, or zeros and -infinity when the clipped box
+ * is narrower or lower than min_size or the index is out of range. */
+typedef struct hps_det_rpn_decode_args {
+    int struct_bytes;
+    int B, h, w, A, k, n_out, out_offset;
+    float stride_h, stride_w, min_size;
+    float base[HPS_DET_MAX_ANCHORS][4];
+    const float* deltas;
+    const int64_t* index;
+    const float* logits;
+    float* boxes;
+    float* scores;
+    int size[HPS_DET_MAX_IMAGES][2];                           /* resized (h, w) per image */
+} hps_det_rpn_decode_args;
+int hps_sizeof_det_rpn_decode_args(void);
+int hps_det_rpn_decode(const hps_det_rpn_decode_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_det_nms: greedy non-maximum suppression inside each of G independent groups (one category of one image: an FPN level for the
+ * proposals, a class for the detections -- the categories are never mixed, no coordinate offsets).  Position i of group g is box
+ * boxes[g, order[g, i]] (order NULL: i itself) with score scores[g, i]; the caller has sorted the positions by descending score
+ * (absent ones, -infinity, may sit anywhere).  Walking i upwards, a present position that is still alive is kept and removes every
+ * later alive position t with inter / (area_i + area_t - inter) > thresh, inter = max(min(x2) - max(x1), 0) max(min(y2) - max(y1), 0),
+ * area = (x2 - x1) (y2 - y1), all fp32 (0 / 0 is not greater: kept).  keep_scores (G, N) = the score where kept, else -infinity.
+ * One workgroup per group, the group's boxes in LDS: N <= HPS_DET_NMS_MAX_BOXES. */
+typedef struct hps_det_nms_args {
+    int struct_bytes;
+    int G, N;
+    float thresh;
+    const float* boxes;                                        /* (G, N, 4) */
+    const int64_t* order;                                      /* (G, N) or NULL */
+    const float* scores;                                       /* (G, N) */
+    float* keep_scores;                                        /* (G, N) */
+} hps_det_nms_args;
+int hps_sizeof_det_nms_args(void);
+int hps_det_nms(const hps_det_nms_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_det_roi_align  (MultiScaleRoIAlign: LevelMapper(k_min 2, canonical scale 224, canonical level 4, eps 1e-6) and roi_align with a
+ * bins x bins output, sampling_ratio 2, aligned = False): box r of image b, boxes (B, R, 4) in resized-image pixels, present where
+ * scores (B, R) > -infinity, reads level clamp(floor(4 + log2(sqrt(area) / 224 + 1e-6)), 2, 1 + n_levels) - 2 of image b's zero-haloed
+ * NHWC frames level[.].x (B, h + 2 pad, w + 2 pad, C).  start = x1 scale, roi_w = max(x2 scale - x1 scale, 1), bin = roi_w / bins,
+ * samples at start + p bin + (i + 1/2) bin / 2, i = 0, 1 (likewise y); a sample with y < -1, y > h, x < -1 or x > w is 0, else it is held
+ * to >= 0, low = int(.), and low >= h - 1 reads row h - 1 twice with fraction 0; the bin is the mean of its four samples, each
+ * (1-ly)(1-lx) v1 + (1-ly) lx v2 + ly (1-lx) v3 + ly lx v4.  y (B, R, bins, bins, C): channel fastest (the order the box head's first
+ * layer is permuted to); an absent box writes zeros.  C % 4 == 0 not required. */
+typedef struct hps_det_level {
+    const float* x;
+    int h, w, pad;
+    float scale;
+} hps_det_level;
+typedef struct hps_det_roi_align_args {
+    int struct_bytes;
+    int B, R, C, bins, n_levels;
+    hps_det_level level[HPS_DET_MAX_LEVELS];
+    const float* boxes;
+    const float* scores;
+    float* y;
+} hps_det_roi_align_args;
+int hps_sizeof_det_roi_align_args(void);
+int hps_det_roi_align(const hps_det_roi_align_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_det_box_decode  (RoIHeads.postprocess_detections up to the per-class NMS): logits (B, R, NC), deltas (B, R, 4 NC), proposals
+ * (B, R, 4) present where prop_scores (B, R) > -infinity.  prob = exp(l_c - max) / sum_c' exp(l_c' - max) (sum in class order);
+ * class c >= 1: BoxCoder.decode with weights (10, 10, 5, 5) (dx = d / 10, ..., dw = d / 5 held to <= log(1000 / 16)) from the proposal,
+ * clipped to the image's resized size.  Row (b, c - 1, r) of boxes (B, NC - 1, R, 4) / scores (B, NC - 1, R): the box and prob where
+ * the proposal is present, prob > score_thresh and the clipped box is at least min_size wide and high, else zeros and -infinity.
+ * probs (B, R, NC), when not NULL, receives every probability. */
+typedef struct hps_det_box_decode_args {
+    int struct_bytes;
+    int B, R, NC;
+    float score_thresh, min_size;
+    const float* logits;
+    const float* deltas;
+    const float* proposals;
+    const float* prop_scores;
+    float* boxes;
+    float* scores;
+    float* probs;                                              /* or NULL */
+    int size[HPS_DET_MAX_IMAGES][2];                           /* resized (h, w) per image */
+} hps_det_box_decode_args;
+int hps_sizeof_det_box_decode_args(void);
+int hps_det_box_decode(const hps_det_box_decode_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_det_gather: the D best detections of each image after the per-class NMS.  top_scores / top_index (B, D): a descending top-k of
+ * the kept scores over (NC - 1, R) sorted positions; position (c - 1, p) is proposal r = order[b, c - 1, p].  Row d of out_boxes
+ * (B, D, 4): boxes[b, c - 1, r] with x times float(ow) / float(rw) and y times float(oh) / float(rh) (back to the input image's
+ * pixels); out_labels (B, D) int64 = c; out_scores (B, D); absent rows (-infinity) are zeros with label 0 and score 0.
+ * counts (B) int32 = the number of present rows (they come first). */
+typedef struct hps_det_gather_args {
+    int struct_bytes;
+    int B, D, R, NC;
+    const float* top_scores;
+    const int64_t* top_index;
+    const int64_t* order;                                      /* (B, NC - 1, R) */
+    const float* boxes;                                        /* (B, NC - 1, R, 4) */
+    float* out_boxes;
+    int64_t* out_labels;
+    float* out_scores;
+    int32_t* counts;
+    int size[HPS_DET_MAX_IMAGES][4];                           /* resized (h, w), original (h, w) per image */
+} hps_det_gather_args;
+int hps_sizeof_det_gather_args(void);
+int hps_det_gather(const hps_det_gather_args* args /* HOST */, hps_stream_t stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }
