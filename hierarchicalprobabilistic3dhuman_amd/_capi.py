@@ -181,10 +181,15 @@ _PROTOTYPES = {
     "hps_det_nms": [_P, _P],
     "hps_sizeof_det_roi_align_args": [],
     "hps_det_roi_align": [_P, _P],
+    "hps_det_roi_align_halo": [_P, _I, _P],
     "hps_sizeof_det_box_decode_args": [],
     "hps_det_box_decode": [_P, _P],
     "hps_sizeof_det_gather_args": [],
     "hps_det_gather": [_P, _P],
+    "hps_sizeof_det_mask_predict_args": [],
+    "hps_det_mask_predict": [_P, _P],
+    "hps_sizeof_det_paste_masks_args": [],
+    "hps_det_paste_masks": [_P, _P],
 }
 _RESTYPES = {"hps_last_error": _c.c_char_p, "hps_smpl_split_bf16x3_bytes": _c.c_size_t, "hps_query_workspace": _c.c_int64, "hps_conv3x3_winograd_workspace": _c.c_size_t,
              "hps_stem_phase_frames_bytes": _c.c_size_t, "hps_stem_pool_side_bytes": _c.c_size_t,
@@ -473,6 +478,20 @@ class DetGatherArgs(_c.Structure):
     _fields_ = [(n, _I) for n in ("struct_bytes", "B", "D", "R", "NC")] + [
         (n, _P) for n in ("top_scores", "top_index", "order", "boxes", "out_boxes", "out_labels", "out_scores", "counts")] + [
         ("size", (_I * 4) * DET_MAX_IMAGES)]
+
+
+DET_MASK_BINS, DET_MASK_CHANNELS, DET_MASK_SIZE = 14, 256, 28
+
+
+class DetMaskPredictArgs(_c.Structure):
+    """include/hps.h: hps_det_mask_predict_args."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "K", "NC")] + [
+        (n, _P) for n in ("x", "wd", "bd", "wl", "bl", "labels", "scores", "probs", "logits")]
+
+
+class DetPasteMasksArgs(_c.Structure):
+    """include/hps.h: hps_det_paste_masks_args."""
+    _fields_ = [(n, _I) for n in ("struct_bytes", "n", "H", "W", "binary")] + [("threshold", _c.c_float)] + [(n, _P) for n in ("probs", "boxes", "out")]
 
 
 C16_MAX_PROBLEMS, HRNET_MAX_TERMS = 4, 4

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(PKG_DIR, "libhps.so")
 DEV_LIB_PATH = os.path.join(PKG_DIR, "libhps_dev.so")
 
 SOURCES = ["api.hip", "smpl.hip", "blend_gemm.hip", "mesh_fused.hip", "mesh_split.hip", "mf_sample.hip", "head.hip", "conv_pad.hip", "conv_expand_down.hip", "conv_wino.hip", "stem_wino.hip", "composite.hip",
-           "host_svd.hip", "frontend.hip", "metrics.hip", "mf_loss.hip", "smpl_backward.hip", "head_backward.hip", "conv_backward.hip", "conv1x1_backward.hip", "bn_train.hip", "train_frontend.hip", "optim.hip", "render.hip", "visualise.hip", "conv_c16.hip", "hrnet.hip", "predict_frontend.hip", "data_layer.hip", "png.hip", "jpeg.hip", "jpeg_encode.hip", "detector.hip"]
+           "host_svd.hip", "frontend.hip", "metrics.hip", "mf_loss.hip", "smpl_backward.hip", "head_backward.hip", "conv_backward.hip", "conv1x1_backward.hip", "bn_train.hip", "train_frontend.hip", "optim.hip", "render.hip", "visualise.hip", "conv_c16.hip", "hrnet.hip", "predict_frontend.hip", "data_layer.hip", "png.hip", "jpeg.hip", "jpeg_encode.hip", "detector.hip", "detector_mask.hip"]
 DEV_ONLY_SOURCES = ["conv.hip", "conv_wino_dev.hip", "stem_wino_dev.hip"]
 # per-file flags.  mesh_fused.hip: hipcc's SLP vectoriser turns the skinning epilogue into v_pk_fma_f32 plus one v_mov
 # per packed operand (525 moves, 2 051 instructions); unpacked it is 1 963 instructions with 109 moves, and packed fp32
@@ -39,12 +39,15 @@ DEV_ONLY_SOURCES = ["conv.hip", "conv_wino_dev.hip", "stem_wino_dev.hip"]
 # utils/image_utils.py:310-334) and is held to them bit for bit; the resample is held to a float32 restatement that rounds every product.
 # data_layer.hip: the crop's matrix and joints repeat NumPy's float64 operations one by one (utils/image_utils.py:191-194, :212-214), the heat
 # map the float32 ones (utils/label_conversions.py:101); the resize and the warp are integer arithmetic.
+# detector_mask.hip: the paste's box repeats torchvision's float32 tensor operations one by one (expand_boxes: a product and a sum are two
+# roundings), and its integer corners are a truncation of the result.
 # optim.hip: the refreshed BatchNorm fold repeats _ConvBN.fold's float64 operations one by one (beta - mean * scale: two roundings).
 FILE_FLAGS = {"mesh_fused.hip": ["-fno-slp-vectorize"], "mesh_split.hip": ["-fno-slp-vectorize"],
               "frontend.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-ilp"],
               "train_frontend.hip": ["-ffp-contract=off"], "optim.hip": ["-ffp-contract=off"],
               "render.hip": ["-ffp-contract=off"], "visualise.hip": ["-ffp-contract=off"],
-              "predict_frontend.hip": ["-ffp-contract=off"], "data_layer.hip": ["-ffp-contract=off"]}
+              "predict_frontend.hip": ["-ffp-contract=off"], "data_layer.hip": ["-ffp-contract=off"],
+              "detector_mask.hip": ["-ffp-contract=off"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-fvisibility=hidden",
          "-Wall", "-Wno-unused-function"]
 

@@ -164,18 +164,21 @@ struct RoiAlign {
     const float* boxes;
     const float* scores;
     float* y;
-    int R, C, bins, n_levels;
+    int R, C, bins, n_levels, halo;
 };
 
 // One workgroup per box; a thread owns channels tid, tid + 256, ... (neighbouring lanes read neighbouring NHWC floats); the sample
-// geometry is uniform over the workgroup.
+// geometry is uniform over the workgroup.  The box's output is a (bins + 2 halo)^2 frame whose border is written as zeros; blockIdx.z
+// takes an equal share of the frame's positions (one workgroup per box leaves most of the chip idle at 100 boxes of 256 positions).
 __global__ __launch_bounds__(256) void det_roi_align_kernel(const RoiAlign T) {
     const int r = blockIdx.x, b = blockIdx.y;
     const size_t row = (size_t)b * T.R + r;
-    float* y = T.y + row * (size_t)(T.bins * T.bins) * T.C;
-    const int n = T.bins * T.bins;
+    const int fb = T.bins + 2 * T.halo, n = fb * fb;
+    float* y = T.y + row * (size_t)n * T.C;
+    const int share = ceil_div(n, (int)gridDim.z);
+    const int p0 = (int)blockIdx.z * share, p1 = min(n, p0 + share);
     if (!(T.scores[row] > -INFINITY)) {
-        for (int p = 0; p < n; ++p)
+        for (int p = p0; p < p1; ++p)
             for (int c = threadIdx.x; c < T.C; c += 256) y[(size_t)p * T.C + c] = 0.0f;
         return;
     }
@@ -189,8 +192,13 @@ __global__ __launch_bounds__(256) void det_roi_align_kernel(const RoiAlign T) {
     const float bw = rw / (float)T.bins, bh = rh / (float)T.bins;
     const size_t fw = (size_t)(L.w + 2 * L.pad);
     const float* base = L.x + ((size_t)b * (L.h + 2 * L.pad) + L.pad) * fw * T.C + (size_t)L.pad * T.C;
-    for (int p = 0; p < n; ++p) {
-        const int ph = p / T.bins, pw = p - ph * T.bins;
+    for (int p = p0; p < p1; ++p) {
+        const int fy = p / fb;
+        const int ph = fy - T.halo, pw = p - fy * fb - T.halo;
+        if (ph < 0 || ph >= T.bins || pw < 0 || pw >= T.bins) {
+            for (int c = threadIdx.x; c < T.C; c += 256) y[(size_t)p * T.C + c] = 0.0f;
+            continue;
+        }
         // the four samples' taps and weights (uniform)
         size_t off[4][4];
         float wt[4][4];
@@ -414,11 +422,14 @@ extern "C" int hps_det_nms(const hps_det_nms_args* a, hps_stream_t stream) {
     return check_launch("hps_det_nms");
 }
 
-extern "C" int hps_det_roi_align(const hps_det_roi_align_args* a, hps_stream_t stream) {
+extern "C" int hps_det_roi_align(const hps_det_roi_align_args* a, hps_stream_t stream) { return hps_det_roi_align_halo(a, 0, stream); }
+
+extern "C" int hps_det_roi_align_halo(const hps_det_roi_align_args* a, int halo, hps_stream_t stream) {
     if (!a) return bad_arg("hps_det_roi_align: null pointer (args)");
     if (a->struct_bytes != (int)sizeof(hps_det_roi_align_args)) return bad_arg("hps_det_roi_align: struct_bytes does not match this library");
     if (a->B == 0 || a->R == 0) return HPS_OK;
     if (a->B < 0 || a->B > 65535 || a->R < 0 || a->C < 1 || a->bins < 1 || a->bins > 64) return bad_arg("hps_det_roi_align: sizes out of range");
+    if (halo < 0 || halo > 8) return bad_arg("hps_det_roi_align: halo out of range (0 to 8)");
     if (a->n_levels < 1 || a->n_levels > HPS_DET_MAX_LEVELS) return bad_arg("hps_det_roi_align: 1 to HPS_DET_MAX_LEVELS levels");
     if (!a->boxes || !a->scores || !a->y) return bad_arg("hps_det_roi_align: null pointer");
     if (!aligned(a->boxes, 16) || !aligned(a->scores, 4) || !aligned(a->y, 4)) return bad_arg("hps_det_roi_align: unaligned pointer (boxes 16 bytes)");
@@ -429,8 +440,8 @@ extern "C" int hps_det_roi_align(const hps_det_roi_align_args* a, hps_stream_t s
         if (s.h < 1 || s.w < 1 || s.pad < 0 || !(s.scale > 0.0f) || !std::isfinite(s.scale)) return bad_arg("hps_det_roi_align: level geometry out of range");
         T.level[l].x = s.x; T.level[l].h = s.h; T.level[l].w = s.w; T.level[l].pad = s.pad; T.level[l].scale = s.scale;
     }
-    T.boxes = a->boxes; T.scores = a->scores; T.y = a->y; T.R = a->R; T.C = a->C; T.bins = a->bins; T.n_levels = a->n_levels;
-    hipLaunchKernelGGL(det_roi_align_kernel, dim3((unsigned)a->R, (unsigned)a->B), dim3(256), 0, (hipStream_t)stream, T);
+    T.boxes = a->boxes; T.scores = a->scores; T.y = a->y; T.R = a->R; T.C = a->C; T.bins = a->bins; T.n_levels = a->n_levels; T.halo = halo;
+    hipLaunchKernelGGL(det_roi_align_kernel, dim3((unsigned)a->R, (unsigned)a->B, halo ? 8u : 1u), dim3(256), 0, (hipStream_t)stream, T);
     return check_launch("hps_det_roi_align");
 }
 

@@ -1,4 +1,4 @@
-"""Person detector: the box path of Mask R-CNN with a ResNet-50-FPN backbone, the detector the reference builds with
+"""Person detector: Mask R-CNN with a ResNet-50-FPN backbone (its box path, and opt-in its mask branch), the detector the reference builds with
 ``torchvision.models.detection.maskrcnn_resnet50_fpn(pretrained=True)`` (run_predict.py:43) and reads in one place
 (predict/predict_hrnet.py:52-57: ``boxes``, ``labels``, ``scores``).  Module tree and state-dict keys are those of the released
 ``maskrcnn_resnet50_fpn_coco`` file (strict loading; the later torchvision spelling ``inner_blocks.N.0.*`` / ``layer_blocks.N.0.*`` /
@@ -8,13 +8,28 @@
     detector.load_state_dict(torch.load("maskrcnn_resnet50_fpn_coco.pth"))
     out = detector([image_a, image_b])        # (3, H, W) float32 device tensors in [0, 1], any sizes; or one (B, 3, H, W) tensor
     out[0]["boxes"], out[0]["labels"], out[0]["scores"]          # (n, 4) x1 y1 x2 y2 in the input's pixels, (n,) int64, (n,) descending
+    out = detector([image_a, image_b], masks=True)               # opt-in: also out[0]["masks"], (n, 1, H, W) float32 probabilities
+    out = detector([image_a, image_b], masks=True, mask_threshold=0.5)          # ... or (n, 1, H, W) uint8, probability > 0.5
 
 THE SEMANTICS ARE A RESTATEMENT of torchvision 0.7.0 (the version the reference pins) written from its description; torchvision is
 not part of this stack and this restatement HAS NEVER BEEN RUN AGAINST TORCHVISION.  tests/detector_scenario.py restates the same
 stages in float64 on the CPU; the device code is held to that.
 
-Eval mode only, no backward (an input that requires grad is refused, ``.train()`` is refused).  The mask branch is held (its
-parameters load) and never computed: no ``masks`` key.  Not here: training, keypoint R-CNN, other backbones.
+Eval mode only, no backward (an input that requires grad is refused, ``.train()`` is refused).  Without ``masks=True`` the mask branch
+is held (its parameters load) and not computed: no ``masks`` key, and the call launches and allocates what the box path alone does.
+Not here: training, keypoint R-CNN, other backbones.
+
+THE MASK BRANCH (``masks=True``; the same caveat: restated from torchvision 0.7.0's description, never run against torchvision;
+tests/detector_mask_scenario.py is its float64 restatement).  ``detections(..., with_rois=True)`` also returns the detections' boxes in
+resized-image pixels -- the candidates hps_det_gather selects, before its rescale -- and their presence mark; ``mask_branch`` runs
+hps_det_roi_align_halo (MultiScaleRoIAlign over P2..P5, 14 x 14, sampling ratio 2, the box head's level mapper) into zero-haloed frames,
+the four 3x3 + ReLU layers over the B D maps of 14 x 14 on the wide kernel (K in slices of 256 products, frames and launch list cached
+like the box head's), and hps_det_mask_predict: ConvTranspose2d(256, 256, 2, 2) + ReLU, the 1x1 logit of the detection's own class and
+the sigmoid in one launch on the fp32 matrix instructions -- the (B D, 28, 28, 256) tensor (80 MB at 100 detections) is never written
+and no other class's logit is formed.  ``forward`` pastes after its one synchronisation (hps_det_paste_masks: one launch per image that
+writes every pixel of the n masks; torchvision's paste_masks_in_image with padding 1, probabilities, not thresholded).  100 float masks
+of 720 x 960 take 276 MB; the uint8 form (``mask_threshold``) takes a quarter of that.  ``detect_padded(masks=True)`` returns the
+(B, D, 28, 28) probabilities as a fifth tensor and does not synchronise.
 
 Stages (public, ``forward`` is their composition): ``features`` (hps_det_transform writes the stem's input frame; the project's
 ResNet-50 encoder with frozen statistics, tapped after layer1..4 by ``ResNet.stage_taps``; the FPN's laterals and 3x3 output layers on
@@ -213,16 +228,22 @@ def nms_per_category(boxes, scores, categories, num_categories, thresh):
     return idx[torch.argsort(sc, descending=True)]
 
 
-def multiscale_roi_align(levels, boxes, scores=None, bins=7):
+def multiscale_roi_align(levels, boxes, scores=None, bins=7, halo=0):
     """hps_det_roi_align: ``levels`` = [(frame (B, h + 2 pad, w + 2 pad, C), pad, scale)] for P2.., boxes (B, R, 4), scores (B, R) or
-    None (every box present) -> (B, R, bins * bins * C), (bin row, bin column, channel) order."""
+    None (every box present) -> (B, R, bins * bins * C), (bin row, bin column, channel) order.  With ``halo`` > 0
+    (hps_det_roi_align_halo): (B * R, bins + 2 halo, bins + 2 halo, C), the same values inside a border of zeros -- the input frames of
+    a 3x3 layer over the boxes."""
     _capi.require_device(boxes, "boxes")
     boxes = _capi.f32c(boxes)
     B, R, _ = boxes.shape
     if scores is None:
         scores = torch.zeros(B, R, device=boxes.device, dtype=torch.float32)
     C = levels[0][0].shape[3]
-    y = torch.empty(B, R, bins * bins * C, device=boxes.device, dtype=torch.float32)
+    halo = int(halo)
+    if halo:
+        y = torch.empty(B * R, bins + 2 * halo, bins + 2 * halo, C, device=boxes.device, dtype=torch.float32)
+    else:
+        y = torch.empty(B, R, bins * bins * C, device=boxes.device, dtype=torch.float32)
     a = _capi.DetRoiAlignArgs(struct_bytes=ctypes.sizeof(_capi.DetRoiAlignArgs), B=B, R=R, C=C, bins=bins, n_levels=len(levels),
                               boxes=_capi.ptr(boxes), scores=_capi.ptr(scores), y=_capi.ptr(y))
     for l, (frame, pad, scale) in enumerate(levels):
@@ -230,8 +251,70 @@ def multiscale_roi_align(levels, boxes, scores=None, bins=7):
             raise _capi.HpsError("roi_align: level %d is %s; expected batch %d and %d channels" % (l, tuple(frame.shape), B, C))
         lv = a.level[l]
         lv.x, lv.h, lv.w, lv.pad, lv.scale = _capi.ptr(frame), frame.shape[1] - 2 * pad, frame.shape[2] - 2 * pad, pad, float(scale)
-    _capi.call("hps_det_roi_align", ctypes.byref(a), _capi.stream())
+    if halo:
+        _capi.call("hps_det_roi_align_halo", ctypes.byref(a), halo, _capi.stream())
+    else:
+        _capi.call("hps_det_roi_align", ctypes.byref(a), _capi.stream())
     return y
+
+
+def _check_threshold(threshold):
+    if threshold is not None and not 0.0 < float(threshold) < 1.0:
+        raise ValueError("mask threshold %r: a probability strictly between 0 and 1 (None: the probabilities themselves)" % (threshold,))
+    return None if threshold is None else float(threshold)
+
+
+def mask_weights(conv5_weight):
+    """hps_det_mask_predict's form of ConvTranspose2d(256, 256, 2, 2).weight (ci, co, dy, dx): (4, 128, 64, 8) with element
+    [2 dy + dx][s][lane][t] = W[2 s + (lane >> 5)][32 t + (lane & 31)][dy][dx] -- a lane's eight row blocks are two 16-byte loads."""
+    w = conv5_weight.detach().float()
+    C = _capi.DET_MASK_CHANNELS
+    if tuple(w.shape) != (C, C, 2, 2):
+        raise _capi.HpsError("mask predictor: conv5_mask.weight is %s; expected (%d, %d, 2, 2)" % (tuple(w.shape), C, C))
+    w = w.permute(2, 3, 0, 1).reshape(4, C // 2, 2, C // 32, 32)              # tap, s, h, t, i
+    return w.permute(0, 1, 2, 4, 3).reshape(4, C // 2, 64, C // 32).contiguous()
+
+
+def mask_predict(frames, weights, bias, logit_weight, logit_bias, labels, scores=None, with_logits=False):
+    """hps_det_mask_predict: frames (K, 16, 16, 256) zero-haloed NHWC (the last mask-head layer's output), ``weights`` from
+    mask_weights, bias (256,), logit_weight (NC, 256), logit_bias (NC,), labels (K,) int64, scores (K,) or None (every row present) ->
+    (probs (K, 28, 28), logits (K, 28, 28) or None).  A row that is absent or has label 0 is zero."""
+    _capi.require_device(frames, "frames")
+    K, S, F, C = frames.shape[0], _capi.DET_MASK_SIZE, _capi.DET_MASK_BINS + 2, _capi.DET_MASK_CHANNELS
+    NC = logit_weight.shape[0]
+    if tuple(frames.shape) != (K, F, F, C) or tuple(weights.shape) != (4, C // 2, 64, C // 32) or tuple(bias.shape) != (C,) or \
+            tuple(logit_weight.shape) != (NC, C) or tuple(logit_bias.shape) != (NC,) or tuple(labels.shape) != (K,) or \
+            (scores is not None and tuple(scores.shape) != (K,)):
+        raise _capi.HpsError("mask_predict: frames (K, %d, %d, %d), weights (4, %d, 64, %d), bias (%d,), logit weight (NC, %d) and bias "
+                             "(NC,), labels (K,)" % (F, F, C, C // 2, C // 32, C, C))
+    probs = torch.empty(K, S, S, device=frames.device, dtype=torch.float32)
+    logits = torch.empty(K, S, S, device=frames.device, dtype=torch.float32) if with_logits else None
+    a = _capi.DetMaskPredictArgs(struct_bytes=ctypes.sizeof(_capi.DetMaskPredictArgs), K=K, NC=NC, x=_capi.ptr(frames), wd=_capi.ptr(weights),
+                                 bd=_capi.ptr(bias), wl=_capi.ptr(logit_weight), bl=_capi.ptr(logit_bias), labels=_capi.ptr(labels, torch.int64),
+                                 scores=_capi.ptr(scores), probs=_capi.ptr(probs), logits=_capi.ptr(logits))
+    _capi.call("hps_det_mask_predict", ctypes.byref(a), _capi.stream())
+    return probs, logits
+
+
+def paste_masks(mask_probs, boxes, image_size, threshold=None):
+    """hps_det_paste_masks (torchvision's paste_masks_in_image, padding 1) for ONE image: mask_probs (n, 28, 28) or (n, 1, 28, 28), boxes
+    (n, 4) in the image's pixels, image_size (H, W) -> (n, 1, H, W): float32 probabilities (torchvision does not threshold), or with
+    ``threshold`` in (0, 1) uint8 ``probability > threshold``.  One launch that writes every pixel; no synchronisation."""
+    threshold = _check_threshold(threshold)
+    _capi.require_device(mask_probs, "mask_probs")
+    _capi.require_device(boxes, "boxes")
+    S = _capi.DET_MASK_SIZE
+    n = mask_probs.shape[0]
+    if tuple(mask_probs.shape) not in ((n, S, S), (n, 1, S, S)) or tuple(boxes.shape) != (n, 4):
+        raise _capi.HpsError("paste_masks: mask_probs (n, %d, %d) and boxes (n, 4), got %s and %s" % (S, S, tuple(mask_probs.shape), tuple(boxes.shape)))
+    H, W = int(image_size[0]), int(image_size[1])
+    probs, boxes = _capi.f32c(mask_probs), _capi.f32c(boxes)
+    out = torch.empty(n, 1, H, W, device=probs.device, dtype=torch.float32 if threshold is None else torch.uint8)
+    a = _capi.DetPasteMasksArgs(struct_bytes=ctypes.sizeof(_capi.DetPasteMasksArgs), n=n, H=H, W=W, binary=0 if threshold is None else 1,
+                                threshold=0.0 if threshold is None else threshold, probs=_capi.ptr(probs), boxes=_capi.ptr(boxes),
+                                out=_capi._P(out.data_ptr()))
+    _capi.call("hps_det_paste_masks", ctypes.byref(a), _capi.stream())
+    return out
 
 
 class MaskRCNNBoxDetector(DeviceStateModule):
@@ -270,7 +353,7 @@ class MaskRCNNBoxDetector(DeviceStateModule):
         self.roi_heads.box_predictor = nn.Module()
         self.roi_heads.box_predictor.cls_score = nn.Linear(1024, self.num_classes)
         self.roi_heads.box_predictor.bbox_pred = nn.Linear(1024, 4 * self.num_classes)
-        # the mask branch: held for strict loading, never run
+        # the mask branch: run by mask_branch (detect_padded / forward with masks=True)
         self.roi_heads.mask_head = nn.Module()
         for i in range(1, 5):
             setattr(self.roi_heads.mask_head, "mask_fcn%d" % i, conv(256, 256, 3))
@@ -313,7 +396,12 @@ class MaskRCNNBoxDetector(DeviceStateModule):
                     "fc6": _wide_layer(w6[:, :, None, None], rh.box_head.fc6.bias, 0),
                     "fc7": _wide_layer(rh.box_head.fc7.weight.detach()[:, :, None, None], rh.box_head.fc7.bias, 0),
                     "cls": fc(rh.box_predictor.cls_score), "box": fc(rh.box_predictor.bbox_pred),
-                    "anchors": [base_anchors(s) for s in _LEVEL_SIZES]}
+                    "anchors": [base_anchors(s) for s in _LEVEL_SIZES],
+                    "mask": [W(getattr(rh.mask_head, "mask_fcn%d" % i)) for i in range(1, 5)],
+                    "mask_wd": mask_weights(rh.mask_predictor.conv5_mask.weight),
+                    "mask_bd": rh.mask_predictor.conv5_mask.bias.detach().float().contiguous().clone(),
+                    "mask_wl": rh.mask_predictor.mask_fcn_logits.weight.detach().float().reshape(self.num_classes, -1).contiguous().clone(),
+                    "mask_bl": rh.mask_predictor.mask_fcn_logits.bias.detach().float().contiguous().clone()}
         self._prepared = prep
         return prep
 
@@ -485,11 +573,14 @@ class MaskRCNNBoxDetector(DeviceStateModule):
 
     # ---- stage 5 ----
     @torch.no_grad()
-    def detections(self, feats, props, head, with_probs=False):
+    def detections(self, feats, props, head, with_probs=False, with_rois=False):
         """Stage 5: ``boxes`` (B, D, 4) in the input images' pixels, ``labels`` (B, D) int64, ``scores`` (B, D) descending (absent rows
         zero), ``counts`` (B,) int32 on the device; and the intermediate ``cand_boxes`` (B, NC - 1, R, 4) / ``cand_scores`` (B, NC - 1, R)
         after soft-max, decode, clip and the filters (resized-image pixels, proposal order), ``order`` (each class's descending order),
-        ``keep_scores`` (B, NC - 1, R) after the per-class NMS in that order, ``probs`` (B, R, NC) with ``with_probs``.  No synchronisation."""
+        ``keep_scores`` (B, NC - 1, R) after the per-class NMS in that order, ``probs`` (B, R, NC) with ``with_probs``.  With
+        ``with_rois`` (the mask branch's input): ``roi_boxes`` (B, D, 4), the rows of ``cand_boxes`` that hps_det_gather selects, before
+        its rescale (resized-image pixels; absent rows zero), and ``roi_scores`` (B, D), the presence mark of the library: the score
+        where the row is present, -infinity where it is absent (``scores`` has 0 there).  No synchronisation."""
         sizes, orig = feats["sizes"], feats["orig"]
         B, R, _ = props["boxes"].shape
         NC, dev = self.num_classes, props["boxes"].device
@@ -516,23 +607,79 @@ class MaskRCNNBoxDetector(DeviceStateModule):
                                 counts=_capi.ptr(counts, torch.int32))
         _set_sizes(g.size, [s + o for s, o in zip(sizes, orig)])
         _capi.call("hps_det_gather", ctypes.byref(g), _capi.stream())
-        return {"boxes": ob, "labels": ol, "scores": osc, "counts": counts, "cand_boxes": cb, "cand_scores": cs, "order": order,
-                "keep_scores": keep.view(B, NC - 1, R), "probs": probs}
+        out = {"boxes": ob, "labels": ol, "scores": osc, "counts": counts, "cand_boxes": cb, "cand_scores": cs, "order": order,
+               "keep_scores": keep.view(B, NC - 1, R), "probs": probs}
+        if with_rois:
+            # hps_det_gather's own selection: position (c - 1, p) of the top-k is proposal order[b, c - 1, p] of class c
+            r = order.view(B, (NC - 1) * R).gather(1, tidx)
+            flat = tidx - tidx % R + r
+            present = tvals > _NEG_INF
+            out["roi_boxes"] = (cb.view(B, (NC - 1) * R, 4).gather(1, flat[:, :, None].expand(B, D, 4)) * present[:, :, None]).contiguous()
+            out["roi_scores"] = tvals
+        return out
+
+    # ---- the mask branch ----
+    def _mask_plan(self, prep, K, device):
+        def build():
+            F, C = _capi.DET_MASK_BINS + 2, _capi.DET_MASK_CHANNELS
+            roi, f1, f2 = (torch.zeros(K, F, F, C, device=device, dtype=torch.float32) for _ in range(3))
+            m = prep["mask"]
+            ops, ws = _wide_ops([(m[0], roi, 1, f1, 1, True), (m[1], f1, 1, f2, 1, True), (m[2], f2, 1, f1, 1, True), (m[3], f1, 1, f2, 1, True)], device)
+            return {"ops": ops, "scratch": ws, "roi": roi, "features": f2, "keep": f1}
+        return self._derived("mask", (K, _capi.stream().value), build, limit=4)
+
+    @torch.no_grad()
+    def mask_branch(self, feats, dets, with_logits=True):
+        """The mask branch on ``features``' and ``detections(..., with_rois=True)``'s output: ``roi`` (B D, 16, 16, 256), the 14 x 14
+        RoIAlign of the detections' boxes (resized-image pixels) over P2..P5 inside a zero halo; ``features`` (B D, 16, 16, 256) after
+        the four 3x3 + ReLU layers (the wide kernel, K in slices of 256 products); ``probs`` / ``logits`` (B, D, 28, 28) from
+        hps_det_mask_predict: the sigmoid of the detection's own class's logit, and the logit (None without ``with_logits``).  Absent
+        rows are zero.  ``roi`` and ``features`` are the module's buffers.  No synchronisation."""
+        prep = self._prepared or self.prepare()
+        if "roi_boxes" not in dets:
+            raise _capi.HpsError("mask_branch: the detections carry no roi_boxes; call detections(..., with_rois=True)")
+        boxes, scores, labels = dets["roi_boxes"], dets["roi_scores"], dets["labels"]
+        B, D, _ = boxes.shape
+        plan = self._mask_plan(prep, B * D, boxes.device)
+        a = _capi.DetRoiAlignArgs(struct_bytes=ctypes.sizeof(_capi.DetRoiAlignArgs), B=B, R=D, C=_capi.DET_MASK_CHANNELS, bins=_capi.DET_MASK_BINS,
+                                  n_levels=4, boxes=_capi.ptr(boxes), scores=_capi.ptr(scores), y=_capi.ptr(plan["roi"]))
+        for l, frame in enumerate(feats["P"]):
+            lv = a.level[l]
+            lv.x, lv.h, lv.w, lv.pad, lv.scale = _capi.ptr(frame), frame.shape[1] - 2, frame.shape[2] - 2, 1, 1.0 / (4 << l)
+        _capi.call("hps_det_roi_align_halo", ctypes.byref(a), 1, _capi.stream())
+        _capi.run_enc_ops(plan["ops"], 0, len(plan["ops"]))
+        probs, logits = mask_predict(plan["features"], prep["mask_wd"], prep["mask_bd"], prep["mask_wl"], prep["mask_bl"], labels.view(B * D),
+                                     scores.view(B * D), with_logits=with_logits)
+        S = _capi.DET_MASK_SIZE
+        return {"roi": plan["roi"], "features": plan["features"], "probs": probs.view(B, D, S, S),
+                "logits": logits.view(B, D, S, S) if with_logits else None}
 
     # ---- the composition ----
-    def detect_padded(self, images, frame=None):
+    def detect_padded(self, images, frame=None, masks=False):
         """(boxes (B, D, 4), labels (B, D) int64, scores (B, D), counts (B,) int32), D = box_detections_per_img; rows past an image's
-        count are zero.  Everything stays on the device: no host synchronisation."""
+        count are zero.  With ``masks`` a fifth tensor, mask_probs (B, D, 28, 28): each detection's mask inside its box, before the
+        paste.  Everything stays on the device: no host synchronisation."""
         feats = self.features(images, frame)
         props = self.proposals(feats)
-        det = self.detections(feats, props, self.box_head(feats, props))
-        return det["boxes"], det["labels"], det["scores"], det["counts"]
+        det = self.detections(feats, props, self.box_head(feats, props), with_rois=bool(masks))
+        if not masks:
+            return det["boxes"], det["labels"], det["scores"], det["counts"]
+        return det["boxes"], det["labels"], det["scores"], det["counts"], self.mask_branch(feats, det, with_logits=False)["probs"]
 
-    def forward(self, images, frame=None):
+    def forward(self, images, frame=None, masks=False, mask_threshold=None):
         """[{"boxes": (n, 4), "labels": (n,) int64, "scores": (n,)}] per image, by descending score.  The last step reads the counts on
-        the host to size the returned tensors: the call's one synchronisation."""
-        boxes, labels, scores, counts = self.detect_padded(images, frame)
-        return [{"boxes": boxes[b, :n], "labels": labels[b, :n], "scores": scores[b, :n]} for b, n in enumerate(counts.tolist())]
+        the host to size the returned tensors: the call's one synchronisation.  With ``masks`` each dict gains ``"masks"`` (n, 1, H, W):
+        float32 probabilities in the input image's pixels as torchvision returns them, or uint8 ``probability > mask_threshold`` with a
+        ``mask_threshold`` in (0, 1); the paste (hps_det_paste_masks, one launch per image, only the n masks allocated) follows the
+        synchronisation."""
+        mask_threshold = _check_threshold(mask_threshold)
+        if not masks:
+            boxes, labels, scores, counts = self.detect_padded(images, frame)
+            return [{"boxes": boxes[b, :n], "labels": labels[b, :n], "scores": scores[b, :n]} for b, n in enumerate(counts.tolist())]
+        boxes, labels, scores, counts, probs = self.detect_padded(images, frame, masks=True)
+        sizes = [tuple(im.shape[-2:]) for im in images]
+        return [{"boxes": boxes[b, :n], "labels": labels[b, :n], "scores": scores[b, :n],
+                 "masks": paste_masks(probs[b, :n], boxes[b, :n], sizes[b], mask_threshold)} for b, n in enumerate(counts.tolist())]
 
 
 def maskrcnn_resnet50_fpn(pretrained=False, progress=True, num_classes=91, pretrained_backbone=False, **kwargs):

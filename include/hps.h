@@ -2042,6 +2042,10 @@ typedef struct hps_det_roi_align_args {
 } hps_det_roi_align_args;
 int hps_sizeof_det_roi_align_args(void);
 int hps_det_roi_align(const hps_det_roi_align_args* args /* HOST */, hps_stream_t stream);
+/* The same launch into a haloed frame per box: y (B, R, bins + 2 halo, bins + 2 halo, C), the bins x bins values in the interior (the
+ * same bits as hps_det_roi_align's) and the border written as zeros; an absent box writes a whole frame of zeros.  0 <= halo <= 8;
+ * halo 0 is hps_det_roi_align.  (B R, bins + 2, bins + 2, C) with halo 1 is the input frame of a 3x3 / pad 1 layer over B R maps. */
+int hps_det_roi_align_halo(const hps_det_roi_align_args* args /* HOST */, int halo, hps_stream_t stream);
 
 /* hps_det_box_decode  (RoIHeads.postprocess_detections up to the per-class NMS): logits (B, R, NC), deltas (B, R, 4 NC), proposals
  * (B, R, 4) present where prop_scores (B, R) > -infinity.  prob = exp(l_c - max) / sum_c' exp(l_c' - max) (sum in class order);
@@ -2085,6 +2089,62 @@ typedef struct hps_det_gather_args {
 } hps_det_gather_args;
 int hps_sizeof_det_gather_args(void);
 int hps_det_gather(const hps_det_gather_args* args /* HOST */, hps_stream_t stream);
+
+/* The mask branch (csrc/detector_mask.hip; RoIHeads' mask path, MaskRCNNPredictor, maskrcnn_inference, paste_masks_in_image -- the same
+ * caveat: a restatement that has not been run against torchvision).  Its RoIAlign is hps_det_roi_align_halo with 14 bins and halo 1,
+ * its four 3x3 layers run on hps_conv2d_bn_act_pad. */
+#define HPS_DET_MASK_BINS 14                                   /* the mask head's map: 14 x 14 */
+#define HPS_DET_MASK_CHANNELS 256
+#define HPS_DET_MASK_SIZE 28                                   /* the predicted mask: 28 x 28 */
+
+/* hps_det_mask_predict  (ConvTranspose2d(256, 256, 2, 2) + ReLU, the 1x1 logit of the detection's own class, sigmoid) in one launch on
+ * the fp32 matrix instructions.  x: K zero-haloed NHWC frames (K, 16, 16, 256), the interior (halo 1) is read.  Detection k with label
+ * c = labels[k], 1 <= c < NC, present where scores is NULL or scores[k] > -infinity:
+ *   t[co, 2 y + dy, 2 x + dx] = max(bd[co] + sum_ci x[k, y, x, ci] Wd[ci, co, dy, dx], 0),
+ *   logits[k, i, j] = bl[c] + sum_co wl[c, co] t[co, i, j],        probs[k, i, j] = 1 / (1 + exp(-logits[k, i, j])).
+ * The sum over ci is one fp32 multiply-add chain in ascending ci from 0 (v_mfma_f32_32x32x2_f32); the sum over co: with co = 32 t + 8 q
+ * + 4 h + e, a chain of fused multiply-adds over (q, e) ascending from 0 for each (t, h), those added over t ascending from 0, then
+ * h = 0 plus h = 1, then bl[c].  No atomics; a detection's bits depend on its own frame, label and the weights only.  The (K, 28, 28,
+ * 256) tensor is never written and no other class's logit is formed.  An absent detection and one with a label outside [1, NC) write
+ * zeros to probs and logits.  probs / logits (K, 28, 28); logits may be NULL.
+ * wd: Wd in the kernel-side form (4, 128, 64, 8): element [2 dy + dx][s][64-lane l][t] = Wd[2 s + (l >> 5)][32 t + (l & 31)][dy][dx]
+ * (16-byte aligned).  bd (256), wl (NC, 256) row-major, bl (NC), labels (K) int64. */
+typedef struct hps_det_mask_predict_args {
+    int struct_bytes;
+    int K, NC;
+    const float* x;
+    const float* wd;
+    const float* bd;
+    const float* wl;
+    const float* bl;
+    const int64_t* labels;
+    const float* scores;                                       /* (K) or NULL */
+    float* probs;
+    float* logits;                                             /* or NULL */
+} hps_det_mask_predict_args;
+int hps_sizeof_det_mask_predict_args(void);
+int hps_det_mask_predict(const hps_det_mask_predict_args* args /* HOST */, hps_stream_t stream);
+
+/* hps_det_paste_masks  (paste_masks_in_image with padding 1) for the n masks of ONE image: probs (n, 28, 28), boxes (n, 4) x1 y1 x2 y2
+ * in the image's pixels -> out (n, H, W); every element is written (16-byte stores; out 16-byte aligned), no memset is needed.
+ * Mask k gets a ring of zeros (30 x 30, m[i][j], i, j in [0, 30)).  Its box, every operation rounded once in fp32 (no fused
+ * multiply-add):  w_half = (x2 - x1) 0.5,  x_c = (x2 + x1) 0.5,  w_half = w_half float(30 / 28),  ex0 = x_c - w_half,
+ * ex1 = x_c + w_half (likewise y);  X0 = int(ex0), X1 = int(ex1) toward zero (values beyond +-2^29 held there),
+ * w = max(X1 - X0 + 1, 1), h likewise.  Pixel (y, x) with max(X0, 0) <= x < min(X1 + 1, W) and max(Y0, 0) <= y < min(Y1 + 1, H):
+ *   fx = max((x - X0 + 1/2) (30 / w) - 1/2, 0) with the quotient in fp32, j0 = min(int(fx), 29), j1 = min(j0 + 1, 29), lx = fx - j0
+ *   (likewise fy, i0, i1, ly);  value = (1 - ly) ((1 - lx) m[i0][j0] + lx m[i0][j1]) + ly ((1 - lx) m[i1][j0] + lx m[i1][j1]);
+ * every other pixel 0.  binary 0: out is float32, the value (a probability; torchvision does not threshold).  binary 1: out is uint8,
+ * 1 where value > threshold else 0, 0 < threshold < 1. */
+typedef struct hps_det_paste_masks_args {
+    int struct_bytes;
+    int n, H, W, binary;
+    float threshold;
+    const float* probs;
+    const float* boxes;
+    void* out;
+} hps_det_paste_masks_args;
+int hps_sizeof_det_paste_masks_args(void);
+int hps_det_paste_masks(const hps_det_paste_masks_args* args /* HOST */, hps_stream_t stream);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus
